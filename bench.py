@@ -3,16 +3,17 @@
 on synthetic RWARE tiny-4ag-shaped inputs, 4096 envs per GPU, rollout_length 128, 4 epochs x 2
 minibatches (BASELINE.json configs[1]).  One "step" = one full PPO update.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  env-steps are counted exactly like the reference
 (mava/systems/ppo/ff_mappo.py:468-474,496-504): D * updates * T * U * E over the wall time of the
-updates with device syncs on both sides; `value` is the MEDIAN of --repeats such learn(state) calls of --steps updates.
-Kernel durations for the roofline objects are measured live with HIP events on the launch stream in a separate
-instrumented pass of the same updates (outside every timed call).  The default single-GPU run then times the secondary
-claims (exact-f32 arithmetic, the reference's U = 2 replica split, ff_ippo, BASELINE config 4) the same way and attaches
-them under "secondary".
+updates with device syncs on both sides.  A plain run sets up, runs W untimed updates, times ONE learn(state) call of
+exactly K updates (`value` is the MEDIAN of --repeats such calls, default 1) and prints the line; --dump-outputs writes
+what that call returned for its last update.  --full then also measures, outside every timed call: kernel durations for
+the roofline objects (HIP events on the launch stream in a separate instrumented pass of the same updates), the
+secondary claims (exact-f32 arithmetic, the reference's U = 2 replica split, ff_ippo, BASELINE config 4; single GPU)
+and the CPU baseline, attached to the same line.
 """
 from __future__ import annotations
 
@@ -166,23 +167,23 @@ def build_learner(system: str, env_name: str, scenario: str, envs_per_gpu: int, 
     return learn, state, learn.learner, cfg
 
 
-def time_learn(learn, state, L, steps: int, warmup: int, repeats: int, world: int):
+def time_learn(learn, state, L, steps: int, warmup: int, repeats: int, world: int, settle: bool = True):
     """`warmup` untimed updates, then `repeats` timed learn(state) calls of exactly `steps` updates each, every call
     bracketed by a barrier + device synchronisation on both sides (the reference's own window, ff_mappo.py:496-504).
     Returns the per-call wall times (seconds, this rank) and the last output."""
     for i in range(warmup):
         L.update(0)
         torch.cuda.synchronize()
-    # untimed learn() calls on top of the warm-up updates until the device has been busy for >= 0.5 s (at least one call):
-    # the first calls through the boundary pay one-off costs (permutation / statistics buffers, the caching allocator's
-    # growth for the stacked output leaves) and a fresh box holds low clocks for the first few hundred milliseconds of
-    # load - both showed as 1.5 - 3x slower first calls next to identical later ones
+    # settle: untimed learn() calls on top of the warm-up updates until the device has been busy for >= 0.5 s (at least
+    # one call): the first calls through the boundary pay one-off costs (permutation / statistics buffers, the caching
+    # allocator's growth for the stacked output leaves) and a fresh box holds low clocks for the first few hundred
+    # milliseconds of load - both showed as 1.5 - 3x slower first calls next to identical later ones.  The headline does
+    # not settle: the number of updates before its timed call must be `warmup`, whatever the clock says.
     t_w = time.perf_counter()
-    while True:
+    while settle:
         state = learn(state).learner_state
         torch.cuda.synchronize()
-        if time.perf_counter() - t_w >= 0.5:
-            break
+        settle = time.perf_counter() - t_w < 0.5
     times, out_state = [], None
     for _ in range(repeats):
         _sync_barrier(world)
@@ -199,6 +200,59 @@ def time_learn(learn, state, L, steps: int, warmup: int, repeats: int, world: in
 def _median(xs):
     ys = sorted(xs)
     return ys[len(ys) // 2]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _tensor_leaves(prefix: str, x):
+    """(path, tensor) of every tensor leaf of a tree of NamedTuples / dicts / lists (other leaves are skipped)."""
+    if isinstance(x, torch.Tensor):
+        yield prefix, x
+    elif hasattr(x, "_fields"):
+        for k in x._fields:
+            yield from _tensor_leaves(f"{prefix}.{k}", getattr(x, k))
+    elif isinstance(x, dict):
+        for k, v in x.items():
+            yield from _tensor_leaves(f"{prefix}.{k}", v)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            yield from _tensor_leaves(f"{prefix}.{i}", v)
+
+
+def dump_outputs(out, path: str) -> None:
+    """--dump-outputs: what the timed learn(state) call returned for its LAST update - the whole learner state after it and
+    that update's slice ([:, -1] of the (1, steps, ...) leaves) of the episode and train metrics - as path/<leaf>.npy,
+    float32 (float64 for float64, integer and bool leaves: exact).  If all of it would exceed 64 MB, every leaf of more
+    than `cap` elements keeps `cap` of them (flattened, at indices drawn with a fixed seed: the same ones for the same
+    shape in every run), so that two builds can be compared entry for entry."""
+    import numpy as np
+
+    leaves = list(_tensor_leaves("learner_state", out.learner_state))
+    for group in ("episode_metrics", "train_metrics"):
+        leaves += [(name, t[:, -1]) for name, t in _tensor_leaves(group, getattr(out, group))]
+    host = []
+    for name, t in leaves:
+        dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        host.append((name, t.detach().to("cpu", dt).numpy()))
+    cap = max(a.size for _, a in host)
+    if sum(a.nbytes for _, a in host) > DUMP_LIMIT_BYTES:
+        lo, hi = 0, cap  # the largest cap whose sampled leaves fit
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if sum(min(a.size, mid) * a.itemsize for _, a in host) <= DUMP_LIMIT_BYTES:
+                lo = mid
+            else:
+                hi = mid - 1
+        cap = lo
+    os.makedirs(path, exist_ok=True)
+    sampled = 0
+    for name, a in host:
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+            sampled += 1
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    log(f"outputs of the last timed update: {len(host)} arrays under {path}" + (f" ({sampled} sampled to {cap} entries)" if sampled else ""))
 
 
 def _graph_time_us(fn_of_set, n_sets: int, dev, n_launch: int = 20, reps: int = 5) -> float:
@@ -452,19 +506,25 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="timed learn() calls of --steps updates each; value / ms_per_step are those of the MEDIAN call")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed calls, write what the last one returned for its last update as DIR/<name>.npy "
+                         "(rank 0; float32 / float64, at most 64 MB, larger outputs as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the instrumented kernel-timer pass (roofline objects), the secondary "
+                         "workloads and the CPU baseline (each can still be left out with its --no-* option)")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU (arch.num_envs * update_batch_size)")
     ap.add_argument("--update-batch-size", type=int, default=1)
     ap.add_argument("--scenario", default="tiny-4ag")
     ap.add_argument("--system", default="ff_mappo", choices=["ff_mappo", "ff_ippo", "rec_mappo", "rec_ippo"])
     ap.add_argument("--env", default="rware", choices=["rware", "smax"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-envs", type=int, default=256)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-kernel-timers", action="store_true")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="--full without the instrumented kernel-timer pass")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workloads that the default single-GPU run times after the primary line's region")
+                    help="--full without the secondary workloads that a single-GPU run times after the primary line's region")
     ap.add_argument("--no-critic-aggregation", action="store_true",
                     help="centralised critic: one network pass per AGENT row (the reference's A identical passes) instead of one per (t,e) row")
     ap.add_argument("--action-head", default="discrete", choices=["discrete", "continuous"],
@@ -515,11 +575,24 @@ def main() -> None:
     central = args.system.endswith("mappo")
     if args.no_critic_aggregation:
         L.ctx.set(L.ctx.CRITIC_AGGREGATION, 0)
+    # The first two learn() calls of a process pay one-off costs of the boundary itself (the first launches of its torch
+    # kernels load their code objects; the f16-range guard takes a second path from the second call on): 16 and 87 ms
+    # more than later calls at 20 updates each on one MI355X.  Two calls of a throwaway learner of the same shape, one
+    # update each, pay them untimed, so that exactly args.warmup updates of THIS learner precede its timed call.
+    learn_w, state_w, _, _ = build_learner(args.system, args.env, args.scenario, args.envs, U, args.matmul, 1, 0, dev,
+                                           continuous=cont)
+    for _ in range(2):
+        state_w = learn_w(state_w).learner_state
+    torch.cuda.synchronize()
+    del learn_w, state_w
     log(f"setup done: {world} rank(s), E={E} U={U} T={T} A={A} Oa={L.Oa} Oc={L.Oc} matmul={args.matmul}")
     # ---- the timed region: `repeats` learn(state) calls of exactly args.steps updates each through the drop-in boundary
-    # (adopt + updates + the returned state's leaf stacking), no instrumentation inside; the line reports the MEDIAN call
+    # (adopt + updates + the returned state's leaf stacking), no instrumentation inside; the line reports the MEDIAN call.
+    # Exactly args.warmup updates precede it, so that the same arguments give the same inputs (and dumped outputs).
     repeats = max(1, args.repeats)
-    times, _out_state = time_learn(learn, state, L, max(args.steps, 1), args.warmup, repeats, world)
+    times, out_state = time_learn(learn, state, L, max(args.steps, 1), args.warmup, repeats, world, settle=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out_state, args.dump_outputs)
     rank_times = None
     if world > 1:
         import torch.distributed as dist
@@ -578,8 +651,8 @@ def main() -> None:
 
     default_shape = (args.envs == 4096 and args.update_batch_size == 1 and args.scenario == "tiny-4ag"
                      and args.system == "ff_mappo" and not continuous)
-    # ---- instrumented pass (NOT part of `value`): per-kernel HIP-event timings for the roofline objects
-    if not args.no_kernel_timers:
+    # ---- --full: instrumented pass (NOT part of `value`): per-kernel HIP-event timings for the roofline objects
+    if args.full and not args.no_kernel_timers:
         ff_t, rec_t, n_t = instrumented_pass(L, max(1, min(args.steps, 5 if hasattr(L, "_timed") else 2)), world)
         if rank == 0 and ff_t:
             out.update(ff_rooflines(L, args.matmul, ff_t, n_t, default_shape, args.no_critic_aggregation, continuous, dev))
@@ -587,10 +660,10 @@ def main() -> None:
             out.update(rec_rooflines(L, args.matmul, rec_t, n_t))
 
     Oa, Oc, nA = L.Oa, L.Oc, L.nA
-    # ---- secondary claims, driver-timed in the same run (single-GPU default run only; each a fresh learner with its own
-    # context handle, after the primary learner's buffers are released)
-    if rank == 0 and world == 1 and default_shape and not args.no_secondary:
-        del learn, state, L, _out_state
+    # ---- --full: secondary claims, driver-timed in the same run (single-GPU default shape only; each a fresh learner with
+    # its own context handle, after the primary learner's buffers are released)
+    if args.full and rank == 0 and world == 1 and default_shape and not args.no_secondary:
+        del learn, state, L, out_state
         torch.cuda.empty_cache()
         sec = {}
         try:
@@ -612,7 +685,7 @@ def main() -> None:
             log(f"secondary workloads stopped: {sec['error']}")
         out["secondary"] = sec
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.system.startswith("rec") and not continuous:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.system.startswith("rec") and not continuous:
         from oracle import rec_cpu_loop
 
         cores = usable_cores()
@@ -627,7 +700,7 @@ def main() -> None:
         }
         log(f"cpu baseline: {res['env_steps_per_sec']:,.0f} env-steps/s")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.system.startswith("ff") and not continuous:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.system.startswith("ff") and not continuous:
         from oracle import cpu_loop
 
         cores = usable_cores()

@@ -7,7 +7,7 @@ OUT=gpurun_out/$1; shift
 EXTRA="$@"
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 --no-secondary $EXTRA > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --no-secondary $EXTRA > $OUT/bench.json 2> $OUT/bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-kernel-timers --no-secondary --repeats 1 $EXTRA > $OUT/stats.json 2> $OUT/stats.err || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_r -- python3 bench.py --steps 1 --warmup 2 --no-cpu-baseline --no-kernel-timers --no-secondary --repeats 1 $EXTRA > /dev/null 2> $OUT/pmc_r.err || exit 1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_w -- python3 bench.py --steps 1 --warmup 2 --no-cpu-baseline --no-kernel-timers --no-secondary --repeats 1 $EXTRA > /dev/null 2> $OUT/pmc_w.err || exit 1
