@@ -228,6 +228,27 @@ int mava_synth_rware_step(int E, int A, int O, int n_actions, int gs_tiles, int 
                           float* reward, uint8_t* done, float* info_return, int32_t* info_length,
                           uint8_t* info_terminal, const int32_t* action, int reward_mode, mava_stream_t s);
 
+/* ---- Level-Based Foraging environment step (mava_amd/csrc/lbf.hip; rules in DESIGN.md "Level-Based Foraging",
+ *      restated in tests/lbf_model.py).  E environments of a G x G grid with A agents and F foods (A, F <= 16, G <= 32,
+ *      (G-2)^2 >= 9 (F-1) + 1, G^2 >= F + A, max_agent_level <= 1000).  Actions (E, A) int32: 0 NOOP, 1 UP, 2 DOWN,
+ *      3 LEFT, 4 RIGHT, 5 LOAD.  State (struct of arrays, advanced in place): agent_pos (E, A, 2), agent_level (E, A),
+ *      food_pos (E, F, 2), food_level (E, F), food_alive (E, F) u8, total_food_level (E) f32, step_count (E, A) and the
+ *      RecordEpisodeMetrics words run_return / run_length / ep_return / ep_length (E), as mava_synth_rware_step.
+ *      Outputs: agents_view (E, A, A + 3 (F + A)) = [one-hot id | raw view], global_state (E, 1, A * 3 (F + A)) = the
+ *      concatenated raw views, action_mask (E, A, 6) u8, obs_step_count (E, A); reward (E, A) (team: the agents' summed
+ *      reward repeated per agent; individual_rewards 1: each agent's own), done (E, A), info_* (E).
+ *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a terminal step regenerates
+ *      that env and returns the reset observation (AutoResetWrapper).  Randomness: Philox4x32-10 with key `seed`, counter
+ *      (env_offset + e, t + *t_base, block, "LBFS"); t_base (a device word, may be NULL) is added on the device, so the
+ *      step replays from a captured graph.  No host state, no synchronisation. */
+int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop, int individual_rewards,
+                  int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
+                  int32_t* agent_pos, int32_t* agent_level, int32_t* food_pos, int32_t* food_level, uint8_t* food_alive,
+                  float* total_food_level, int32_t* step_count, float* run_return, int32_t* run_length,
+                  float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                  uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                  int32_t* info_length, uint8_t* info_terminal, const int32_t* action, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments

@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "ppo_train_w8.hip",
     "rollout_h2.hip",
     "synth_rware.hip",
+    "lbf.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",
     "rec_gru.hip",
