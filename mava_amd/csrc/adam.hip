@@ -52,8 +52,8 @@ struct AdamTail {
   const double* norm_partials;
   int n_partial;
   unsigned int* ticket;
-  const float* pack_params;  // start of the network whose W1 is re-split (inside p)
-  int pack_din;
+  int pack_offset;  // start of the network whose W1 is re-split, as an offset into p: the pack reads what this launch wrote
+  int pack_din;     // through p itself, not through a second (restrict) pointer to the same memory
   uint4* w1_split;
 };
 
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void clip_adam_kernel(
     if constexpr (PACK > 0) {
       if (s_last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the other blocks' parameter stores, not this CU's cached lines
-        h2::pack_w1_body<PACK>(tail.pack_params, tail.pack_din, tail.w1_split, threadIdx.x, h2::W_SCALE_CRITIC);
+        h2::pack_w1_body<PACK>(p + tail.pack_offset, tail.pack_din, tail.w1_split, threadIdx.x, h2::W_SCALE_CRITIC);
       }
     }
   }
@@ -406,7 +406,7 @@ extern "C" int mava_ppo_finish_f32(mava_ctx* ctx, const float* slab_a, long stri
   AdamSegs segs = {};
   segs.off[0] = 0; segs.off[1] = Pa; segs.off[2] = Pa + Pc;
   segs.lr[0] = lr_a; segs.lr[1] = lr_c;
-  AdamTail tail = {reduced ? nullptr : partials, nblk, ticket, nullptr, 0, nullptr};
+  AdamTail tail = {reduced ? nullptr : partials, nblk, ticket, 0, 0, nullptr};
   // the wide f16x2 critic (96 .. 287 inputs) reads W1 through a pre-split copy: re-split it here, from the parameters this
   // launch writes, and mark the handle's copy fresh - the next critic launch of the handle then skips its own pack launch
   const int steps = (critic_din + 1 + 15) / 16;
@@ -415,7 +415,7 @@ extern "C" int mava_ppo_finish_f32(mava_ctx* ctx, const float* slab_a, long stri
   if (pack) {
     void*& slot = ctx->w1_split[1];
     if (slot == nullptr) MAVA_HIP_CHECK(hipMalloc(&slot, h2::W1_SPLIT_BYTES));
-    tail.pack_params = p + Pa;
+    tail.pack_offset = Pa;
     tail.pack_din = critic_din;
     tail.w1_split = static_cast<uint4*>(slot);
   }
@@ -430,6 +430,11 @@ extern "C" int mava_ppo_finish_f32(mava_ctx* ctx, const float* slab_a, long stri
   else FINISH_ADAM(0);
 #undef FINISH_ADAM
   MAVA_LAUNCH_CHECK();
-  if (pack) ctx->w1_fresh[1] = 1;
+  if (pack) {  // the key of the copy (ctx.h): the critic's parameters, width and the steps of the instantiation that packed it
+    ctx->w1_fresh[1] = 1;
+    ctx->w1_key_params[1] = p + Pa;
+    ctx->w1_key_din[1] = critic_din;
+    ctx->w1_key_steps[1] = steps <= 12 ? 12 : 18;
+  }
   return MAVA_OK;
 }

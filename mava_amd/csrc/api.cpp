@@ -33,7 +33,11 @@ extern "C" int mava_ctx_create(mava_ctx** out) {
   c->train_variant = 0;
   c->w8_launches = 0;
   c->w1_split[0] = c->w1_split[1] = nullptr;
-  c->w1_fresh[0] = c->w1_fresh[1] = 0;
+  for (int i = 0; i < 2; ++i) {
+    c->w1_fresh[i] = 0;
+    c->w1_key_params[i] = nullptr;
+    c->w1_key_din[i] = c->w1_key_steps[i] = 0;
+  }
   *out = c;
   return MAVA_OK;
 }
@@ -52,6 +56,7 @@ extern "C" int mava_ctx_set(mava_ctx* c, int key, long value) {
     case CTX_MATMUL_MODE:
       MAVA_ARG_CHECK(value == 0 || value == 1, 1, "mava_ctx_set: matmul mode %ld (0 = exact f32, 1 = f16x2)", value);
       c->matmul_mode = (int)value;
+      c->w1_fresh[0] = c->w1_fresh[1] = 0;  // (launches of the other arithmetic do not read the copy: it may go stale meanwhile)
       return MAVA_OK;
     case CTX_CRITIC_AGGREGATION: c->critic_aggregation = value ? 1 : 0; return MAVA_OK;
     case CTX_GAE_VARIANT: c->gae_variant = (int)value; return MAVA_OK;

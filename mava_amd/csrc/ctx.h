@@ -15,9 +15,13 @@ struct mava_ctx {
   long h2_launches;        // diagnostic: gradient launches of this handle that ran on the f16x2 kernels
   long w8_launches;        // diagnostic: ... of which on the eight-wave kernel (ppo_train_w8.hip)
   void* w1_split[2];       // f16x2, inputs wider than 95: pre-split W1 in fragment order (actor, critic), lazily allocated
-  int w1_fresh[2];         // one-shot: the copy already matches the parameters of the NEXT gradient launch (written by the Adam
-                           // launch of mava_ppo_finish_f32); cleared by that launch, and by the caller whenever parameters may
-                           // have changed in between (MAVA_CTX_W1_SPLIT_FRESH)
+  int w1_fresh[2];         // one-shot: the copy holds W1 of the parameters named by w1_key (written by the Adam launch of
+                           // mava_ppo_finish_f32).  Cleared by the next gradient launch of that kind, whichever kernel it runs on,
+                           // by mava_ctx_set(MAVA_CTX_MATMUL_MODE), and by the caller (MAVA_CTX_W1_SPLIT_FRESH)
+  const float* w1_key_params[2];  // ... key of that copy: the network's parameters, its input width and 16-input steps (the
+  int w1_key_din[2];              // instantiation's, 12 or 18); a wide launch skips its own pack only when all three match.  What the
+  int w1_key_steps[2];            // key cannot see: a caller who rewrites the CONTENTS of the same buffer between the finish launch and
+                                  // the next gradient launch must clear the flag
 };
 
 static inline int mava_ctx_matmul_mode(const mava_ctx* c) { return c ? c->matmul_mode : 0; }

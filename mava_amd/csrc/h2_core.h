@@ -194,7 +194,7 @@ __device__ __forceinline__ void sw_write_image(u8* img, int r, int w, int h, con
 // (8 x STEPS <= 144 floats) is issued before the first is used: one round trip instead of one per few steps.
 // `scale` (a power of two): the weights are split as scale * w (the consumer unscales its f32 accumulator), see W_SCALE_CRITIC.
 template <int STEPS>
-__device__ __forceinline__ void pack_w1_body(const float* __restrict__ P, int din, uint4* __restrict__ out, int tid, float scale) {
+__device__ __forceinline__ void pack_w1_body(const float* P, int din, uint4* __restrict__ out, int tid, float scale) {
   const int w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   float v[STEPS][8];
   // pass 1: nothing but loads (rows past din clamped to a valid address); pass 2: select, scale, split.  A select or a

@@ -1074,9 +1074,9 @@ extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int 
   tk.old_value = old_value; tk.targets = targets; tk.clip_eps = clip_eps; tk.vf_coef = vf_coef;
   tk.slab = slab; tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
-  if (mava_ctx_matmul_mode(ctx) == 1) {
-    const int rc = mava_train_h2_launch(ctx, tk, n_slab, false, s);
-    if (rc <= 0) return rc;
-  }
+  int rc = 1;
+  if (mava_ctx_matmul_mode(ctx) == 1) rc = mava_train_h2_launch(ctx, tk, n_slab, false, s);
+  if (ctx != nullptr) ctx->w1_fresh[1] = 0;  // one-shot whichever kernel takes the launch (the exact-f32 one does not read the copy)
+  if (rc <= 0) return rc;
   return dispatch_kt<1, false>(tk, n_slab, s);
 }

@@ -1027,8 +1027,11 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
     void*& slot = ctx->w1_split[ACTOR ? 0 : 1];
     if (slot == nullptr) MAVA_HIP_CHECK(hipMalloc(&slot, W1_SPLIT_BYTES));
     uint4* const buf = static_cast<uint4*>(slot);
-    int& fresh = ctx->w1_fresh[ACTOR ? 0 : 1];  // set by mava_ppo_finish_f32: its Adam launch has already re-split these weights
-    if (!fresh) {
+    // set by mava_ppo_finish_f32: its Adam launch has already re-split W1 - of the parameters, width and steps in the key
+    const int kind = ACTOR ? 0 : 1;
+    int& fresh = ctx->w1_fresh[kind];
+    const bool keyed = ctx->w1_key_params[kind] == tk.params && ctx->w1_key_din[kind] == tk.din && ctx->w1_key_steps[kind] == S1;
+    if (!(fresh && keyed)) {
       hipLaunchKernelGGL((pack_w1_kernel<S1>), dim3(1), dim3(256), 0, s, tk.params, tk.din, buf, ACTOR ? 1.0f : W_SCALE_CRITIC);
       MAVA_LAUNCH_CHECK();
     }

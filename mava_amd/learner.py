@@ -303,6 +303,8 @@ class FFLearner:
                 net.flat_from_tree(st.mu, self.m[sl])
                 net.flat_from_tree(st.nu, self.v[sl])
                 self.count[i] = int(st.count.reshape(-1)[0])
+            # the same buffer with other contents: the W1 copy the last finish launch left in the handle is stale
+            self.ctx.set(self.ctx.W1_SPLIT_FRESH, 0)
 
     # ------------------------------------------------------------------------------------ update
     def _rollout(self, n: int) -> None:

@@ -590,6 +590,79 @@ def test_fused_tail_equals_separate_launches(dev, din_c, mode, big):
         assert torch.equal(outs[0], outs[1]), "critic gradient on the W1 copy re-split inside the Adam launch"
 
 
+def _critic_case(rng, flat, din, TE, A):
+    """Shared-row critic inputs for the `flat` network (x_share = A) with old values on both sides of the clip range."""
+    gs = rng.standard_normal((TE, din)).astype(np.float32)
+    v_now = po.mlp_forward(po.mlp_unflatten(flat.astype(np.float64), din, 1), gs.astype(np.float64))[:, 0]
+    v_rows = np.repeat(v_now, A)
+    old_v = (v_rows + rng.standard_normal(TE * A) * 0.2).astype(np.float32)
+    tgt = (v_rows + rng.standard_normal(TE * A)).astype(np.float32)
+    return gs, old_v, tgt
+
+
+@pytest.mark.parametrize("seq", ["other_params", "other_width", "mode_switch"])
+def test_w1_copy_is_never_stale(dev, seq):
+    """mava_ppo_finish_f32 leaves the wide critic's W1 re-split in the handle for the next critic launch, which then skips its
+    own pack.  That copy belongs to ONE network (parameters, input width, steps): a launch on another buffer of the same or
+    another width, or a launch after the flag outlived a change of the parameters (matmul mode switched, an exact f32 critic
+    launch that does not read the copy, a plain Adam step on the same buffer) must re-split W1 itself.  The slabs
+    must be bit for bit those of a fresh handle, and the gradient within the kernels' 1e-4 of the float64 oracle."""
+    from mava_amd import ops
+    from mava_amd._lib import Ctx
+
+    rng = np.random.default_rng(11)
+    din_a, nA, din_c, n_slab = 70, 5, 264, 7
+    Pa, Pc = ops.mlp_param_count(din_a, nA), ops.mlp_param_count(din_c, 1)
+    P = Pa + Pc
+    p = _t((rng.standard_normal(P) * 0.1).astype(np.float32), dev)
+    m, v = torch.zeros(P, device=dev), torch.zeros(P, device=dev)
+    count = torch.zeros(2, dtype=torch.int32, device=dev)
+    g = torch.zeros(P + 4, device=dev)
+    slab_a = _t((rng.standard_normal((n_slab, Pa + 2)) * 0.3 / n_slab).astype(np.float32), dev)
+    slab_c = _t((rng.standard_normal((n_slab, Pc + 2)) * 0.3 / n_slab).astype(np.float32), dev)
+    kw = dict(max_norm=0.5, decay=False, steps_per_update=1, num_updates=1, vf_coef=0.5, ent_coef=0.01)
+    ctx = Ctx("f16x2")
+    ops.ppo_finish(ctx, slab_a, slab_c, Pa, Pc, g, p, m, v, count, 1e-3, 1e-3, grad_scale=1.0,
+                   metrics_out=torch.zeros(4, device=dev), critic_din=din_c, workspace=ops.ppo_finish_workspace(Pa, Pc, dev), **kw)
+    assert ctx.get(ctx.W1_SPLIT_FRESH) == 1, "the finish launch re-split the wide critic's W1 into the handle"
+
+    TE, A = 64, 4
+    if seq in ("other_params", "other_width"):  # another parameter buffer, of the same width / of 150 inputs (12 steps, not 18)
+        din = din_c if seq == "other_params" else 150
+        params = _t((rng.standard_normal(ops.mlp_param_count(din, 1)) * 0.1).astype(np.float32), dev)
+    else:
+        din = din_c
+        params = p[Pa:]
+        # the flag outlives a mode switch and an exact-f32 critic launch; a plain Adam step then moves p under the copy
+        ctx.set(ctx.MATMUL_MODE, 0)
+        flat = params.cpu().numpy()
+        gs, ov, tg = _critic_case(rng, flat, din, TE, A)
+        ops.ppo_critic_grad(params, _t(gs, dev), A, _t(ov, dev), _t(tg, dev), None, 0, TE, A, 0.2, 0.5,
+                            torch.zeros((3, Pc + 2), device=dev), ctx=ctx)
+        ops.clip_adam(p, g, m, v, count, [0, Pa, P], [1e-3, 1e-3], grad_scale=1.0, loss_sums=g[P:], **kw)
+        ctx.set(ctx.MATMUL_MODE, 1)
+    torch.cuda.synchronize()
+    flat = params.cpu().numpy()
+    gs, ov, tg = _critic_case(rng, flat, din, TE, A)
+    Pn = flat.size
+    slabs = []
+    for c in (ctx, Ctx("f16x2")):
+        h2_before = c.h2_launches
+        slab = torch.zeros((3, Pn + 2), device=dev)
+        ops.ppo_critic_grad(params, _t(gs, dev), A, _t(ov, dev), _t(tg, dev), None, 0, TE, A, 0.2, 0.5, slab, ctx=c)
+        torch.cuda.synchronize()
+        assert c.h2_launches == h2_before + 1, "the wide f16x2 critic kernel took the launch"
+        slabs.append(slab)
+    assert ctx.get(ctx.W1_SPLIT_FRESH) == 0, "the fresh flag is one-shot"
+    assert torch.equal(slabs[0], slabs[1]), f"{seq}: critic gradient on a stale W1 copy"
+    got = slabs[0].sum(0).cpu().numpy()  # (3 slabs: the order of a float sum of three does not matter at 1e-4)
+    rows = np.arange(TE * A) // A
+    _, vl, want = po.critic_loss_and_grad(flat.astype(np.float64), din, gs[rows].astype(np.float64), ov.astype(np.float64),
+                                          tg.astype(np.float64), 0.2, 0.5)
+    assert_close(got[:Pn], want, 1e-4, f"{seq}: critic grad")
+    assert_close(got[Pn : Pn + 1], np.array([vl]), 1e-5, f"{seq}: value loss", scale=1.0)
+
+
 @pytest.mark.parametrize("exact_rows", ["all", "some"])
 def test_f16_exact_inputs_skip_the_low_term_with_the_same_bits(dev, exact_rows):
     """Observations that are exact in f16 (flags, one-hot ids, small integers: RobotWarehouse's agents_view) have a zero low

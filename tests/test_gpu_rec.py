@@ -298,6 +298,13 @@ def test_rec_learner_update_matches_oracle(dev, system, U, E, matmul):
     """End to end: the HIP recurrent learner against the whole-update oracle on identical inputs.  E = 64 switches the
     centralised critic to one sequence per ENV (the agents share the global state; the oracle, like the reference,
     evaluates all E*A tiled rows)."""
+    _rec_learner_vs_oracle(dev, system, U, E, matmul)
+
+
+def _rec_learner_vs_oracle(dev, system, U, E, matmul):
+    """test_rec_learner_update_matches_oracle's body, also run by tests/test_gpu_paths.py under other MAVA_REC_* paths."""
+    import os
+
     from mava_amd import envs
     from mava_amd.config import compose
     from mava_amd.systems.ppo import rec_ippo, rec_mappo
@@ -318,7 +325,7 @@ def test_rec_learner_update_matches_oracle(dev, system, U, E, matmul):
     env, _ = envs.make(cfg, add_global_state=central, device=dev)
     learn, actor_network, state = mod.learner_setup(env, (42, 7, 8), cfg, device=dev)
     L = learn.learner
-    assert L.critic_agg == (central and E == 64)
+    assert L.critic_agg == (central and E == 64 and os.environ.get("MAVA_REC_CRITIC_AGG", "1") != "0")
     assert state.hstates.policy_hidden_state.shape == (1, U, E, A, 128) and state.dones.shape == (1, U, E, A)
     assert state.hstates.critic_hidden_state.shape == (1, U, E, A, 128)
     k = state.params.actor_params["params"]["ScannedRNN_0"]["GRUCell_0"]["hz"]["kernel"]
@@ -358,6 +365,7 @@ def test_rec_learner_update_matches_oracle(dev, system, U, E, matmul):
     out = learn(L.learner_state())
     torch.cuda.synchronize()
     assert out.train_metrics["total_loss"].shape == (1, 2, U, K, M) and torch.isfinite(out.train_metrics["total_loss"]).all()
+    return L
 
 
 def test_rec_dense_any_t32_width(dev, rec_mode):
