@@ -253,6 +253,21 @@ int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int 
                   uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
                   int32_t* info_length, uint8_t* info_terminal, const int32_t* action, mava_stream_t s);
 
+/* The same step plus what AutoResetWrapper keeps in extras["real_next_obs"] (mava/wrappers/auto_reset_wrapper.py:52-101),
+ * for rec_iql's replay buffer: real_view (E, A, A + 3 (F + A)) / real_mask (E, A, 6) are the observation of the state
+ * the rules produced BEFORE any auto-reset (equal to agents_view / action_mask where the step did not end), and
+ * terminated (E) is 1 only when every food was eaten - a time-limit end is a truncation (termination vs truncation as in
+ * Jumanji's LBF).  None of the three is written on a reset call (they may then be NULL); otherwise they must not alias
+ * agents_view / action_mask.  Every other output equals mava_lbf_step's. */
+int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop, int individual_rewards,
+                            int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
+                            int32_t* agent_pos, int32_t* agent_level, int32_t* food_pos, int32_t* food_level, uint8_t* food_alive,
+                            float* total_food_level, int32_t* step_count, float* run_return, int32_t* run_length,
+                            float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                            uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                            int32_t* info_length, uint8_t* info_terminal, const int32_t* action, float* real_view,
+                            uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments
@@ -419,6 +434,48 @@ int mava_rec_step_packed_f32(const void* pack_a, const void* pack_c, const float
                              const float* critic_params, int critic_din, const float* critic_input, int critic_share,
                              const uint8_t* done_c, int done_c_stride, const float* h_critic_in, float* h_critic_out,
                              int rows_c, int value_broadcast, float* value, mava_stream_t s);
+
+/* ---- rec_iql (mava/systems/q_learning/rec_iql.py; csrc/rec_step.hip, csrc/q_learning.hip) ----
+ * Acting step (:241-276): the recurrent Q network of mava_rec_step_f32's actor (same flat parameters, same T32 hidden
+ * state, reset where done), then MaskedEpsGreedyDistribution (mava/distributions.py:94-138): greedy action = the first
+ * argmax of where(mask, q, finfo(f32).min); with probability eps a uniformly drawn valid action instead.  Word x of Philox
+ * (row_offset + row, step, 0, "QEPS") with key seed decides (u01_open(x) < eps), word y picks the valid action
+ * floor(y * n_valid / 2^32).  rows a multiple of 32, 1 <= n_actions <= 16; q_out (rows, n_actions) or NULL. */
+int mava_rec_q_step_f32(const float* params, int din, int n_actions, const float* agents_view, const uint8_t* action_mask,
+                        const uint8_t* done, const float* h_in, float* h_out, int rows, float eps, uint64_t seed, uint32_t step,
+                        uint32_t row_offset, int32_t* action, float* q_out, mava_stream_t s);
+/* Replay add (flashbax add with a time axis of 1): writes time slot `slot` of every field for all E envs into buffers laid
+ * out (E, capacity, A, ...): obs / next_obs (.., O) f32, action_mask / next_mask (.., n_actions) u8, action i32, reward
+ * f32, terminal u8 (the per-env flag `terminal` (E) repeated per agent), term_or_trunc u8.  Inputs are (E, A, ...). */
+int mava_replay_add_f32(int E, int A, int O, int n_actions, int capacity, int slot, const float* obs, const uint8_t* action_mask,
+                        const int32_t* action, const float* reward, const uint8_t* terminal, const uint8_t* term_or_trunc,
+                        const float* next_obs, const uint8_t* next_mask, float* b_obs, uint8_t* b_mask, int32_t* b_action,
+                        float* b_reward, uint8_t* b_terminal, uint8_t* b_term_or_trunc, float* b_next_obs,
+                        uint8_t* b_next_mask, mava_stream_t s);
+/* Replay sample: B windows of S consecutive steps.  Sample b draws Philox (b, counter, 0, "RBSM") with key seed: env =
+ * floor(x E / 2^32), k = floor(y n_win / 2^32) with filled = min(n_added, capacity) and n_win = filled - S + 1; the window
+ * starts at step n_added - filled + k (slot modulo capacity), so it lies in the filled region and never crosses the write
+ * head.  Every field is gathered time-major (S, Rp, ...) with rows b * A + agent; rows from B * A to Rp (a multiple of 32)
+ * are zero with term_or_trunc = 1.  pairs (B, 2) i32 = (env, start slot). */
+int mava_replay_sample_f32(int E, int A, int O, int n_actions, int capacity, uint32_t n_added, int B, int S, int Rp, uint64_t seed,
+                           uint32_t counter, const float* b_obs, const uint8_t* b_mask, const int32_t* b_action,
+                           const float* b_reward, const uint8_t* b_terminal, const uint8_t* b_term_or_trunc,
+                           const float* b_next_obs, const uint8_t* b_next_mask, float* obs, uint8_t* action_mask, int32_t* action,
+                           float* reward, uint8_t* terminal, uint8_t* term_or_trunc, float* next_obs, uint8_t* next_mask,
+                           int32_t* pairs, mava_stream_t s);
+/* Double-Q TD loss (:368-410) on three T32 (L*Rp x n_actions) Q arrays, rows t * Rp + m, real where m < n_real:
+ * a* = first argmax of where(next_mask, q_next_online, finfo.min), target = reward + (1 - terminal_next) * gamma *
+ * q_next_target[a*], dq (T32, same shape) = 2 (q[a] - target) / N * grad_scale at the taken action a and 0 elsewhere
+ * (N = L * n_real; padding rows get 0).  partials (nblk, 3): per-block sums of (q_loss, mean_q, mean_target), each
+ * already divided by N (their column sums are the metrics).  action / reward / terminal_next (L, Rp), next_mask
+ * (L, Rp, n_actions). */
+int mava_q_td_loss_f32(int L, int Rp, int n_actions, int n_real, const float* q, const float* q_next_online,
+                       const float* q_next_target, const int32_t* action, const float* reward, const uint8_t* terminal_next,
+                       const uint8_t* next_mask, float gamma, float grad_scale, float* dq, float* partials, int nblk,
+                       mava_stream_t s);
+/* Target network update (:411-418): hard = 0: target = tau * online + (1 - tau) * target (optax.incremental_update);
+ * hard = 1: target = online (optax.periodic_update on a step where it fires; the caller decides when). */
+int mava_target_update_f32(long n, const float* online, float* target, float tau, int hard, mava_stream_t s);
 
 /* T32 <-> row-major conversion of a (rows x N) matrix. */
 int mava_t32_convert_f32(const float* src, int N, int rows, int to_t32, float* dst, mava_stream_t s);

@@ -62,6 +62,12 @@ _SIGNATURES = {
     "mava_ppo_critic_grad_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp],
     "mava_synth_rware_step": [i32, i32, i32, i32, i32, i32, i32, u64, u32, vp, u32, i32] + [vp] * 14 + [vp, i32, vp],
     "mava_lbf_step": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
+    "mava_lbf_step_real_next": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 24 + [vp],
+    "mava_rec_q_step_f32": [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, u64, u32, u32, vp, vp, vp],
+    "mava_replay_add_f32": [i32] * 6 + [vp] * 16 + [vp],
+    "mava_replay_sample_f32": [i32] * 5 + [u32, i32, i32, i32, u64, u32] + [vp] * 17 + [vp],
+    "mava_q_td_loss_f32": [i32, i32, i32, i32] + [vp] * 7 + [f32, f32, vp, vp, i32, vp],
+    "mava_target_update_f32": [lng, vp, vp, f32, i32, vp],
     "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18 + [vp, vp, f32, f32, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],

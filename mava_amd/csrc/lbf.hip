@@ -16,6 +16,12 @@
 //                   instruction covers consecutive addresses instead of lanes a whole observation apart.
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
 // graph.
+//
+// mava_lbf_step_real_next (the REAL instantiation) also writes what AutoResetWrapper keeps in
+// extras["real_next_obs"] (mava/wrappers/auto_reset_wrapper.py:52-101): the agents_view / action_mask of the state the
+// rules produced, BEFORE the auto-reset, and a per-env `terminated` flag (every food eaten).  The reset of ending envs
+// then moves behind one more output pass over the same LDS tile; the plain kernel is the same code with those parts
+// compiled out.
 #include "common.h"
 
 namespace {
@@ -55,6 +61,13 @@ struct LbfArgs {
   int32_t* info_length;
   uint8_t* info_terminal;
   const int32_t* action;     // (E, A) or null (reset)
+};
+
+// extra outputs of the REAL instantiation (not written on a reset call)
+struct LbfReal {
+  float* view;               // (E, A, A + 3 (F + A)) pre-reset agents_view
+  uint8_t* mask;             // (E, A, 6) pre-reset action_mask
+  uint8_t* terminated;       // (E) 1 when every food was eaten (a time-limit end is a truncation: 0)
 };
 
 struct Tile {
@@ -181,7 +194,44 @@ __device__ __forceinline__ float view_value(const Tile& s, int le, int j, int q,
   return vis ? (float)v : (comp < 2 ? -1.0f : 0.0f);
 }
 
-__global__ __launch_bounds__(THREADS) void lbf_step_kernel(LbfArgs a) {
+// agents_view / action_mask of the workgroup's rows [e0 * A, (e0 + ne) * A) from the LDS state (all threads, stores to
+// consecutive addresses); av / mk point at row e0 * A
+__device__ __forceinline__ void write_view(const LbfArgs& a, const Tile& s, float* av, int ne, int tid) {
+  const int A = a.A, F = a.F;
+  const int W = A + 3 * (F + A);
+  const int n = ne * A * W;
+  for (int i = tid; i < n; i += THREADS) {
+    const int row = (unsigned)i / (unsigned)W, f = i - row * W;
+    const int le = (unsigned)row / (unsigned)A, j = row - le * A;
+    av[i] = f < A ? (f == j ? 1.0f : 0.0f) : view_value(s, le, j, f - A, F, a.fov);
+  }
+}
+
+__device__ __forceinline__ void write_mask(const LbfArgs& a, const Tile& s, uint8_t* mk, int ne, int tid) {
+  const int A = a.A, F = a.F, G = a.G;
+  {
+    const int n = ne * A * N_ACT;
+    for (int i = tid; i < n; i += THREADS) {
+      const int row = (unsigned)i / (unsigned)N_ACT, act = i - row * N_ACT;
+      const int le = (unsigned)row / (unsigned)A, j = row - le * A;
+      const int r = s.ar[j][le], c = s.ac[j][le];
+      bool ok;
+      if (act == 0) {
+        ok = true;
+      } else if (act == LOAD) {
+        ok = false;
+        for (int f = 0; f < F; ++f) ok |= (s.fa[f][le] != 0) & (abs(s.fr[f][le] - r) + abs(s.fc[f][le] - c) == 1);
+      } else {
+        const int tr = r + (act == 2) - (act == 1), tc = c + (act == 4) - (act == 3);
+        ok = tr >= 0 && tr < G && tc >= 0 && tc < G && !food_at(s, le, F, tr, tc) && !agent_at(s, le, A, tr, tc);
+      }
+      mk[i] = ok ? 1 : 0;
+    }
+  }
+}
+
+template <bool REAL>
+__device__ __forceinline__ void lbf_step_body(const LbfArgs& a, const LbfReal& rn) {
   __shared__ Tile s;
   const int tid = threadIdx.x;
   const int A = a.A, F = a.F, G = a.G;
@@ -277,6 +327,7 @@ __global__ __launch_bounds__(THREADS) void lbf_step_kernel(LbfArgs a) {
       // 6. terminal, RecordEpisodeMetrics (mava/wrappers/episode_metrics.py:88-111)
       const int sc_new = sc_old + 1;
       const bool term = left == 0 || sc_new >= a.time_limit;
+      if constexpr (REAL) rn.terminated[e] = left == 0 ? 1 : 0;  // Jumanji: termination vs truncation
       const float new_ret = run_ret + mean_rew;
       const int new_len = run_len + 1;
       const float ret_info = term ? new_ret : ep_ret;
@@ -299,8 +350,23 @@ __global__ __launch_bounds__(THREADS) void lbf_step_kernel(LbfArgs a) {
       s.term[le] = 0;
     }
     // 7. (auto-)reset at this step's counter
-    if (reset) total = (float)generate(a, s, le, g, t);
-    a.total_food_level[e] = total;
+    if constexpr (!REAL) {  // (REAL: after the pre-reset output pass below)
+      if (reset) total = (float)generate(a, s, le, g, t);
+      a.total_food_level[e] = total;
+    }
+  }
+  if constexpr (REAL) {
+    // the pre-reset observation of every env (equal to the returned one where the step did not end), then the reset
+    __syncthreads();
+    if (!a.is_reset && ne > 0) {
+      write_view(a, s, rn.view + (long)e0 * A * (A + 3 * (F + A)), ne, tid);
+      write_mask(a, s, rn.mask + (long)e0 * A * N_ACT, ne, tid);
+    }
+    __syncthreads();
+    if (tid < ne && (a.is_reset || s.term[tid])) {  // (a continuing env keeps its total food level)
+      const uint32_t t = a.t + (a.t_base ? *a.t_base : 0u);
+      a.total_food_level[e0 + tid] = (float)generate(a, s, tid, a.env_offset + (uint32_t)(e0 + tid), t);
+    }
   }
   __syncthreads();
 
@@ -373,9 +439,13 @@ __global__ __launch_bounds__(THREADS) void lbf_step_kernel(LbfArgs a) {
   }
 }
 
+__global__ __launch_bounds__(THREADS) void lbf_step_kernel(LbfArgs a) { lbf_step_body<false>(a, LbfReal{}); }
+
+__global__ __launch_bounds__(THREADS) void lbf_step_real_kernel(LbfArgs a, LbfReal rn) { lbf_step_body<true>(a, rn); }
+
 }  // namespace
 
-extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
+static int lbf_step_impl(const char* fn, const LbfReal* rn, int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
                              int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
                              uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
                              int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
@@ -384,23 +454,23 @@ extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_
                              int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
                              int32_t* info_length, uint8_t* info_terminal, const int32_t* action, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXA && F >= 1 && F <= MAXF && G >= 3 && G <= MAXG, 0,
-                 "mava_lbf_step: bad shape E=%d A=%d F=%d G=%d (1 <= A <= %d, 1 <= F <= %d, 3 <= G <= %d)", E, A, F, G,
+                 "%s: bad shape E=%d A=%d F=%d G=%d (1 <= A <= %d, 1 <= F <= %d, 3 <= G <= %d)", fn, E, A, F, G,
                  MAXA, MAXF, MAXG);
   MAVA_ARG_CHECK(fov >= 0 && max_agent_level >= 1 && max_agent_level <= 1000 && time_limit >= 1 &&
                      (force_coop == 0 || force_coop == 1) && (individual_rewards == 0 || individual_rewards == 1),
-                 1, "mava_lbf_step: bad scenario fov=%d max_agent_level=%d time_limit=%d force_coop=%d individual=%d",
-                 fov, max_agent_level, time_limit, force_coop, individual_rewards);
+                 1, "%s: bad scenario fov=%d max_agent_level=%d time_limit=%d force_coop=%d individual=%d",
+                 fn, fov, max_agent_level, time_limit, force_coop, individual_rewards);
   MAVA_ARG_CHECK((G - 2) * (G - 2) >= 9 * (F - 1) + 1 && G * G >= F + A, 2,
-                 "mava_lbf_step: a %dx%d grid cannot place %d foods and %d agents", G, G, F, A);
-  MAVA_ARG_CHECK((long)E * A * (A + 3 * (F + A)) < (1L << 31), 3, "mava_lbf_step: E=%d exceeds 32-bit indexing", E);
+                 "%s: a %dx%d grid cannot place %d foods and %d agents", fn, G, G, F, A);
+  MAVA_ARG_CHECK((long)E * A * (A + 3 * (F + A)) < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(agent_pos && agent_level && food_pos && food_level && food_alive && total_food_level && step_count &&
                      run_return && run_length && ep_return && ep_length && agents_view && global_state && action_mask &&
                      obs_step_count,
-                 4, "mava_lbf_step: null state/observation pointer");
+                 4, "%s: null state/observation pointer", fn);
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "mava_lbf_step: null transition pointer");
-  MAVA_ARG_CHECK(is_reset || action, 6, "mava_lbf_step: a step needs the (E, A) action array");
+                 "%s: null transition pointer", fn);
+  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
   LbfArgs a;
   a.E = E; a.A = A; a.F = F; a.G = G; a.fov = fov; a.max_level = max_agent_level; a.force_coop = force_coop;
   a.individual = individual_rewards; a.time_limit = time_limit;
@@ -412,7 +482,45 @@ extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_
   a.ep_length = ep_length; a.agents_view = agents_view; a.global_state = global_state; a.action_mask = action_mask;
   a.obs_step_count = obs_step_count; a.reward = reward; a.done = done; a.info_return = info_return;
   a.info_length = info_length; a.info_terminal = info_terminal; a.action = action;
-  hipLaunchKernelGGL(lbf_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
+  if (rn == nullptr) {
+    hipLaunchKernelGGL(lbf_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
+  } else {
+    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
+    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
+                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
+    hipLaunchKernelGGL(lbf_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, *rn);
+  }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
+}
+
+extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
+                             int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
+                             int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
+                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, hipStream_t s) {
+  return lbf_step_impl("mava_lbf_step", nullptr, E, A, F, G, fov, max_agent_level, force_coop, individual_rewards, time_limit, seed, t, t_base, env_offset, is_reset,
+                       agent_pos, agent_level, food_pos, food_level, food_alive, total_food_level, step_count, run_return,
+                       run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done,
+                       info_return, info_length, info_terminal, action, s);
+}
+
+// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
+extern "C" int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
+                             int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
+                             int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
+                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, float* real_view, uint8_t* real_mask,
+                                       uint8_t* terminated, hipStream_t s) {
+  const LbfReal rn = {real_view, real_mask, terminated};
+  return lbf_step_impl("mava_lbf_step_real_next", &rn, E, A, F, G, fov, max_agent_level, force_coop, individual_rewards, time_limit, seed, t, t_base, env_offset, is_reset,
+                       agent_pos, agent_level, food_pos, food_level, food_alive, total_food_level, step_count, run_return,
+                       run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done,
+                       info_return, info_length, info_terminal, action, s);
 }

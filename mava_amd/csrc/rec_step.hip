@@ -13,11 +13,24 @@
 // from L2 one 8-k-step batch ahead of the MFMAs that use them (no launch-long preload), activations cross waves
 // through [feature][row] LDS tiles (stride 33).  Blocks [0, nblk_actor) serve the actor, the rest the critic - e.g.
 // one critic sequence per ENV when the agents share the critic input - so both networks share one launch.
+#include <type_traits>
+
 #include "mlp_core.h"
 #include "rec_step_task.h"
 #include "tanh_normal.h"
 
 namespace {
+
+// Epilogue arguments of the rec_iql acting step (mava_rec_q_step_f32): the same network, the head's outputs are Q-values
+// and the action is epsilon-greedy (mava/systems/q_learning/rec_iql.py:241-276, mava/distributions.py:94-138).
+struct RecQOut {
+  const uint8_t* mask;   // (rows, no)
+  uint32_t seed_lo, seed_hi, step, row_offset;
+  float eps;
+  int32_t* action;       // (rows)
+  float* q;              // (rows, no) row-major, or null
+};
+constexpr uint32_t QEPS_STREAM = 0x51455053u;  // "QEPS"
 
 constexpr int LDT = 33;
 constexpr int G3 = 3 * MLP_H;
@@ -69,8 +82,8 @@ __device__ __forceinline__ void stream_mm(f32x16 (&acc)[NG], const float* __rest
   }
 }
 
-template <int NO, bool ACTOR>
-__device__ __forceinline__ void rec_step_body(const RecNet& nt, const RecStepOut& out, float* lds, int bid, int nblk) {
+template <int NO, bool ACTOR, class Out = RecStepOut>
+__device__ __forceinline__ void rec_step_body(const RecNet& nt, const Out& out, float* lds, int bid, int nblk) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6, h = lane >> 5, j = lane & 31;
   const int srow = tid >> 3, l8 = tid & 7;
@@ -199,7 +212,37 @@ __device__ __forceinline__ void rec_step_body(const RecNet& nt, const RecStepOut
       for (int o = 0; o < NO; ++o)
         y[o] = (((YP[(0 * NO + o) * 32 + j] + YP[(1 * NO + o) * 32 + j]) + YP[(2 * NO + o) * 32 + j]) +
                 YP[(3 * NO + o) * 32 + j]) + ((o < no) ? bhead[o] : 0.0f);
-      if (!ACTOR) {
+      if constexpr (std::is_same<Out, RecQOut>::value) {
+        // MaskedEpsGreedyDistribution: greedy = argmax of where(mask, q, finfo.min), first index on ties; with
+        // probability eps the action is drawn uniformly from the valid ones instead.  Word x of one Philox block decides
+        // exploration, word y picks the valid action (floor(y * n_valid / 2^32)).
+        const uint8_t* mk = out.mask + (long)row * no;
+        float best = -FLT_MAX;
+        int a = 0, nvalid = 0;
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+          if (o < no) {
+            const bool ok = mk[o] != 0;
+            const float z = ok ? y[o] : -FLT_MAX;
+            if (o == 0 || z > best) { best = z; a = o; }
+            nvalid += ok ? 1 : 0;
+            if (out.q != nullptr) out.q[(long)row * no + o] = y[o];
+          }
+        }
+        const Philox4 rnd = philox4x32_10(out.row_offset + (uint32_t)row, out.step, 0u, QEPS_STREAM, out.seed_lo, out.seed_hi);
+        if (nvalid > 0 && u01_open(rnd.x) < out.eps) {
+          const int k = (int)__umulhi(rnd.y, (uint32_t)nvalid);
+          int c = 0;
+#pragma unroll
+          for (int o = 0; o < NO; ++o) {
+            if (o < no && mk[o] != 0) {
+              if (c == k) a = o;
+              ++c;
+            }
+          }
+        }
+        out.action[row] = a;
+      } else if (!ACTOR) {
         for (int b = 0; b < out.vbroadcast; ++b) out.value[(long)row * out.vbroadcast + b] = y[0];
       } else if (out.action_f != nullptr) {
         // ContinuousActionHead (networks.py:127-169): same noise stream as mava_seq_sample_continuous_f32
@@ -263,6 +306,12 @@ __global__ __launch_bounds__(256, 1) void rec_step_kernel(RecNet actor, RecNet c
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if ((int)blockIdx.x < nblk_actor) rec_step_body<NOA, true>(actor, out, lds, (int)blockIdx.x, nblk_actor);
   else rec_step_body<1, false>(critic, out, lds, (int)blockIdx.x - nblk_actor, (int)gridDim.x - nblk_actor);
+}
+
+template <int NOA>
+__global__ __launch_bounds__(256, 1) void rec_q_step_kernel(RecNet net, RecQOut out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  rec_step_body<NOA, true, RecQOut>(net, out, lds, (int)blockIdx.x, (int)gridDim.x);
 }
 
 void carve(RecNet& n, int no_pad) {
@@ -393,4 +442,47 @@ extern "C" int mava_rec_step_packed_f32(const void* pack_a, const void* pack_c, 
                        h_actor_out, rows_a, seed, step, row_offset, greedy, action_f ? nullptr : action, action_f, log_prob,
                        critic_params, critic_din, critic_input, critic_share, done_c, done_c_stride, h_critic_in, h_critic_out,
                        rows_c, value_broadcast, value, s, min_scale, pack_a, pack_c);
+}
+
+// rec_iql acting step: the recurrent Q network of one step (the actor half of rec_step_kernel) with the epsilon-greedy
+// epilogue.  Rows multiples of 32; the padding rows' all-zero masks give action 0.
+extern "C" int mava_rec_q_step_f32(const float* params, int din, int n_actions, const float* agents_view,
+                                   const uint8_t* action_mask, const uint8_t* done, const float* h_in, float* h_out, int rows,
+                                   float eps, uint64_t seed, uint32_t step, uint32_t row_offset, int32_t* action, float* q_out,
+                                   hipStream_t s) {
+  MAVA_ARG_CHECK(rows >= 0 && rows % 32 == 0, 0, "mava_rec_q_step_f32: rows must be a multiple of 32 (rows=%d)", rows);
+  if (rows == 0) return MAVA_OK;
+  // (a 32-wide head spills in this epilogue: 1..16 actions are instantiated)
+  MAVA_ARG_CHECK(din >= 1 && n_actions >= 1 && n_actions <= 16, 1, "mava_rec_q_step_f32: bad shape din=%d n_actions=%d (1..16)",
+                 din, n_actions);
+  MAVA_ARG_CHECK(params && agents_view && action_mask && done && h_in && h_out && action, 2,
+                 "mava_rec_q_step_f32: null pointer");
+  MAVA_ARG_CHECK(h_in != h_out, 3, "mava_rec_q_step_f32: the hidden state cannot be updated in place");
+  MAVA_ARG_CHECK(eps >= 0.0f && eps <= 1.0f, 4, "mava_rec_q_step_f32: eps=%g outside [0, 1]", (double)eps);
+  const int noa = n_actions <= 8 ? 8 : 16;
+  RecNet n = {};
+  n.params = params; n.x = agents_view; n.done = done; n.h_in = h_in; n.h_out = h_out;
+  n.din = din; n.no = n_actions; n.xshare = 1; n.rows = rows; n.done_stride = 1;
+  carve(n, noa);
+  const size_t lb = (size_t)n.end * sizeof(float);
+  MAVA_ARG_CHECK(lb <= 163840, 5, "mava_rec_q_step_f32: %zu bytes of LDS needed (din %d) exceed 160 KiB", lb, din);
+  RecQOut o = {};
+  o.mask = action_mask; o.seed_lo = (uint32_t)seed; o.seed_hi = (uint32_t)(seed >> 32); o.step = step;
+  o.row_offset = row_offset; o.eps = eps; o.action = action; o.q = q_out;
+  const int nblk = rows / 32 < 256 ? rows / 32 : 256;
+#define LAUNCH(NOA)                                                                                              \
+  do {                                                                                                           \
+    static bool attr_set = false;                                                                                \
+    if (!attr_set) {                                                                                             \
+      MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)rec_q_step_kernel<NOA>,                                    \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 163840));                   \
+      attr_set = true;                                                                                           \
+    }                                                                                                            \
+    hipLaunchKernelGGL(rec_q_step_kernel<NOA>, dim3(nblk), dim3(256), lb, s, n, o);                             \
+  } while (0)
+  if (noa == 8) LAUNCH(8);
+  else LAUNCH(16);
+#undef LAUNCH
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
 }

@@ -40,6 +40,33 @@ class Categorical:
         return -(torch.where(p > 0, p * lsm, torch.zeros_like(p))).sum(-1)
 
 
+class MaskedEpsGreedyDistribution:
+    """mava/distributions.py:94-138: probability eps spread evenly over the valid actions plus 1 - eps on the greedy
+    action, the first argmax of where(mask, q, finfo(f32).min).  Host view for the evaluator seam and tests; the rec_iql
+    rollout samples inside mava_rec_q_step_f32."""
+
+    def __init__(self, q_values: torch.Tensor, epsilon: float, mask: torch.Tensor):
+        self.q_values = q_values
+        self.epsilon = float(epsilon)
+        m = mask.bool()
+        uniform = m.float() / m.float().sum(-1, keepdim=True)
+        greedy = torch.where(m, q_values, torch.full_like(q_values, F32_MIN)).argmax(-1)
+        self.greedy = greedy.to(torch.int32)
+        self.probs = self.epsilon * uniform + (1.0 - self.epsilon) * torch.nn.functional.one_hot(greedy, q_values.shape[-1]).float()
+
+    def mode(self) -> torch.Tensor:
+        return self.greedy
+
+    def sample(self, seed: Optional[torch.Generator] = None) -> torch.Tensor:
+        if self.epsilon == 0.0:
+            return self.greedy
+        p = self.probs.reshape(-1, self.probs.shape[-1])
+        return torch.multinomial(p, 1, generator=seed).view(self.probs.shape[:-1]).to(torch.int32)
+
+    def log_prob(self, action: torch.Tensor) -> torch.Tensor:
+        return torch.log(self.probs.gather(-1, action.long().unsqueeze(-1)).squeeze(-1))
+
+
 class TanhNormal:
     """Independent(TanhTransformedDistribution(Normal(loc, softplus(log_std) + 1e-3)), 1): mava/networks.py:127-169,
     mava/distributions.py:24-91.  Host view for the evaluator seam like Categorical above; the rollout and the loss use

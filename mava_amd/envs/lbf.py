@@ -45,6 +45,7 @@ class LevelBasedForaging:
     gs_tiles = 1
     global_state_shared = True
     supports_fused_rollout = False
+    emits_real_next_obs = True  # step_into(real_obs=, terminated=): what rec_iql stores as next_obs / terminal
 
     def __init__(self, num_envs: int, grid_size: int, fov: int, num_agents: int, num_food: int, max_agent_level: int,
                  force_coop: bool, time_limit: int = 100, use_individual_rewards: bool = False,
@@ -112,21 +113,28 @@ class LevelBasedForaging:
     # ---- kernel call ----------------------------------------------------------------------
     def step_into(self, state: LBFState, t: int, obs: Dict[str, torch.Tensor], reward=None, done=None, info_return=None,
                   info_length=None, info_terminal=None, is_reset: bool = False, env_offset: Optional[int] = None,
-                  t_base: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None) -> None:
+                  t_base: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None,
+                  real_obs: Optional[Dict[str, torch.Tensor]] = None, terminated: Optional[torch.Tensor] = None) -> None:
         """One vectorised step (or reset) with the (E, A) int32 `action`, writing the next observation into `obs` and the
         transition into the given (E, A) / (E,) slots.  `t` is the replica's global step index (Philox counter of the
-        resets); `t_base` (a device int32 word) is added to it on the device, for rollouts replayed from a captured graph."""
+        resets); `t_base` (a device int32 word) is added to it on the device, for rollouts replayed from a captured graph.
+        `real_obs` ({"agents_view", "action_mask"}) and `terminated` (E,) u8, given together, receive the pre-reset
+        observation (AutoResetWrapper's extras["real_next_obs"]) and the termination flag (every food eaten; a time-limit
+        end is a truncation) - mava_lbf_step_real_next; they are not written on a reset."""
         off = self.env_offset if env_offset is None else env_offset
         if not is_reset and (action is None or action.dtype != torch.int32 or action.numel() != self.num_envs * self.num_agents):
             raise ValueError("LevelBasedForaging.step_into needs the (E, A) int32 discrete actions of the step")
-        launch("env_step", lib().mava_lbf_step, self.num_envs, self.num_agents, self.num_food, self.grid_size, self.fov,
+        if (real_obs is None) != (terminated is None):
+            raise ValueError("LevelBasedForaging.step_into: real_obs and terminated go together")
+        real = () if real_obs is None else (ptr(real_obs["agents_view"]), ptr(real_obs["action_mask"]), ptr(terminated))
+        launch("env_step", lib().mava_lbf_step_real_next if real else lib().mava_lbf_step, self.num_envs, self.num_agents, self.num_food, self.grid_size, self.fov,
                self.max_agent_level, int(self.force_coop), int(self.use_individual_rewards), self.time_limit,
                self.seed & 0xFFFFFFFFFFFFFFFF, t & 0xFFFFFFFF, ptr(t_base), off & 0xFFFFFFFF, int(is_reset),
                ptr(state.agent_pos), ptr(state.agent_level), ptr(state.food_pos), ptr(state.food_level),
                ptr(state.food_alive), ptr(state.total_food_level), ptr(state.step_count), ptr(state.run_return),
                ptr(state.run_length), ptr(state.ep_return), ptr(state.ep_length), ptr(obs["agents_view"]),
                ptr(obs["global_state"]), ptr(obs["action_mask"]), ptr(obs["step_count"]), ptr(reward), ptr(done),
-               ptr(info_return), ptr(info_length), ptr(info_terminal), None if is_reset else ptr(action), stream_ptr())
+               ptr(info_return), ptr(info_length), ptr(info_terminal), None if is_reset else ptr(action), *real, stream_ptr())
 
     # ---- MarlEnv-style batched API (allocating; the learner uses step_into) -----------------
     def _observation(self, obs: Dict[str, torch.Tensor]):

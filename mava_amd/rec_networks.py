@@ -590,6 +590,36 @@ class RecurrentValueNet(_RecurrentNet):
         return h, v.squeeze(-1)
 
 
+class RecQNetwork(_RecurrentNet):
+    """mava/networks.py:343-384: MLPTorso [128] relu -> ScannedRNN GRU(128) -> MLPTorso [128] relu -> Dense(n_actions,
+    orthogonal(0.01)), the head named params/Dense_0.  rec_iql acts on it with mava_rec_q_step_f32 and trains it with
+    forward_sequence / backward_sequence (mava_amd/iql_learner.py)."""
+
+    head_scale = 0.01
+
+    def __init__(self, pre_torso: MLPTorso, post_torso: MLPTorso, action_dim: int, obs_dim: int, hidden_state_dim: int = 128):
+        super().__init__(obs_dim, int(action_dim), hidden_state_dim, pre_torso, post_torso)
+        if self.generic:
+            raise NotImplementedError("RecQNetwork runs the default network/rnn.yaml torsos only ([128] relu)")
+        self.action_dim = int(action_dim)
+
+    def _head_tree(self, head):
+        return {"Dense_0": head}
+
+    def get_q_values(self, params: Any, hstate: torch.Tensor, observation_done) -> Tuple[torch.Tensor, torch.Tensor]:
+        """q_net.apply(..., method="get_q_values"): (hstate, Q (T, E, A, n_actions))."""
+        observation, done = observation_done
+        return self._apply_sequence(params, hstate, observation.agents_view, done)
+
+    def apply(self, params: Any, hstate: torch.Tensor, observation_done, eps: float = 0.0):
+        """q_net.apply(params, hstate, (observation, done), eps) -> (hstate, MaskedEpsGreedyDistribution), leading time
+        axis on observation and done (networks.py:366-384)."""
+        from .distributions import MaskedEpsGreedyDistribution
+
+        h, q = self.get_q_values(params, hstate, observation_done)
+        return h, MaskedEpsGreedyDistribution(q, eps, observation_done[0].action_mask)
+
+
 def t32_to_rows(src: torch.Tensor, N: int, rows: int) -> torch.Tensor:
     out = torch.empty((rows, N), device=src.device)
     check(lib().mava_t32_convert_f32(ptr(src), N, rows, 0, ptr(out), stream_ptr()), "t32_convert")
