@@ -268,6 +268,53 @@ int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_l
                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, float* real_view,
                             uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
+/* ---- Robot Warehouse environment step (mava_amd/csrc/rware.hip; rules in DESIGN.md "Robot Warehouse", restated in
+ *      tests/rware_model.py; parity with Jumanji's RobotWarehouse is unpinned).  E environments of an H x W grid
+ *      (H, W <= 32; coordinates (x = column, y = row), y grows downward) with A agents (<= 16), S shelves (<= 256) and
+ *      R requested shelves (1 <= R <= 16, R < S); sensor_range in {1, 2}.  The layout is the caller's (HOST arrays, copied
+ *      into the launch): highway_rows[H] - bit x of word y set when cell (x, y) is a highway - and shelf_home[S], the
+ *      increasing non-highway cells (y * W + x) of shelves 0 .. S-1; the goals are (W/2 - 1, H - 1) and (W/2, H - 1).
+ *      Actions (E, A) int32: 0 NOOP, 1 FORWARD, 2 LEFT, 3 RIGHT, 4 TOGGLE_LOAD; directions 0 UP, 1 RIGHT, 2 DOWN, 3 LEFT.
+ *      State (struct of arrays, advanced in place): agent_pos (E, A, 2) (x, y), agent_dir (E, A), agent_carry (E, A)
+ *      (shelf id or -1), shelf_pos (E, S) (cell; a carried shelf has its carrier's cell, a ground shelf stands on a
+ *      home cell), request_queue (E, R) (distinct shelf ids), step_count (E, A) and the RecordEpisodeMetrics words, as
+ *      mava_lbf_step.  One step: turns and FORWARD moves (refused off the grid, or when a carried shelf would meet a
+ *      ground shelf; agents do not block each other); a collision (two agents on one cell after the moves, or two that
+ *      exchanged cells) ends the episode when collision_terminates is 1 and is ignored when 0; carried shelves follow;
+ *      TOGGLE_LOAD in agent order (pick up the ground shelf of the cell / put down on a non-highway cell without one);
+ *      deliveries in agent order (a carried, requested shelf on a goal scores 1 and its queue slot is refilled with the
+ *      (draw mod (S - R))-th shelf outside the queue); reward = deliveries, the same for every agent; the episode also
+ *      ends (a truncation) at time_limit.  Outputs: agents_view (E, A, A + raw) = [one-hot id | raw view], raw =
+ *      8 + 7 (2 sensor_range + 1)^2: [x, y, carrying, direction one-hot (4), on_highway] then per view cell (rows outer)
+ *      [agent, its direction one-hot (4), shelf, shelf requested]; global_state (E, 1, A * raw); action_mask (E, A, 5)
+ *      u8 (FORWARD iff it would move); obs_step_count, reward, done (E, A); info_* (E).  is_reset 1 generates every env
+ *      (reward, done, info_* and action may then be NULL); a terminal step regenerates that env and returns the reset
+ *      observation.  Randomness: Philox4x32-10, key `seed`, counter (env_offset + e, t + *t_base, block, "RWRS") for a
+ *      reset and (.., agent / 4, "RWRQ") word agent % 4 for a refill; t_base (a device word, may be NULL) is added on the
+ *      device, so the step replays from a captured graph.  No host state, no synchronisation. */
+int mava_rware_step(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit, int collision_terminates,
+                    const uint32_t* highway_rows, const int32_t* shelf_home, uint64_t seed, uint32_t t,
+                    const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_dir,
+                    int32_t* agent_carry, int32_t* shelf_pos, int32_t* request_queue, int32_t* step_count,
+                    float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                    float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                    float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
+                    mava_stream_t s);
+
+/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
+ * (E, A, A + raw) / real_mask (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
+ * 1 only on a collision termination - a time-limit end is a truncation.  None of the three is written on a reset call
+ * (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
+int mava_rware_step_real_next(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit,
+                              int collision_terminates, const uint32_t* highway_rows, const int32_t* shelf_home,
+                              uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
+                              int32_t* agent_pos, int32_t* agent_dir, int32_t* agent_carry, int32_t* shelf_pos,
+                              int32_t* request_queue, int32_t* step_count, float* run_return, int32_t* run_length,
+                              float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                              uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                              float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
+                              float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments

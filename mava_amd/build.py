@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "rollout_h2.hip",
     "synth_rware.hip",
     "lbf.hip",
+    "rware.hip",
     "q_learning.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",
