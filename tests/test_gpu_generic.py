@@ -53,6 +53,10 @@ CASES = [
     dict(kind="mlp", sizes=[128], act="relu", ln=True, din=20),
     dict(kind="cnn", shape=(5, 5, 3), channels=[8, 16], kernels=[3, 3], strides=[1, 2], act="relu", ln=True, din=75),
     dict(kind="cnn", shape=(4, 6, 2), channels=[32, 32], kernels=[3, 3], strides=[1, 1], act="tanh", ln=False, din=48),
+    # geometries tests/test_gpu_generic_layers.py pins kernel by kernel: even kernels with asymmetric 'SAME' padding and
+    # H != W; stride = kernel (asymmetric, total 1) followed by a 1 x 1 convolution
+    dict(kind="cnn", shape=(4, 6, 2), channels=[8, 16], kernels=[2, 4], strides=[1, 2], act="tanh", ln=True, din=48),
+    dict(kind="cnn", shape=(5, 5, 3), channels=[8, 8], kernels=[3, 1], strides=[3, 1], act="relu", ln=False, din=75),
 ]
 
 

@@ -95,7 +95,7 @@ def test_lbf_real_next_matches_model(dev):
 
 
 # ---- 2. the acting step -----------------------------------------------------------------------------------------------
-def _q_step(dev, flat, x, mask, done, h, eps, seed=99, step=3, q_out=True):
+def _q_step(dev, flat, x, mask, done, h, eps, seed=99, step=3, q_out=True, row_offset=0):
     from mava_amd._lib import check, lib, ptr, stream_ptr
 
     R, O = x.shape
@@ -104,12 +104,13 @@ def _q_step(dev, flat, x, mask, done, h, eps, seed=99, step=3, q_out=True):
     hi, ho = _t(_to_t32(h.astype(np.float32)), dev), torch.empty(R * 128, device=dev)
     act, q = torch.empty(R, dtype=torch.int32, device=dev), torch.empty((R, nA), device=dev)
     fl = _t(flat, dev)
-    check(lib().mava_rec_q_step_f32(ptr(fl), O, nA, ptr(xs), ptr(ms), ptr(ds), ptr(hi), ptr(ho), R, eps, seed, step, 0,
+    check(lib().mava_rec_q_step_f32(ptr(fl), O, nA, ptr(xs), ptr(ms), ptr(ds), ptr(hi), ptr(ho), R, eps, seed, step, row_offset,
                                     ptr(act), ptr(q) if q_out else None, stream_ptr()), "mava_rec_q_step_f32")
     return _np(act), _np(q), _from_t32(_np(ho), R, 128)
 
 
-def _q_case(R=64, real=48, O=21, nA=6, seed=0):
+def _q_case(R=64, real=48, O=21, nA=6, seed=0, no_valid=()):
+    """no_valid: real rows whose mask is all zero (no valid action: the kernel answers action 0)."""
     rng = np.random.default_rng(seed)
     flat = ro.init_rec(rng, O, nA, 0.01).astype(np.float32)
     # a larger head so that the Q-values spread (the greedy choice is then not decided by rounding)
@@ -119,6 +120,7 @@ def _q_case(R=64, real=48, O=21, nA=6, seed=0):
     mask = np.zeros((R, nA), bool)
     mask[:real] = rng.random((real, nA)) < 0.6
     mask[:real, 0] = True
+    mask[list(no_valid)] = False
     done = np.zeros(R, bool)
     done[:real] = rng.random(real) < 0.3
     h = np.zeros((R, 128), np.float32)
@@ -126,20 +128,41 @@ def _q_case(R=64, real=48, O=21, nA=6, seed=0):
     return flat, x, mask, done, h
 
 
-def test_q_step_matches_oracle(dev):
-    flat, x, mask, done, h = _q_case()
+# (rows, real rows, din, actions, row_offset, q_out given)
+Q_STEP_CASES = [
+    (64, 48, 21, 6, 0, True),
+    (64, 48, 16, 11, 0, True),       # one 16-input batch; the 16-wide instantiation
+    (96, 96, 40, 16, 12345, True),   # an odd number of input batches, 16 actions, a row offset in the Philox counter
+    (64, 64, 155, 1, 0, True),       # a single action
+    (8288, 8288, 37, 6, 7, False),   # 259 tiles on 256 blocks: three blocks walk a second tile; q_out = None as the learner calls it
+]
+
+
+@pytest.mark.parametrize("R,real,O,nA,row_offset,q_out", Q_STEP_CASES)
+def test_q_step_matches_oracle(dev, R, real, O, nA, row_offset, q_out):
+    no_valid = (5, 17, real - 1)
+    flat, x, mask, done, h = _q_case(R, real, O, nA, no_valid=no_valid)
+    assert not mask[list(no_valid)].any() and mask[:real].any(-1).sum() == real - 3
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).double()
-    y, hn = ro.t_rec_forward(t(flat), x.shape[1], 6, t(x[None]), torch.from_numpy(done[None]), t(h))
+    y, hn = ro.t_rec_forward(t(flat), x.shape[1], nA, t(x[None]), torch.from_numpy(done[None]), t(h))
+    valid = mask.any(-1)
     for eps in (0.0, 0.3, 1.0):
-        act, q, h_out = _q_step(dev, flat, x, mask, done, h, eps)
-        assert_close(q[:48], y[0].numpy()[:48], 1e-5, "q_out")
-        assert_close(h_out[:48], hn.numpy()[:48], 1e-5, "hidden state")
-        want, greedy = qm.eps_greedy(q, mask, np.float32(eps), 99, 3)  # the greedy part from the kernel's own q
+        act, q, h_out = _q_step(dev, flat, x, mask, done, h, eps, row_offset=row_offset, q_out=q_out)
+        if not q_out:  # the Q-values of a second call that writes them; the two calls must agree bit for bit
+            act2, q, h2 = _q_step(dev, flat, x, mask, done, h, eps, row_offset=row_offset, q_out=True)
+            _eq(act, act2, f"actions with and without q_out at eps={eps}")
+            _eq(h_out, h2, f"hidden state with and without q_out at eps={eps}")
+        assert_close(q[:real], y[0].numpy()[:real], 1e-5, "q_out")
+        assert_close(h_out[:real], hn.numpy()[:real], 1e-5, "hidden state")
+        want, greedy = qm.eps_greedy(q, mask, np.float32(eps), 99, 3, row_offset)  # the greedy part from the kernel's own q
         _eq(act, want.astype(np.int32), f"actions at eps={eps}")
         if eps == 0.0:
             _eq(act, np.where(mask, q, qm.F32_MIN).argmax(-1).astype(np.int32), "greedy actions")
-        assert (act[48:] == 0).all()  # padding rows: all-zero masks
-        assert mask[np.arange(48), act[:48]].all()
+        assert (act[real:] == 0).all()  # padding rows: all-zero masks
+        assert (act[~valid] == 0).all()  # and real rows without a valid action
+        assert mask[valid, act[valid]].all()
+        if eps == 1.0 and nA > 1:
+            assert (act != greedy)[valid].any()  # exploration happened
 
 
 def test_q_step_frequencies(dev):
@@ -161,10 +184,12 @@ def test_q_step_frequencies(dev):
 
 
 # ---- 3. replay -------------------------------------------------------------------------------------------------------
-def test_replay_add_and_sample_match_model(dev):
+def _replay_run(dev, S):
+    """Adds 2 * cap + 2 steps and samples after each one that leaves a window; returns the (n_added, pairs) of every sample."""
     from mava_amd._lib import check, lib, ptr, stream_ptr
 
-    E, A, O, nA, cap, B, S = 7, 3, 5, 6, 9, 11, 4
+    E, A, O, nA, cap, B = 7, 3, 5, 6, 9, 11
+    drawn = []
     Rp = -(-(B * A) // 32) * 32
     rng = np.random.default_rng(2)
     rb = qm.Replay(E, A, O, nA, cap)
@@ -197,44 +222,115 @@ def test_replay_add_and_sample_match_model(dev):
         _eq(pairs, want_pairs, f"sample {n}: pairs")
         for k, o in zip(("obs", "mask", "action", "reward", "terminal", "tot", "next_obs", "next_mask"), out):
             _eq(o, smp[k], f"sample {n}: {k}")
+        drawn.append((rb.n_added, _np(pairs)))
+    return cap, drawn
+
+
+def test_replay_add_and_sample_match_model(dev):
+    cap, drawn = _replay_run(dev, 4)
+    assert len(drawn) == 2 * cap + 2 - 3
+    starts = np.concatenate([p[:, 1] for _, p in drawn])
+    assert len(set(starts.tolist())) > 1  # several windows to choose from
+
+
+def test_replay_sample_window_of_the_whole_buffer(dev):
+    """S == capacity: exactly one valid window, and it starts at the oldest slot (the write head)."""
+    cap, drawn = _replay_run(dev, 9)
+    assert [n for n, _ in drawn] == list(range(cap, 2 * cap + 3))
+    for n, pairs in drawn:
+        assert (pairs[:, 1] == n % cap).all(), (n, pairs[:, 1])
 
 
 # ---- 4. TD loss --------------------------------------------------------------------------------------------------------
-def test_td_loss_matches_f64(dev):
-    from mava_amd._lib import check, lib, ptr, stream_ptr
-
-    L, B, A, nA, gamma = 5, 9, 3, 6, 0.99
-    BA, Rp = B * A, 32
+def _td_case(L, Rp, n_real, nA):
+    """Inputs with the three fixtures every case must hold: exact ties of the masked maximum (the first index wins), a
+    masked maximum (never chosen), and terminal rows (no bootstrap).  A single action admits no tie between two entries
+    and its only entry is the maximum: there the masked-maximum rows have NO valid action (the argmax is still index 0)."""
     rows = L * Rp
     rng = np.random.default_rng(8)
     q, qn, qt = (rng.standard_normal((rows, nA)).astype(np.float32) for _ in range(3))
-    qn[:40, 2] = qn[:40, 4] = 5.0         # exact ties: the first index wins
+    t1, t2 = (2, 4) if nA >= 5 else (max(nA - 2, 0), nA - 1)
+    qn[: rows // 4, t1] = qn[: rows // 4, t2] = 5.0    # exact ties: the first index wins
     mask = rng.random((L, Rp, nA)) < 0.5
     mask[:, :, 0] = True
-    qn[40:80, 1] = 50.0                    # a masked maximum: never chosen where action 1 is invalid
+    big = 1 if nA > 1 else 0
+    qn[rows // 4 : rows // 2, big] = 50.0              # a masked maximum: never chosen where that action is invalid
+    if nA == 1:
+        mask.reshape(rows, nA)[rows // 4 : rows // 2 : 2] = False
     act = rng.integers(0, nA, (L, Rp)).astype(np.int32)
     rew = rng.standard_normal((L, Rp)).astype(np.float32)
     term = (rng.random((L, Rp)) < 0.3).astype(np.uint8)  # terminal rows do not bootstrap, truncated ones (0) do
-    gs = 256.0
-    nblk = 3
-    dq, part = torch.full((rows * nA,), 9.0, device=dev), torch.zeros((nblk, 3), device=dev)
+    # the fixtures are there, among the real rows
+    real = np.arange(Rp) < n_real
+    z = np.where(mask, qn.reshape(L, Rp, nA), qm.F32_MIN)
+    if nA > 1:
+        tied = (z == z.max(-1, keepdims=True)).sum(-1) >= 2
+        assert tied[:, real].any() and (z.argmax(-1) == t1)[tied & real].any()
+    hidden = qn.reshape(L, Rp, nA).argmax(-1) != z.argmax(-1) if nA > 1 else ~mask[..., 0]
+    assert hidden[:, real].any()
+    assert term[:, real].any() and not term[:, real].all()
+    return q, qn, qt, mask, act, rew, term
+
+
+def _td_run(dev, case, L, Rp, n_real, nA, nblk, gamma=0.99, gs=256.0):
+    from mava_amd._lib import check, lib, ptr, stream_ptr
+
+    q, qn, qt, mask, act, rew, term = case
+    rows = L * Rp
+    dq, part = torch.full((rows * nA,), 9.0, device=dev), torch.full((nblk, 3), 9.0, device=dev)
     ins = [_t(_to_t32(a), dev) for a in (q, qn, qt)] + [_t(a, dev) for a in (act, rew, term, mask.astype(np.uint8))]  # kept alive
-    check(lib().mava_q_td_loss_f32(L, Rp, nA, BA, *[ptr(a) for a in ins], gamma, gs, ptr(dq), ptr(part), nblk, stream_ptr()),
+    check(lib().mava_q_td_loss_f32(L, Rp, nA, n_real, *[ptr(a) for a in ins], gamma, gs, ptr(dq), ptr(part), nblk, stream_ptr()),
           "mava_q_td_loss_f32")
+    return _np(dq), _np(part)
+
+
+def _td_check(case, L, Rp, n_real, nA, dq, part, gamma=0.99, gs=256.0):
+    q, qn, qt, mask, act, rew, term = case
+    rows = L * Rp
     q3, qn3, qt3 = (a.reshape(L, Rp, nA).astype(np.float64) for a in (q, qn, qt))
     a_star = np.where(mask, qn3, qm.F32_MIN).argmax(-1)
     target = rew + (1.0 - term) * gamma * np.take_along_axis(qt3, a_star[..., None], -1)[..., 0]
     qa = np.take_along_axis(q3, act[..., None].astype(np.int64), -1)[..., 0]
-    real = np.arange(Rp) < BA
-    N = L * BA
+    real = np.arange(Rp) < n_real
+    N = L * n_real
     want_dq = np.zeros((L, Rp, nA))
     np.put_along_axis(want_dq, act[..., None].astype(np.int64), (2.0 * (qa - target) / N * gs)[..., None], -1)
     want_dq[:, ~real] = 0.0
-    got = _from_t32(_np(dq), rows, nA).reshape(L, Rp, nA)
+    got = _from_t32(dq, rows, nA).reshape(L, Rp, nA)
     assert_close(got, want_dq, 1e-6, "dQ")
-    metrics = _np(part).sum(0)
+    metrics = part.sum(0)
     d = (qa - target)[:, real]
     assert_close(metrics, np.array([(d ** 2).mean(), qa[:, real].mean(), target[:, real].mean()]), 1e-5, "metrics")
+
+
+# (L, Rp, real rows, actions, blocks)
+TD_CASES = [
+    (5, 32, 27, 6, 3),
+    (20, 96, 96, 6, 8),    # the learner's launch at the reference defaults: 1920 rows, no padding rows
+    (20, 96, 96, 6, 1),    # one block strides eight times
+    (20, 96, 96, 6, 16),   # idle blocks
+    (3, 64, 33, 32, 2),    # padding rows that start inside the second tile; the widest head
+    (2, 32, 32, 1, 1),     # a single action
+]
+
+
+@pytest.mark.parametrize("L,Rp,n_real,nA,nblk", TD_CASES)
+def test_td_loss_matches_f64(dev, L, Rp, n_real, nA, nblk):
+    case = _td_case(L, Rp, n_real, nA)
+    dq, part = _td_run(dev, case, L, Rp, n_real, nA, nblk)
+    _td_check(case, L, Rp, n_real, nA, dq, part)
+    idle = np.arange(nblk) * 256 >= L * Rp
+    assert (part[idle] == 0.0).all()  # a block without rows contributes exact zeros
+
+
+def test_td_loss_gradient_is_independent_of_the_block_count(dev):
+    """The three launches of the learner's shape: dQ bit-identical whatever the grid, the metrics at 1e-5 each."""
+    L, Rp, n_real, nA = 20, 96, 96, 6
+    case = _td_case(L, Rp, n_real, nA)
+    runs = {nblk: _td_run(dev, case, L, Rp, n_real, nA, nblk) for nblk in (8, 1, 16)}
+    for nblk, (dq, part) in runs.items():
+        _td_check(case, L, Rp, n_real, nA, dq, part)
+        _eq(dq, runs[8][0], f"dQ with {nblk} blocks against 8")
 
 
 # ---- 5. target update --------------------------------------------------------------------------------------------------
