@@ -25,6 +25,7 @@ int launch_coop(const CoopTask& tk, hipStream_t s) {
   MAVA_ARG_CHECK(lb <= 163840, 8, "mlp_coop: %zu bytes of LDS needed exceed the 160 KiB of a CU", lb);
   MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)mlp_coop_kernel<NO, KT1, MODE>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+  g_policy_last_instance = policy_instance_id(3, MODE, NO, KT1);
   int blocks = mava_cdiv(tk.R, 32);
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL((mlp_coop_kernel<NO, KT1, MODE>), dim3(blocks), dim3(256), lb, s, tk, L);

@@ -45,6 +45,13 @@ CoopLds make_coop_layout(int kt1) {
 
 enum { MODE_RAW = 0, MODE_SAMPLE = 1, MODE_VALUE = 2 };
 
+// Diagnostic (mlp_policy.hip: mava_debug_policy_last_instance): the template instance the last acting-side launch of this
+// process used, as KERNEL * 100000 + MODE * 10000 + NO * 100 + KT1 - KERNEL 1: policy_hybrid_kernel<NOA, KT1C> (NO = NOA,
+// KT1 = KT1C), 2: policy_step_kernel<NOA>, 3: mlp_coop_kernel<NO, KT1, MODE>, 4: mlp_forward_kernel<NO>; MODE and KT1
+// are 0 where the kernel has no such parameter.
+extern int g_policy_last_instance;
+constexpr int policy_instance_id(int kernel, int mode, int no, int kt1) { return kernel * 100000 + mode * 10000 + no * 100 + kt1; }
+
 // Body of the block-cooperative forward: block `bid` of `nblk` walks the 32-row tiles bid, bid + nblk, ...
 // (called by mlp_coop_kernel with the whole grid, and by policy_hybrid_kernel with the critic's share of a grid
 // whose other blocks run the per-wave actor)

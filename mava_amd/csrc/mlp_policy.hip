@@ -238,6 +238,7 @@ int launch_hybrid_t(const FwdTask& ta, const coop::CoopTask& ck, int nba, int nb
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     attr_set = true;
   }
+  coop::g_policy_last_instance = coop::policy_instance_id(1, 0, NOA, KT1C);
   hipLaunchKernelGGL((policy_hybrid_kernel<NOA, KT1C>), dim3(nba + nbc), dim3(256), lb, s, ta, ck, Lc, nba, mask, slo,
                      shi, step, row_offset, greedy, so);
   MAVA_LAUNCH_CHECK();
@@ -286,6 +287,14 @@ int mava_coop_raw(const float* params, int din, int n_out, const float* x, int x
 
 extern "C" int mava_mlp_param_count(int din, int n_out) { return mlp_param_count(din, n_out); }
 
+// Diagnostic (not part of include/mava_hip.h, like mava_debug_rollout_last_instance): which acting-side kernel instance the
+// last launch of this process used (encoding: mlp_coop_body.h), so that a parity test can assert WHICH instantiation it
+// checked (tests/test_gpu_instances.py).  Read-only; a refused launch leaves it unchanged.
+namespace coop {
+int g_policy_last_instance = 0;
+}
+extern "C" int mava_debug_policy_last_instance(void) { return coop::g_policy_last_instance; }
+
 extern "C" int mava_mlp_forward_f32(const mava_ctx* ctx, const float* params, int din, int n_out, const float* x,
                                     int x_share, int rows, float* out, hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && n_out >= 1 && n_out <= 32, 0,
@@ -307,6 +316,7 @@ extern "C" int mava_mlp_forward_f32(const mava_ctx* ctx, const float* params, in
                                          (int)lds_bytes<NO>()));                              \
       attr_set = true;                                                                        \
     }                                                                                         \
+    coop::g_policy_last_instance = coop::policy_instance_id(4, 0, NO, 0);                     \
     hipLaunchKernelGGL(mlp_forward_kernel<NO>, dim3(blocks), dim3(256), lds_bytes<NO>(), s, tk, \
                        out);                                                                  \
   } while (0)
@@ -382,6 +392,7 @@ static int policy_step_impl(int variant, const float* actor_params, int actor_di
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb)); \
       attr_set = true;                                                                          \
     }                                                                                           \
+    coop::g_policy_last_instance = coop::policy_instance_id(2, 0, NO, 0);                       \
     hipLaunchKernelGGL(policy_step_kernel<NO>, dim3(nba + nbc), dim3(256), lb, s, ta, tc, nba,  \
                        action_mask, slo, shi, step, row_offset, value_broadcast, greedy, so);   \
   } while (0)

@@ -906,6 +906,7 @@ int launch_train(const TrainTask& tk, int n_slab, hipStream_t s) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     attr_set = true;
   }
+  g_train_last_instance = train_instance_id(1, ACTOR, CONT, false, NO, KT1, XV);
   hipLaunchKernelGGL((ppo_train_kernel<NO, KT1, ACTOR, XV, CONT>), dim3(n_slab), dim3(256), lb, s, tk, L);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
@@ -964,6 +965,12 @@ static constexpr unsigned long long* g_stamps = nullptr;
 //     (discrete actor / critic, input width <= 287); everything else stays on mode 0.
 
 extern "C" int mava_adv_stats_blocks(void) { return STATS_BLOCKS; }
+
+// Diagnostic (not part of include/mava_hip.h, like mava_debug_rollout_last_instance): which instance of the three gradient
+// kernel families the last launch of this process used (encoding: ppo_train_task.h), so that a parity test can assert WHICH
+// instantiation it checked (tests/test_gpu_instances.py).  Read-only; a refused launch leaves it unchanged.
+int g_train_last_instance = 0;
+extern "C" int mava_debug_train_last_instance(void) { return g_train_last_instance; }
 
 extern "C" int mava_adv_stats_f64(const float* adv, const int32_t* idx, long idx_base, int Rb, int A,
                                   double* partials, hipStream_t s) {

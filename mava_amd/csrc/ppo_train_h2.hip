@@ -235,15 +235,21 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     }
     W3h[s] = split8(v);
   }
-  Frag W3d;  // actor: A of dz2 = W3 . dy: W3[f = 32w + r][o = 8h + e]
+  // actor: A of dz2 = W3 . dy: W3[f = 32w + r][o = 16s + 8h + e], one 16-output k-step per 16 outputs of the head (a single
+  // step covers outputs 0 .. 15 only: with more than 16 actions the second one carries the rest of dy back)
+  constexpr int ND = NO > 16 ? 2 : 1;
+  Frag W3d[ND];
   if (CHAIN && ACTOR) {
-    float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int o = 8 * h + e;
-      v[e] = (o < no) ? P[oW3 + (32 * w + r) * no + o] * W3_SCALE : 0.0f;
+    for (int s = 0; s < ND; ++s) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int o = 16 * s + 8 * h + e;
+        v[e] = (o < no) ? P[oW3 + (32 * w + r) * no + o] * W3_SCALE : 0.0f;
+      }
+      W3d[s] = split8(v);
     }
-    W3d = split8(v);
   }
   __syncthreads();
   const float adv_mean = ACTOR ? misc[0] : 0.0f;
@@ -735,12 +741,13 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
         const Frag b = sw_read_tr(H2I, SW_PLANE, trS, s, w);
         gW3 = mfma3(a, b, gW3);
       }
-      // dz2^T[f][row] = sum_o W3[f][o] dy[row][o]: one 16-output step
+      // dz2^T[f][row] = sum_o W3[f][o] dy[row][o]: one 16-output step per 16 outputs
 #pragma unroll
       for (int q = 0; q < 16; ++q) dz[q] = 0.0f;
-      {
-        const Frag b = read_row_frag(DYI, DY_PLANE, r * DY_ROW + 16 * h);
-        dz = mfma3(W3d, b, dz);
+#pragma unroll
+      for (int s = 0; s < ND; ++s) {
+        const Frag b = read_row_frag(DYI, DY_PLANE, r * DY_ROW + 32 * s + 16 * h);
+        dz = mfma3(W3d[s], b, dz);
       }
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -1038,6 +1045,7 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
     fresh = 0;
     w1p = buf;
   }
+  g_train_last_instance = train_instance_id(2, ACTOR, false, WIDE, NO, S1, XV);
   hipLaunchKernelGGL((ppo_train_h2_kernel<NO, S1, ACTOR, WIDE, XV>), dim3(n_slab), dim3(WIDE ? 512 : 256), L.end, s, tk, L,
                      w1p);
   MAVA_LAUNCH_CHECK();

@@ -40,3 +40,11 @@ struct mava_ctx;
 // return convention.  Tried first by mava_train_h2_launch unless the handle's MAVA_CTX_TRAIN_VARIANT is 1.
 int mava_train_w8_launch(const TrainTask& tk, int n_slab, bool actor, hipStream_t s);
 int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk, int n_slab, bool actor, hipStream_t s);
+
+// Diagnostic (ppo_train.hip: mava_debug_train_last_instance): the template instance the last gradient launch of this
+// process used, as FAMILY * 1000000 + ROLE * 100000 + NO * 1000 + K * 10 + XV - FAMILY 1: ppo_train_kernel (exact f32, K = KT1),
+// 2: ppo_train_h2_kernel (K = S1), 3: ppo_train_w8_kernel (K = S1); ROLE = ACTOR + 2 * CONT + 4 * WIDE.
+extern int g_train_last_instance;
+constexpr int train_instance_id(int family, bool actor, bool cont, bool wide, int no, int k, int xv) {
+  return family * 1000000 + ((actor ? 1 : 0) + (cont ? 2 : 0) + (wide ? 4 : 0)) * 100000 + no * 1000 + k * 10 + xv;
+}

@@ -798,6 +798,7 @@ int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
                                        L.end));
     attr_set = true;
   }
+  g_train_last_instance = train_instance_id(3, ACTOR, false, false, NO, S1, XV);
   hipLaunchKernelGGL((ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>), dim3(n_slab), dim3(512), L.end, s, tk, L);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;

@@ -46,17 +46,22 @@ def scale_of(log_std):
     return softplus(log_std) + MIN_SCALE
 
 
-def log_ndtr(z):
-    """log Phi(z) by erfc on the central range and the 3-term asymptotic series below -10 (tfp float32 branch points)."""
+SQRT2 = float(np.sqrt(2.0))
+LOG2 = float(np.log(2.0))
+
+
+def log_ndtr(z, dtype=np.float64):
+    """log Phi(z) by erfc on the central range and the 3-term asymptotic series below -10 (tfp float32 branch points).
+    `dtype`: the precision of every operation (the constants are Python floats, which take the arrays' precision)."""
     from scipy.special import erfc
 
-    z = np.asarray(z, np.float64)
+    z = np.asarray(z, dtype)
     out = np.empty_like(z)
     hi = z > 5.0
     lo = z <= -10.0
     mid = ~hi & ~lo
-    out[hi] = -0.5 * erfc(z[hi] / np.sqrt(2.0))
-    out[mid] = np.log(0.5 * erfc(-z[mid] / np.sqrt(2.0)))
+    out[hi] = -0.5 * erfc(z[hi] / SQRT2)
+    out[mid] = np.log(0.5 * erfc(-z[mid] / SQRT2))
     zl = z[lo]
     r2 = 1.0 / (zl * zl)
     out[lo] = -0.5 * zl * zl - np.log(-zl) - HALF_LOG_2PI + np.log(1.0 + r2 * (-1.0 + r2 * (3.0 - 15.0 * r2)))
@@ -64,7 +69,7 @@ def log_ndtr(z):
 
 
 def tanh_fldj(x):
-    return 2.0 * (np.log(2.0) - x - softplus(-2.0 * x))
+    return 2.0 * (LOG2 - x - softplus(-2.0 * x))
 
 
 def normal_noise(seed: int, step: int, rows: int, dim: int, stream: int, row_offset: int = 0, gid=None):
@@ -85,15 +90,15 @@ def normal_noise(seed: int, step: int, rows: int, dim: int, stream: int, row_off
     return out
 
 
-def log_prob_terms(action, mean, scale):
-    """Per-dimension log density and its derivatives with respect to mean and scale."""
-    action, mean = np.asarray(action, np.float64), np.asarray(mean, np.float64)
-    scale = np.broadcast_to(np.asarray(scale, np.float64), mean.shape)
+def log_prob_terms(action, mean, scale, dtype=np.float64):
+    """Per-dimension log density and its derivatives with respect to mean and scale, every operation in `dtype`."""
+    action, mean = np.asarray(action, dtype), np.asarray(mean, dtype)
+    scale = np.broadcast_to(np.asarray(scale, dtype), mean.shape)
     yc = np.clip(action, -THRESH, THRESH)
     left, right = yc <= -THRESH, yc >= THRESH
     inv = 1.0 / scale
     z = np.where(left, (-ATANH_THRESH - mean) * inv, (mean - ATANH_THRESH) * inv)
-    l = log_ndtr(z)
+    l = log_ndtr(z, dtype)
     g = np.exp(-0.5 * z * z - HALF_LOG_2PI - l)
     x = np.arctanh(np.where(left | right, 0.0, yc))
     d = (x - mean) * inv
@@ -120,16 +125,20 @@ def split_params(flat, din: int, dim: int):
     return flat[:n], flat[n : n + dim]
 
 
-def actor_loss_and_grad(flat, din, dim, obs, action, old_log_prob, gae_mb, clip_eps, ent_coef, eps):
+def actor_loss_and_grad(flat, din, dim, obs, action, old_log_prob, gae_mb, clip_eps, ent_coef, eps, dtype=None):
     """ff_mappo.py:160-180 with the continuous head.  flat = [MLP | log_std]; action (R, dim); eps (R, dim) the
-    entropy noise.  Returns (total, actor_loss, entropy, flat_grad)."""
+    entropy noise.  Returns (total, actor_loss, entropy, flat_grad).  `dtype` (e.g. np.float32): every input is cast to it and
+    every operation runs in it - how far float32 itself lies from float64 on given rows; None: the MLP in flat's precision,
+    the distribution terms in float64."""
+    if dtype is not None:
+        flat, action, old_log_prob, eps = (np.asarray(a, dtype) for a in (flat, action, old_log_prob, eps))
     fm, ls = split_params(flat, din, dim)
     p = po.mlp_unflatten(fm, din, dim)
     obs = np.asarray(obs, flat.dtype)
     R = obs.shape[0]
     mean, cache = po.mlp_forward(p, obs, keep=True)
     scale = scale_of(ls)
-    lpd, dmean_lp, dscale_lp = log_prob_terms(action, mean, scale)
+    lpd, dmean_lp, dscale_lp = log_prob_terms(action, mean, scale, np.float64 if dtype is None else dtype)
     lp = lpd.sum(-1)
     ratio = np.exp(lp - old_log_prob)
     adv = po.normalise_advantages(np.asarray(gae_mb, flat.dtype))
@@ -143,7 +152,7 @@ def actor_loss_and_grad(flat, din, dim, obs, action, old_log_prob, gae_mb, clip_
     total = loss_actor - ent_coef * entropy
 
     inside = (ratio >= 1.0 - clip_eps) & (ratio <= 1.0 + clip_eps)
-    g1 = np.where(l1 < l2, 1.0, np.where(l1 == l2, 0.5, 0.0))
+    g1 = np.where(l1 < l2, 1.0, np.where(l1 == l2, 0.5, 0.0)).astype(adv.dtype)
     g2 = 1.0 - g1
     dlp = (-(g1 * adv + g2 * adv * inside) / R * ratio)[:, None]
     th = np.tanh(xs)
