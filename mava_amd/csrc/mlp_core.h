@@ -323,11 +323,15 @@ struct Categorical {
     float se = 0.0f;
 #pragma unroll
     for (int o = 0; o < NO; ++o) se += expf(z[o] - mx);
-    const float lse = mx + logf(se);
+    // A row without a legal action (mx stayed at finfo.min) is uniform over its `no` real slots, as the reference's
+    // softmax of an all-finfo.min row is: log_prob = -log(no); the padding slots o >= no are no part of it (DESIGN.md,
+    // "rows without a legal action").  Such a row is computed as logits 0 on the real slots; every other row exactly as before.
+    const bool none = (mx == -FLT_MAX);
+    const float lse = none ? logf((float)no) : mx + logf(se);
     entropy = 0.0f;
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
-      logp[o] = z[o] - lse;
+      logp[o] = ((none && o < no) ? 0.0f : z[o]) - lse;
       p[o] = expf(logp[o]);
       entropy -= (p[o] > 0.0f) ? p[o] * logp[o] : 0.0f;
     }

@@ -542,7 +542,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
         auto add_op = [](float a, float b) { return a + b; };
         const float mx = group_allreduce<NO>(z, fmax_op);
         const float se = group_allreduce<NO>(expf(z - mx), add_op);
-        const float logp = z - (mx + logf(se));
+        // a row without a legal action (mx stayed at finfo.min) is uniform over its `no` real outputs (mlp_core.h Categorical)
+        const float logp = (mx == -FLT_MAX) ? ((lo < no) ? -logf((float)no) : -FLT_MAX) : z - (mx + logf(se));
         const float pr = expf(logp);
         const float ent = group_allreduce<NO>((pr > 0.0f) ? -(pr * logp) : 0.0f, add_op);
         const int act = r_act;

@@ -361,12 +361,15 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
 #pragma unroll
         for (int k = 0; k < OPL; ++k) se += expf(z[k] - mx);
         se = group_allreduce<8>(se, add_op);
-        const float lse = mx + logf(se);
+        // a row without a legal action (mx stayed at finfo.min) is uniform over its `no` real outputs: computed as logits 0 on
+        // them (mlp_core.h Categorical); padding outputs are no part of it
+        const bool none = (mx == -FLT_MAX);
+        const float lse = none ? logf((float)no) : mx + logf(se);
         const int act = r_act[0];
         float ent = 0.0f, lp = 0.0f;
 #pragma unroll
         for (int k = 0; k < OPL; ++k) {
-          logp[k] = z[k] - lse;
+          logp[k] = ((none && l8 + 8 * k < no) ? 0.0f : z[k]) - lse;
           pr[k] = expf(logp[k]);
           ent += (pr[k] > 0.0f) ? -(pr[k] * logp[k]) : 0.0f;
           lp += (l8 + 8 * k == act) ? logp[k] : 0.0f;

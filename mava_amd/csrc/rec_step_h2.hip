@@ -492,7 +492,8 @@ __device__ __forceinline__ void rec_step_h2_body(const NetH2& nh, const RecStepO
 #pragma unroll
       for (int k = 0; k < OPL; ++k) se += expf(z[k] - mx);
       se = h2::group_allreduce<8>(se, add_op);
-      const float lse = mx + logf(se);
+      // a row without a legal action (mx stayed at finfo.min) is uniform over its `no` real outputs (mlp_core.h Categorical)
+      const float lse = (mx == -FLT_MAX) ? logf((float)no) : mx + logf(se);
       float best = -FLT_MAX;
 #pragma unroll
       for (int k = 0; k < OPL; ++k) {
@@ -519,7 +520,7 @@ __device__ __forceinline__ void rec_step_h2_body(const NetH2& nh, const RecStepO
       float lp = 0.0f;
 #pragma unroll
       for (int k = 0; k < OPL; ++k)
-        if (l8 + 8 * k == a) lp = z[k] - lse;
+        if (l8 + 8 * k == a) lp = ((mx == -FLT_MAX) ? 0.0f : z[k]) - lse;
       lp = h2::group_allreduce<8>(lp, add_op);
       if (l8 == 0) {
         out.action[row] = a;

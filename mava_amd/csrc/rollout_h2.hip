@@ -523,7 +523,8 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
         auto add_op = [](float p, float q) { return p + q; };
         const float mx = group_allreduce<NO>(z, fmax_op);
         const float se = group_allreduce<NO>(expf(z - mx), add_op);
-        const float logp = z - (mx + logf(se));
+        // a row without a legal action (mx stayed at finfo.min) is uniform over its `no` real outputs (mlp_core.h Categorical)
+        const float logp = (mx == -FLT_MAX) ? ((o < no) ? -logf((float)no) : -FLT_MAX) : z - (mx + logf(se));
         // Gumbel-max: argmax_o z[o] - log(-log(u_o)), first index wins ties (jax.random.categorical; the noise is
         // this library's Philox stream: counter (global row, step, o / 4, "POLI"))
         // (drawn before barrier 1 of this step: see forward())

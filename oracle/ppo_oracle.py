@@ -135,8 +135,11 @@ def masked_logits(logits, mask):
 
 
 def log_softmax(z):
-    m = z.max(-1, keepdims=True)
-    return z - (m + np.log(np.exp(z - m).sum(-1, keepdims=True)))
+    """jax.nn.log_softmax: shifted = z - max, shifted - log(sum(exp(shifted))).  The order matters on a row whose every entry is
+    finfo(f32).min (no legal action, networks.py:116-120): shifted is 0 there, the row is uniform, log_prob = -log(n); added to
+    the maximum first, log(n) would vanish in the rounding of 3.4e38."""
+    s = z - z.max(-1, keepdims=True)
+    return s - np.log(np.exp(s).sum(-1, keepdims=True))
 
 
 def categorical_entropy(logp):

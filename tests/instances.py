@@ -294,6 +294,7 @@ def actor_data(c: ActorCase):
     one = rows_sel[5]  # a selected row with a single legal action
     mask[one] = False
     mask[one, action[one]] = True
+    mask[rows_sel[9]] = False  # a selected row without a legal action: uniform over its nA actions, no gradient into its logits
     adv = (rng.standard_normal(rows) * 2.0 + 0.3).astype(np.float32)
     flat = _net(rng, din, nA)
     # old log-probs close to the current ones: both sides of the clip range
@@ -428,6 +429,7 @@ def _forward_cases():
 STEP_CASES = _step_cases()
 FORWARD_CASES = _forward_cases()
 STEP_NUMBER, ROW_OFFSET = 5, 7
+NONE_LEGAL_ROW = 6
 
 
 def top_two_gap(scores):
@@ -456,9 +458,11 @@ def step_data(c: StepCase):
         mask[:, 0] = True
         mask[3, :] = False  # a row with a single legal action, not the first one
         mask[3, nA // 2] = True
+        mask[NONE_LEGAL_ROW, :] = False  # a row without a legal action: an exact tie at finfo.min, the first index wins
+        dec = np.arange(rows) != NONE_LEGAL_ROW
         y = po.mlp_forward(po.mlp_unflatten(fa.astype(np.float64), c.actor_din, nA), av.astype(np.float64))
         z = po.masked_logits(y, mask)
-        if top_two_gap(z).min() >= GAP:
+        if top_two_gap(z)[dec].min() >= GAP:
             break
     else:
         return None
@@ -467,7 +471,7 @@ def step_data(c: StepCase):
     for s in range(64):
         u = philox.policy_uniforms(s, STEP_NUMBER, rows, nA, row_offset=ROW_OFFSET)
         sc = z + -np.log(-np.log(u.astype(np.float64)))
-        if top_two_gap(sc).min() >= GAP:
+        if top_two_gap(sc)[dec].min() >= GAP:
             seed = s
             break
     if seed is None:
@@ -476,8 +480,9 @@ def step_data(c: StepCase):
     v = po.mlp_forward(po.mlp_unflatten(fc.astype(np.float64), c.critic_din, 1), gs.astype(np.float64))[:, 0]
     forced = ((sampled + 1 + np.arange(rows)) % nA).astype(np.int32)  # other actions than the sampled ones, legal or not
     forced = np.where(mask[np.arange(rows), forced], forced, sampled).astype(np.int32)
+    forced[NONE_LEGAL_ROW] = nA - 1  # every action of that row has log_prob = -log(nA)
     return dict(fa=fa, fc=fc, av=av, gs=gs, mask=mask, share=share, seed=seed, logits=y, lsm=lsm, sampled=sampled,
-                greedy=np.argmax(z, axis=-1).astype(np.int32), value=v, forced=forced, one_legal_row=3)
+                greedy=np.argmax(z, axis=-1).astype(np.int32), value=v, forced=forced, one_legal_row=3, none_legal_row=NONE_LEGAL_ROW)
 
 
 @lru_cache(maxsize=None)

@@ -210,6 +210,8 @@ def test_policy_step_instance(dev, c):
     assert_close(value.cpu().numpy(), np.repeat(d["value"], share), 1e-5, "value")
     one = d["one_legal_row"]
     assert d["mask"][one].sum() == 1 and d["mask"][one, a[one]] and abs(float(logp[one])) <= 1e-6, "row with one legal action"
+    none = d["none_legal_row"]  # no legal action: uniform over the nA real actions (padding slots never enter the softmax sum)
+    assert not d["mask"][none].any() and a[none] == 0 and abs(float(logp[none]) + np.log(nA)) <= 1e-5, "row without a legal action"
 
     if actor_id != last_id:  # block-cooperative kernels, one launch per network: the actor's launch alone
         action_a, logp_a, _, _ = ops.policy_step(fa, fc, av, mask, gs, critic_share=share, critic_rows=0, **kw)

@@ -5,6 +5,7 @@ import torch
 
 from oracle import rec_oracle as ro
 from tests.conftest import assert_close, check_and_sync_f16x2_state
+from tests.seq_model import from_t32 as _from_t32, to_t32 as _to_t32
 
 pytestmark = pytest.mark.gpu
 
@@ -14,16 +15,6 @@ def _t(a, dev, dtype=None):
     if dtype is not None:
         t = t.to(dtype)
     return t.to(dev)
-
-
-def _to_t32(a):
-    """(rows, N) row-major numpy -> T32 flat numpy."""
-    rows, N = a.shape
-    return a.reshape(rows // 32, 32, N).transpose(0, 2, 1).reshape(-1).copy()
-
-
-def _from_t32(flat, rows, N):
-    return np.asarray(flat).reshape(rows // 32, N, 32).transpose(0, 2, 1).reshape(rows, N)
 
 
 @pytest.fixture(params=[0, 1], ids=["f32", "f16x2"])
@@ -488,6 +479,7 @@ def test_fused_rec_step_matches_oracle(dev, E, A, din, S, nA, share):
     xc = rng.standard_normal((Rc, S)).astype(np.float32)
     mask = rng.random((R, nA)) > 0.3
     mask[:, 0] = True
+    mask[7] = False  # a row without a legal action: uniform over the nA actions, index 0 wins the exact tie
     done_a = rng.random(R) < 0.3
     done_c = rng.random(Rc) < 0.3
     ha = rng.standard_normal((R, 128)).astype(np.float32)
@@ -521,10 +513,13 @@ def test_fused_rec_step_matches_oracle(dev, E, A, din, S, nA, share):
     torch.cuda.synchronize()
     a, a2 = action.cpu().numpy()[:R], a2.cpu().numpy()[:R]
     assert (a != a2).mean() < 0.02  # f32 logits vs f64-derived logits: near-ties of the Gumbel scores only
-    assert mask[np.arange(R), a].all(), "sampled an illegal action"
-    z = np.where(mask, ya[0], np.finfo(np.float32).min)
-    lsm = z - np.log(np.exp(z - z.max(-1, keepdims=True)).sum(-1, keepdims=True)) - z.max(-1, keepdims=True)
+    assert mask[np.arange(R), a][np.arange(R) != 7].all(), "sampled an illegal action"
+    from oracle import ppo_oracle as po
+
+    lsm = po.log_softmax(np.where(mask, ya[0], np.finfo(np.float32).min))
     assert_close(logp.cpu().numpy()[:R], lsm[np.arange(R), a], 1e-5, "log_prob")
+    assert a[7] == 0 and a2[7] == 0 and np.allclose(lsm[7], -np.log(nA), rtol=0, atol=1e-12)
+    assert abs(float(logp[7]) + np.log(nA)) <= 1e-5 and abs(float(lp2[7]) + np.log(nA)) <= 1e-5, "row without a legal action"
 
 
 RCNN = dict(shape=(2, 7, 1), channels=[8, 8], kernels=[3, 3], strides=[1, 1])  # network/rcnn.yaml-style CNN pre-torso: 14 = A + O inputs

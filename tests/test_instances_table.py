@@ -123,6 +123,7 @@ def test_every_gradient_case_has_a_finite_nonzero_oracle(kind):
             assert np.isfinite(d["grad"]).all() and np.isfinite(d["sums"]).all() and _blocks_nonzero(d["grad"], c.din, c.n_actions), c
             sel = d["mask"][d["rows_sel"]]
             assert (sel.sum(1) == 1).any(), "a selected row with a single legal action"
+            assert (sel.sum(1) == 0).sum() == 1, "a selected row without a legal action"
             assert (d["ratio"] > 1.2).any() and (d["ratio"] < 0.8).any() and ((d["ratio"] > 0.8) & (d["ratio"] < 1.2)).any(), c
             assert len(set(d["idx"].tolist())) == I.RB and not np.array_equal(d["idx"], np.sort(d["idx"]))
     elif kind == "critic":
@@ -143,8 +144,12 @@ def test_every_acting_case_has_a_decided_oracle():
     for c in I.STEP_CASES:
         d = I.step_data(c)
         assert d is not None, c
-        assert 0 <= d["seed"] < 64 and d["mask"][np.arange(c.rows), d["sampled"]].all() and d["mask"][np.arange(c.rows), d["forced"]].all()
+        some = np.arange(c.rows) != d["none_legal_row"]
+        assert 0 <= d["seed"] < 64 and d["mask"][np.arange(c.rows), d["sampled"]][some].all() and d["mask"][np.arange(c.rows), d["forced"]][some].all()
         assert d["mask"][d["one_legal_row"]].sum() == 1
+        none = d["none_legal_row"]  # uniform over the real actions; the exact tie at finfo.min goes to index 0
+        assert not d["mask"][none].any() and d["sampled"][none] == 0 and d["greedy"][none] == 0
+        assert np.allclose(d["lsm"][none], -np.log(c.n_actions), rtol=0, atol=1e-12)
         assert np.isfinite(d["logits"]).all() and np.isfinite(d["value"]).all()
         if c.n_actions > 1 and c.rows < 1000:
             assert len(set(d["sampled"].tolist())) > 1, c
