@@ -315,6 +315,44 @@ int mava_rware_step_real_next(int E, int A, int S, int R, int H, int W, int sens
                               float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
                               float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
+/* ---- Connector environment step (mava_amd/csrc/connector.hip; rules in DESIGN.md "Connector", stated in
+ *      tests/connector_model.py, which is the contract; parity with Jumanji's MaConnector is unpinned).  E environments
+ *      of a G x G board (3 <= G <= 16) with A agents (1 <= A <= 32, 2 A <= G G - 2).  Actions (E, A) int32: 0 NOOP, 1 UP
+ *      (row - 1), 2 RIGHT (col + 1), 3 DOWN (row + 1), 4 LEFT (col - 1).  State (struct of arrays, advanced in place):
+ *      head (E, A, 2) and target (E, A, 2) as (row, col), connected (E, A) u8, grid (E, G, G) u8 with 0 empty and
+ *      1 + 3k / 2 + 3k / 3 + 3k a path cell / the head / the target of agent k (a head on its own target is stored as
+ *      head), step_count (E, A) and the RecordEpisodeMetrics words, as mava_lbf_step.  One step, every test made on the
+ *      grid at its start: an unconnected agent moves iff its destination is on the grid and empty or its own target, and
+ *      no other agent wants the same cell; it leaves a path cell behind and is connected on its target.  Team reward
+ *      (repeated per agent) = (100 c - 3 o) / 100 with c the agents that connected on this step and o those not
+ *      connected at its start.  The episode terminates when no agent has a legal move (all connected or blocked) and is
+ *      truncated at time_limit.  Outputs: agents_view (E, A, G G 5), cell-major with the channels last and NO agent id in
+ *      front: for a cell of agent k seen by agent j, rel = ((k - j) mod A) + 1, [rel / A on a head, rel / A on a target,
+ *      1 on a path, 1 on j's own head, 1 on j's own target]; global_state (E, 1, G G 3) = agent 0's channels 0..2;
+ *      action_mask (E, A, 5) u8 (NOOP always, a move iff it would be allowed); obs_step_count, reward, done (E, A);
+ *      info_* (E).  is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a terminal step
+ *      regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`, counter
+ *      (env_offset + e, t + *t_base, block, "CONR"); t_base (a device word, may be NULL) is added on the device, so the
+ *      step replays from a captured graph.  No host state, no synchronisation. */
+int mava_connector_step(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                        uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
+                        uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                        int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                        int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
+                        uint8_t* info_terminal, const int32_t* action, mava_stream_t s);
+
+/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
+ * (E, A, G G 5) / real_mask (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
+ * 1 when no agent has a legal move - a time-limit end alone is a truncation.  None of the three is written on a reset
+ * call (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
+int mava_connector_step_real_next(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                                  uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
+                                  uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length,
+                                  float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                                  uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                                  float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
+                                  float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments

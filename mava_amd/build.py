@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "synth_rware.hip",
     "lbf.hip",
     "rware.hip",
+    "connector.hip",
     "q_learning.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",

@@ -116,18 +116,6 @@ class RecLearner:
         self.Rm = self.Em * self.A
         if self.Rm % 32:
             raise ValueError(f"(num_envs / num_minibatches) * num_agents = {self.Rm} must be a multiple of 32")
-        # Centralised critic on a global state shared by the A agents of an env: identical inputs, done flags and
-        # initial hidden states give A identical hidden trajectories and values (the reference tiles the state and
-        # runs all A, networks.py:306-331).  The critic then runs ONCE per env - E sequences instead of E*A - and the
-        # sequence loss adds up the A agents' loss gradients per row (mava_seq_critic_loss_f32, agents_per_row = A).
-        self.critic_agg = bool(centralised_critic and self.critic_share == self.A and self.A > 1
-                               and self.E % 32 == 0 and self.Em % 32 == 0 and os.environ.get("MAVA_REC_CRITIC_AGG", "1") != "0")
-        self.Ac = 1 if self.critic_agg else self.A            # critic sequences per env
-        self.Rmc = self.Em * self.Ac                            # critic rows per time step of a minibatch
-        if self.critic_agg:
-            for rep in self.reps:
-                rep.set_critic_rows(1)
-
         net = config.network
         from .generic_networks import CNNTorso, GenericMLPTorso
 
@@ -154,6 +142,18 @@ class RecLearner:
         self.critic_network = RecurrentValueNet(*torsos(net.critic_network, general=wide), centralised_critic, self.Oc, hsd, state_shape)
         self.actor_network.ctx = self.critic_network.ctx = self.ctx
         self.generic_nets = self.actor_network.generic or self.critic_network.generic
+        # Centralised critic on a global state shared by the A agents of an env: identical inputs, done flags and
+        # initial hidden states give A identical hidden trajectories and values (the reference tiles the state and
+        # runs all A, networks.py:306-331).  The critic then runs ONCE per env - E sequences instead of E*A - and the
+        # sequence loss adds up the A agents' loss gradients per row (mava_seq_critic_loss_f32, agents_per_row = A).
+        self.critic_agg = bool(centralised_critic and self.critic_share == self.A and self.A > 1
+                               and self.E % 32 == 0 and self.Em % 32 == 0 and os.environ.get("MAVA_REC_CRITIC_AGG", "1") != "0"
+                               and not self.critic_network.generic)  # (the general path's workspaces hold E * A rows)
+        self.Ac = 1 if self.critic_agg else self.A            # critic sequences per env
+        self.Rmc = self.Em * self.Ac                            # critic rows per time step of a minibatch
+        if self.critic_agg:
+            for rep in self.reps:
+                rep.set_critic_rows(1)
         self.Pa, self.Pc = self.actor_network.num_params, self.critic_network.num_params
         self.P = self.Pa + self.Pc
 

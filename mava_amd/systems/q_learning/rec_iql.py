@@ -44,8 +44,9 @@ def _check_config(config: Config) -> None:
     if qn is None or not (_learner._default_torso(qn.get("pre_torso")) and _learner._default_torso(qn.get("post_torso"))):
         raise NotImplementedError("rec_iql runs network/rnn.yaml's q_network torsos only (MLPTorso [128] relu)")
     native_rware = config.env.get("env_name", None) == "RobotWarehouse" and bool(config.env.get("native", False))
-    if config.env.get("env_name", None) != "LevelBasedForaging" and not native_rware:
-        raise ValueError(f"rec_iql needs an environment that returns its pre-reset observation (env=lbf); "
+    if config.env.get("env_name", None) not in ("LevelBasedForaging", "MaConnector") and not native_rware:
+        raise ValueError(f"rec_iql needs an environment that returns its pre-reset observation (env=lbf, "
+                         f"env=rware_native, env=connector); "
                          f"{config.env.get('env_name', None)} runs on the synthetic stand-in, which does not")
 
 
