@@ -353,6 +353,51 @@ int mava_connector_step_real_next(int E, int A, int G, int time_limit, uint64_t 
                                   float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
                                   float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
+/* ---- Cleaner environment step (mava_amd/csrc/cleaner.hip; rules in DESIGN.md "Cleaner", stated in
+ *      tests/cleaner_model.py, which is the contract; parity with Jumanji's Cleaner is unpinned).  E environments of an
+ *      R x C board (3 <= R, C <= 32, rectangles allowed) with A agents (1 <= A <= 32) that may share a cell.  One byte
+ *      per cell: 0 dirty, 1 clean, 2 wall.  Actions (E, A) int32: 0 UP (row - 1), 1 RIGHT (col + 1), 2 DOWN (row + 1),
+ *      3 LEFT (col - 1); there is no no-op, and any other value is an invalid action.  State (struct of arrays, advanced
+ *      in place): pos (E, A, 2) as (row, col), grid (E, R, C) u8, step_count (E, A) and the RecordEpisodeMetrics words,
+ *      as mava_lbf_step.
+ *      Reset: rooms are the cells with even row and even column, nr = (R + 1) / 2 by nc = (C + 1) / 2 of them; every
+ *      other cell starts as a wall.  Room q = i nc + j has the edge 2q to room (i, j + 1) through cell (2i, 2j + 1) and
+ *      the edge 2q + 1 to room (i + 1, j) through cell (2i + 1, 2j), each only where that room exists (ids are skipped,
+ *      not renumbered).  Edge n has the key "draw n" = word n % 4 of Philox block n / 4; the maze opens exactly the cells
+ *      of the minimum spanning tree under the weight (key, id), compared lexicographically: 2 nr nc - 1 open cells, an
+ *      even R (C) leaves a solid last row (column).  All open cells are dirty, all agents start at (0, 0), which is
+ *      cleaned at once, step_count = 0.
+ *      One step: (1) an agent whose destination is on the board and not a wall moves, any other stays and its action
+ *      was invalid; (2) every dirty cell that now holds an agent becomes clean, n = the number of such CELLS; (3) team
+ *      reward n - 0.5, repeated per agent; (4) step_count += 1; won = no dirty cell left, invalid = some action was
+ *      invalid; done = won | invalid | step_count >= time_limit; terminated = won | invalid (a time-limit end alone is
+ *      a truncation); info_won = done & won.  Outputs: agents_view (E, A, R C 4), cell-major with the channels last and
+ *      NO agent id in front: [dirty, wall, agents in the cell as a float, 1 on the viewer's own cell]; global_state
+ *      (E, 1, R C 3) = the first three channels; action_mask (E, A, 4) u8 = validity of each move on the new board (every
+ *      agent always has a legal move); obs_step_count, reward, done (E, A); info_* (E); info_won (E) u8 may be NULL.
+ *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL, info_won is not written); a
+ *      terminal step regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`,
+ *      counter (env_offset + e, t + *t_base, block, "CLNR"); t_base (a device word, may be NULL) is added on the device,
+ *      so the step replays from a captured graph.  No host state, no synchronisation. */
+int mava_cleaner_step(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                      uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid, int32_t* step_count,
+                      float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                      float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                      float* info_return, int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won,
+                      const int32_t* action, mava_stream_t s);
+
+/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
+ * (E, A, R C 4) / real_mask (E, A, 4) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
+ * won | invalid - a time-limit end alone is a truncation.  None of the three is written on a reset call (they may then
+ * be NULL); otherwise they must not alias agents_view / action_mask. */
+int mava_cleaner_step_real_next(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t,
+                                const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid,
+                                int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                                int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
+                                float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments

@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "lbf.hip",
     "rware.hip",
     "connector.hip",
+    "cleaner.hip",
     "q_learning.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",

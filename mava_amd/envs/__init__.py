@@ -1,4 +1,5 @@
-from . import connector, lbf, rware, synthetic_rware
+from . import cleaner, connector, lbf, rware, synthetic_rware
+from .cleaner import Cleaner  # noqa: F401
 from .connector import Connector  # noqa: F401
 from .lbf import LevelBasedForaging  # noqa: F401
 from .rware import RobotWarehouse  # noqa: F401
@@ -7,7 +8,7 @@ from .synthetic_rware import SyntheticRware  # noqa: F401
 
 def make(config, add_global_state: bool = False, device=None, env_offset: int = 0):
     """mava/utils/make_env.py:215-240: (train_env, eval_env) of the configuration's environment.  `env=lbf` builds the
-    Level-Based Foraging environment, `env=connector` Connector and an env group marked `native: true`
+    Level-Based Foraging environment, `env=connector` Connector, `env=cleaner` Cleaner and an env group marked `native: true`
     (`env=rware_native`) the Robot Warehouse; every other environment name keeps the synthetic stand-in."""
     if config.env.get("env_name", None) == "LevelBasedForaging":
         mk = lbf.make
@@ -15,6 +16,8 @@ def make(config, add_global_state: bool = False, device=None, env_offset: int = 
         mk = rware.make
     elif config.env.get("env_name", None) == "MaConnector":
         mk = connector.make
+    elif config.env.get("env_name", None) == "Cleaner":
+        mk = cleaner.make
     else:
         mk = synthetic_rware.make
     return mk(config, add_global_state=add_global_state, device=device, env_offset=env_offset)

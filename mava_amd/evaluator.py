@@ -45,19 +45,23 @@ def make_rec_eval_act_fn(actor_apply_fn: Callable, config) -> Callable:
 
 def get_eval_fn(env, act_fn: Callable, config, absolute_metric: bool) -> Callable:
     """Every env of `env` plays one episode per loop; metrics are taken at the first terminal step of
-    each env (mava/evaluator.py:139-148)."""
+    each env (mava/evaluator.py:139-148).  When config.env.log_win_rate is set and the env's extras carry `won_episode`
+    (Cleaner), the flag of that same step is returned too (:142-143); otherwise the dict has the two metrics only.  An
+    env that never ends inside its time limit counts as not won."""
     n_episodes = int(config.arch.num_absolute_metric_eval_episodes if absolute_metric else config.arch.num_eval_episodes)
     loops = max(1, -(-n_episodes // env.num_envs))
+    log_win_rate = bool(config.env.get("log_win_rate", False))
 
     def eval_fn(params: Any, seed: int, init_act_state: Any = None) -> Dict[str, torch.Tensor]:
         gen = torch.Generator(device=env.device).manual_seed(int(seed))
-        rets, lens = [], []
+        rets, lens, wons = [], [], []
         for _ in range(loops):
             state, ts = env.reset()
             E = env.num_envs
             finished = torch.zeros(E, dtype=torch.bool, device=env.device)
             ep_ret = torch.zeros(E, device=env.device)
             ep_len = torch.zeros(E, dtype=torch.int32, device=env.device)
+            won = torch.zeros(E, dtype=torch.bool, device=env.device) if (log_win_rate and "won_episode" in ts.extras) else None
             act_state = init_act_state or {}
             for _t in range(int(env.time_limit)):
                 action, act_state = act_fn(params, ts, gen, act_state)
@@ -66,11 +70,18 @@ def get_eval_fn(env, act_fn: Callable, config, absolute_metric: bool) -> Callabl
                 newly = m["is_terminal_step"] & ~finished
                 ep_ret = torch.where(newly, m["episode_return"], ep_ret)
                 ep_len = torch.where(newly, m["episode_length"], ep_len)
+                if won is not None:
+                    won = torch.where(newly, ts.extras["won_episode"].bool(), won)
                 finished |= newly
                 if bool(finished.all()):
                     break
             rets.append(ep_ret)
             lens.append(ep_len)
-        return {"episode_return": torch.cat(rets), "episode_length": torch.cat(lens)}
+            if won is not None:
+                wons.append(won)
+        out = {"episode_return": torch.cat(rets), "episode_length": torch.cat(lens)}
+        if wons:
+            out["won_episode"] = torch.cat(wons)
+        return out
 
     return eval_fn

@@ -145,6 +145,8 @@ def run_experiment(_config: Config, learner_setup: Callable, make_env: Callable,
             logger.log(eval_metrics, t, eval_step, LogEvent.EVAL)
         eval_return = float(eval_metrics["episode_return"].float().mean())
         rec["eval_episode_return"] = eval_return
+        if "won_episode" in eval_metrics:  # env.log_win_rate on an env that reports wins (mava/utils/logger.py:82-99)
+            rec["win_rate"] = 100.0 * float(eval_metrics["won_episode"].float().mean())
         emit(rec)
         if bool(config.arch.absolute_metric) and max_episode_return <= eval_return:
             best_params = trained_params  # copy.deepcopy(trained_params), ff_mappo.py:537-539: already a snapshot
@@ -161,7 +163,10 @@ def run_experiment(_config: Config, learner_setup: Callable, make_env: Callable,
         abs_metrics = abs_evaluator(best_params, key, init_act_state)
         if logger is not None:
             logger.log(abs_metrics, t, int(config.arch.num_evaluation) - 1, LogEvent.ABSOLUTE)
-        emit({"timestep": t, "absolute_episode_return": float(abs_metrics["episode_return"].float().mean())})
+        abs_rec = {"timestep": t, "absolute_episode_return": float(abs_metrics["episode_return"].float().mean())}
+        if "won_episode" in abs_metrics:
+            abs_rec["win_rate"] = 100.0 * float(abs_metrics["won_episode"].float().mean())
+        emit(abs_rec)
     if logger is not None:
         logger.stop()
     return eval_return

@@ -44,9 +44,9 @@ def _check_config(config: Config) -> None:
     if qn is None or not (_learner._default_torso(qn.get("pre_torso")) and _learner._default_torso(qn.get("post_torso"))):
         raise NotImplementedError("rec_iql runs network/rnn.yaml's q_network torsos only (MLPTorso [128] relu)")
     native_rware = config.env.get("env_name", None) == "RobotWarehouse" and bool(config.env.get("native", False))
-    if config.env.get("env_name", None) not in ("LevelBasedForaging", "MaConnector") and not native_rware:
+    if config.env.get("env_name", None) not in ("LevelBasedForaging", "MaConnector", "Cleaner") and not native_rware:
         raise ValueError(f"rec_iql needs an environment that returns its pre-reset observation (env=lbf, "
-                         f"env=rware_native, env=connector); "
+                         f"env=rware_native, env=connector, env=cleaner); "
                          f"{config.env.get('env_name', None)} runs on the synthetic stand-in, which does not")
 
 
@@ -94,8 +94,10 @@ def run_experiment(_config: Config, log: Optional[Callable[[Dict[str, Any]], Non
         if logger is not None:
             logger.log(rec, t, idx, getattr(LogEvent, event))
         else:
-            log({"event": event, "timestep": t, **{k: (float(v.float().mean()) if isinstance(v, torch.Tensor) else v)
-                                                   for k, v in rec.items()}})
+            out = {k: (float(v.float().mean()) if isinstance(v, torch.Tensor) else v) for k, v in rec.items()}
+            if "won_episode" in out:  # what MavaLogger.calc_winrate makes of it
+                out["win_rate"] = 100.0 * out.pop("won_episode")
+            log({"event": event, "timestep": t, **out})
 
     eval_return, max_return, best_params, t = 0.0, -float("inf"), None, 0
     n_evals = int(config.arch.num_evaluation)
