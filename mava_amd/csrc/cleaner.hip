@@ -4,7 +4,7 @@
 // ends when nothing is dirty (won), when some agent moves into a wall or off the board, or at the time limit.  Wrapper
 // semantics of the reference's CleanerWrapper: image observations (R, C, 4) per agent WITHOUT a prepended agent id,
 // global_state = the first three channels (the same for every agent), AutoResetWrapper and RecordEpisodeMetrics
-// bookkeeping as lbf.hip, plus the won flag the evaluator turns into a win rate.
+// bookkeeping (env_common.h), plus the won flag the evaluator turns into a win rate.
 //
 // The rules are small and the output is large (clean-30x30x30a: 432 KB of observation per env and step), so the kernel
 // is shaped by its stores.  A workgroup of THREADS = 64 NE threads owns NE environments:
@@ -30,7 +30,7 @@
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
 // graph.  mava_cleaner_step_real_next (the REAL instantiation of the same body) also writes the pre-reset agents_view /
 // action_mask and the `terminated` flag (won or invalid; a time-limit end alone is a truncation).
-#include "common.h"
+#include "env_common.h"
 
 namespace {
 
@@ -88,10 +88,6 @@ struct Tile {
   int sc[NE], term[NE], rst[NE];
   float rew[NE];
 };
-
-__device__ __forceinline__ uint32_t word_of(const Philox4& p, int i) {
-  return i == 0 ? p.x : (i == 1 ? p.y : (i == 2 ? p.z : p.w));
-}
 
 // i / d for 0 <= i < 2^24 and 1 <= d <= 1024, inv = 1.0f / d: the float product is off by at most one
 __device__ __forceinline__ int quot(int i, int d, float inv) {
@@ -242,34 +238,17 @@ __device__ __forceinline__ void cleaner_step_body(const ClnArgs& a, const ClnRea
     if (agent) build_mask(s, a, le, lane);  // the mask of the new board
     if (live && lane == 0) {
       const float rew = (float)n_clean - 0.5f;  // 3. exact in f32
-      const int sc_new = a.step_count[(long)e * A] + 1;
-      const float run_ret = a.run_return[e], ep_ret = a.ep_return[e];
-      const int run_len = a.run_length[e], ep_len = a.ep_length[e];
       const bool terminated = won || any_inval;
-      const bool term = terminated || sc_new >= a.time_limit;
       if constexpr (REAL) rn.terminated[e] = terminated ? 1 : 0;
-      if (a.info_won != nullptr) a.info_won[e] = (term && won) ? 1 : 0;
-      const float new_ret = run_ret + rew;
-      const int new_len = run_len + 1;
-      const float ret_info = term ? new_ret : ep_ret;
-      const int len_info = term ? new_len : ep_len;
-      a.info_return[e] = ret_info;
-      a.info_length[e] = len_info;
-      a.info_terminal[e] = term ? 1 : 0;
-      a.run_return[e] = term ? 0.0f : new_ret;
-      a.run_length[e] = term ? 0 : new_len;
-      a.ep_return[e] = ret_info;
-      a.ep_length[e] = len_info;
+      const EpisodeEnd end = episode_step(episode_book(a), e, a.step_count[(long)e * A], rew, terminated, a.time_limit);
+      if (a.info_won != nullptr) a.info_won[e] = (end.term && won) ? 1 : 0;
       s.rew[le] = rew;
-      s.term[le] = term ? 1 : 0;
-      s.rst[le] = term ? 1 : 0;
-      s.sc[le] = term ? 0 : sc_new;
+      s.term[le] = end.term ? 1 : 0;
+      s.rst[le] = end.term ? 1 : 0;
+      s.sc[le] = end.step_count;
     }
   } else if (live && lane == 0) {
-    a.run_return[e] = 0.0f;
-    a.run_length[e] = 0;
-    a.ep_return[e] = 0.0f;
-    a.ep_length[e] = 0;
+    episode_clear(episode_book(a), e);
   }
   __syncthreads();
   if constexpr (REAL) {

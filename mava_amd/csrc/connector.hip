@@ -3,7 +3,7 @@
 // from their head towards their own target; a cell holds 0 (empty) or 1 + 3k / 2 + 3k / 3 + 3k (path / head / target of
 // agent k).  Wrapper semantics of the reference's ConnectorWrapper: image observations (G, G, 5) per agent WITHOUT a
 // prepended agent id (the channels encode the agent index relative to the viewer), global_state = agent 0's first three
-// channels, team reward repeated per agent, AutoResetWrapper and RecordEpisodeMetrics bookkeeping as lbf.hip.
+// channels, team reward repeated per agent, AutoResetWrapper and RecordEpisodeMetrics bookkeeping (env_common.h).
 //
 // The rules are small and the output is large (con-10x10x10a: 21 KB of observation per env and step), so the kernel is
 // shaped by its stores.  A workgroup of THREADS = 64 NE threads owns NE environments:
@@ -24,7 +24,7 @@
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
 // graph.  mava_connector_step_real_next (the REAL instantiation of the same body) also writes the pre-reset
 // agents_view / action_mask and the `terminated` flag (nobody can move; a time-limit end alone is a truncation).
-#include "common.h"
+#include "env_common.h"
 
 namespace {
 
@@ -84,10 +84,6 @@ struct Tile {
   int sc[NE], term[NE], rst[NE];
   float rew[NE];
 };
-
-__device__ __forceinline__ uint32_t word_of(const Philox4& p, int i) {
-  return i == 0 ? p.x : (i == 1 ? p.y : (i == 2 ? p.z : p.w));
-}
 
 // the cell a move takes (r, c) to, or -1 off the grid
 __device__ __forceinline__ int dest_of(int r, int c, int m, int G) {
@@ -330,32 +326,15 @@ __device__ __forceinline__ void connector_step_body(const ConArgs& a, const ConT
     if (live && lane == 0) {
       // (100 c - 3 o) / 100: both operands exact, one correctly rounded division
       const float rew = __fdiv_rn((float)(100 * n_conn - 3 * n_open), 100.0f);
-      const int sc_new = a.step_count[(long)e * A] + 1;
-      const float run_ret = a.run_return[e], ep_ret = a.ep_return[e];
-      const int run_len = a.run_length[e], ep_len = a.ep_length[e];
-      const bool term = terminated || sc_new >= a.time_limit;
       if constexpr (REAL) rn.terminated[e] = terminated ? 1 : 0;
-      const float new_ret = run_ret + rew;
-      const int new_len = run_len + 1;
-      const float ret_info = term ? new_ret : ep_ret;
-      const int len_info = term ? new_len : ep_len;
-      a.info_return[e] = ret_info;
-      a.info_length[e] = len_info;
-      a.info_terminal[e] = term ? 1 : 0;
-      a.run_return[e] = term ? 0.0f : new_ret;
-      a.run_length[e] = term ? 0 : new_len;
-      a.ep_return[e] = ret_info;
-      a.ep_length[e] = len_info;
+      const EpisodeEnd end = episode_step(episode_book(a), e, a.step_count[(long)e * A], rew, terminated, a.time_limit);
       s.rew[le] = rew;
-      s.term[le] = term ? 1 : 0;
-      s.rst[le] = term ? 1 : 0;
-      s.sc[le] = term ? 0 : sc_new;
+      s.term[le] = end.term ? 1 : 0;
+      s.rst[le] = end.term ? 1 : 0;
+      s.sc[le] = end.step_count;
     }
   } else if (live && lane == 0) {
-    a.run_return[e] = 0.0f;
-    a.run_length[e] = 0;
-    a.ep_return[e] = 0.0f;
-    a.ep_length[e] = 0;
+    episode_clear(episode_book(a), e);
   }
   __syncthreads();
   if constexpr (REAL) {

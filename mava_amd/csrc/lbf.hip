@@ -22,7 +22,7 @@
 // rules produced, BEFORE the auto-reset, and a per-env `terminated` flag (every food eaten).  The reset of ending envs
 // then moves behind one more output pass over the same LDS tile; the plain kernel is the same code with those parts
 // compiled out.
-#include "common.h"
+#include "env_common.h"
 
 namespace {
 
@@ -270,13 +270,13 @@ __device__ __forceinline__ void lbf_step_body(const LbfArgs& a, const LbfReal& r
     const int le = tid, e = e0 + tid;
     const uint32_t t = a.t + (a.t_base ? *a.t_base : 0u);
     const uint32_t g = a.env_offset + (uint32_t)e;
+    const EpisodeBook bk = episode_book(a);
     bool reset = a.is_reset != 0;
     float total = 0.0f;
     if (!a.is_reset) {
       total = a.total_food_level[e];
       const int sc_old = a.step_count[(long)e * A];
-      const float run_ret = a.run_return[e], ep_ret = a.ep_return[e];
-      const int run_len = a.run_length[e], ep_len = a.ep_length[e];
+      const EpisodeRun run = episode_load(bk, e);  // used at the end of the rule phase
       // 1. targets: cancelled outside the grid, onto an alive food, onto any agent's cell at the start of the step
       for (int j = 0; j < A; ++j) {
         const int ac = s.act[j][le];
@@ -324,29 +324,14 @@ __device__ __forceinline__ void lbf_step_body(const LbfArgs& a, const LbfReal& r
       for (int j = 1; j < A; ++j) team = team + s.rew[j][le];
       s.team[le] = team;
       const float mean_rew = a.individual ? team / (float)A : team;
-      // 6. terminal, RecordEpisodeMetrics (mava/wrappers/episode_metrics.py:88-111)
-      const int sc_new = sc_old + 1;
-      const bool term = left == 0 || sc_new >= a.time_limit;
+      // 6. terminal, RecordEpisodeMetrics
       if constexpr (REAL) rn.terminated[e] = left == 0 ? 1 : 0;  // Jumanji: termination vs truncation
-      const float new_ret = run_ret + mean_rew;
-      const int new_len = run_len + 1;
-      const float ret_info = term ? new_ret : ep_ret;
-      const int len_info = term ? new_len : ep_len;
-      a.info_return[e] = ret_info;
-      a.info_length[e] = len_info;
-      a.info_terminal[e] = term ? 1 : 0;
-      a.run_return[e] = term ? 0.0f : new_ret;
-      a.run_length[e] = term ? 0 : new_len;
-      a.ep_return[e] = ret_info;
-      a.ep_length[e] = len_info;
-      s.term[le] = term ? 1 : 0;
-      s.sc[le] = term ? 0 : sc_new;
-      reset = term;
+      const EpisodeEnd end = episode_commit(bk, e, run, sc_old, mean_rew, left == 0, a.time_limit);
+      s.term[le] = end.term ? 1 : 0;
+      s.sc[le] = end.step_count;
+      reset = end.term;
     } else {
-      a.run_return[e] = 0.0f;
-      a.run_length[e] = 0;
-      a.ep_return[e] = 0.0f;
-      a.ep_length[e] = 0;
+      episode_clear(bk, e);
       s.term[le] = 0;
     }
     // 7. (auto-)reset at this step's counter

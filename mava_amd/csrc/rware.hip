@@ -27,7 +27,7 @@
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
 // graph.  mava_rware_step_real_next (the REAL instantiation of the same body) also writes the pre-reset agents_view /
 // action_mask and the `terminated` flag (a collision in collision mode "terminate"; a time-limit end is a truncation).
-#include "common.h"
+#include "env_common.h"
 
 namespace {
 
@@ -113,10 +113,6 @@ struct Tile {
   int sc[NE], term[NE], rst[NE];
   float rew[NE];
 };
-
-__device__ __forceinline__ uint32_t word_of(const Philox4& p, int i) {
-  return i == 0 ? p.x : (i == 1 ? p.y : (i == 2 ? p.z : p.w));
-}
 
 // the k-th (0-based) non-negative integer that is not among the n distinct values arr[0 .. n) (stride NE): the least
 // fixed point of v = k + #{arr <= v}
@@ -333,11 +329,11 @@ __device__ __forceinline__ void rware_step_body(const RwArgs& a, const RwLayout&
   if (tid < ne) {
     const int le = tid, e = e0 + tid;
     const uint32_t g = a.env_offset + (uint32_t)e;
+    const EpisodeBook bk = episode_book(a);
     bool reset = a.is_reset != 0;
     if (!a.is_reset) {
       const int sc_old = a.step_count[(long)e * A];
-      const float run_ret = a.run_return[e], ep_ret = a.ep_return[e];
-      const int run_len = a.run_length[e], ep_len = a.ep_length[e];
+      const EpisodeRun run = episode_load(bk, e);  // used at the end of the rule phase
       // 1. turns; FORWARD unless off the grid or a carried shelf would meet a ground shelf
       for (int j = 0; j < A; ++j) {
         const int ac = s.act[j][le];
@@ -393,33 +389,18 @@ __device__ __forceinline__ void rware_step_body(const RwArgs& a, const RwLayout&
         const Philox4 p = philox4x32_10(g, t, (uint32_t)(j >> 2), RW_QUEUE, a.seed_lo, a.seed_hi);
         s.rq[q][le] = kth_not_in((int)(word_of(p, j & 3) % (uint32_t)(S - R)), &s.rq[0][le], R);
       }
-      // 6. team reward, terminal, RecordEpisodeMetrics (as lbf.hip)
+      // 6. team reward, terminal, RecordEpisodeMetrics
       const float rew = (float)n_del;
       s.rew[le] = rew;
-      const int sc_new = sc_old + 1;
       const bool terminated = coll && a.terminate;
-      const bool term = terminated || sc_new >= a.time_limit;
       if constexpr (REAL) rn.terminated[e] = terminated ? 1 : 0;
-      const float new_ret = run_ret + rew;
-      const int new_len = run_len + 1;
-      const float ret_info = term ? new_ret : ep_ret;
-      const int len_info = term ? new_len : ep_len;
-      a.info_return[e] = ret_info;
-      a.info_length[e] = len_info;
-      a.info_terminal[e] = term ? 1 : 0;
-      a.run_return[e] = term ? 0.0f : new_ret;
-      a.run_length[e] = term ? 0 : new_len;
-      a.ep_return[e] = ret_info;
-      a.ep_length[e] = len_info;
-      s.term[le] = term ? 1 : 0;
-      s.sc[le] = term ? 0 : sc_new;
-      reset = term;
+      const EpisodeEnd end = episode_commit(bk, e, run, sc_old, rew, terminated, a.time_limit);
+      s.term[le] = end.term ? 1 : 0;
+      s.sc[le] = end.step_count;
+      reset = end.term;
       build_req(a, s, le, false);
     } else {
-      a.run_return[e] = 0.0f;
-      a.run_length[e] = 0;
-      a.ep_return[e] = 0.0f;
-      a.ep_length[e] = 0;
+      episode_clear(bk, e);
       s.term[le] = 0;
       s.rew[le] = 0.0f;
     }

@@ -18,7 +18,7 @@
 //   reward_mode 1 ("match", opt-in, for learning tests): team reward = fraction of the env's agents whose action equals
 //   (first grid coordinate of the observation they acted on) mod n_actions - the only action-dependent quantity
 // Restated bit-for-bit in oracle/synth_env.py.
-#include "common.h"
+#include "env_common.h"
 
 namespace {
 
@@ -165,25 +165,9 @@ __global__ __launch_bounds__(256) void synth_rware_kernel(SynthArgs a) {
   }
   // ---- per-env state and episode metrics (agent 0's thread)
   if (ag == 0) {
-    if (a.is_reset) {
-      a.run_return[e] = 0.0f;
-      a.run_length[e] = 0;
-      a.ep_return[e] = 0.0f;
-      a.ep_length[e] = 0;
-    } else {
-      // episode_metrics.py:88-111 (mean over agents of a repeated team reward == the reward)
-      const float new_ret = a.run_return[e] + rew;
-      const int new_len = a.run_length[e] + 1;
-      const float ret_info = term ? new_ret : a.ep_return[e];
-      const int len_info = term ? new_len : a.ep_length[e];
-      a.info_return[e] = ret_info;
-      a.info_length[e] = len_info;
-      a.info_terminal[e] = term ? 1 : 0;
-      a.run_return[e] = term ? 0.0f : new_ret;
-      a.run_length[e] = term ? 0 : new_len;
-      a.ep_return[e] = ret_info;
-      a.ep_length[e] = len_info;
-    }
+    // (the mean over agents of a repeated team reward == the reward; `term` already holds the time limit)
+    if (a.is_reset) episode_clear(episode_book(a), e);
+    else episode_step(episode_book(a), e, sc_old, rew, term, a.time_limit);
   }
 }
 
