@@ -398,6 +398,65 @@ int mava_cleaner_step_real_next(int E, int A, int R, int C, int time_limit, uint
                                 int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
                                 float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
+/* ---- SMAX environment step (mava_amd/csrc/smax.hip; rules in DESIGN.md "SMAX", stated in tests/smax_model.py, which is
+ *      the contract; parity with JaxMARL's SMAX is unpinned).  E environments of A allies (the agents, 1 <= A <= 16)
+ *      against Ne scripted enemies (1 <= Ne <= 16) on a 32 x 32 map; U = A + Ne units, allies first.  ally_types /
+ *      enemy_types hold one nibble per unit: 0 marine, 1 marauder, 2 stalker, 3 zealot, 4 zergling, 5 hydralisk, with
+ *      (health, damage, attack range, sight range, speed, weapon cooldown in sub-steps) = (45, 9, 5, 9, 3.15, 10),
+ *      (125, 10, 6, 10, 2.25, 18), (160, 13, 6, 10, 4.13, 30), (150, 8, 2, 9, 3.15, 14), (35, 5, 2, 8, 4.13, 8),
+ *      (80, 12, 5, 9, 3.15, 10).  Actions (E, A) int32, 5 + Ne of them: 0 N (y+), 1 E (x+), 2 S (y-), 3 W (x-), 4 stop,
+ *      5 + k attack enemy k.  State (struct of arrays, advanced in place): pos (E, U, 2) f32 (x, y), health (E, U) f32
+ *      (integer values), cd (E, U) i32, last_action (E, U) i32, step_count (E, A) and the RecordEpisodeMetrics words, as
+ *      mava_lbf_step.  All float arithmetic is f32, one rounded operation at a time; distances are compared squared.
+ *      Reset: unit j uses draws 2j and 2j + 1 ("draw n" = word n % 4 of Philox block n / 4), u = (word >> 8) 2^-24;
+ *      allies start at (6 + 4u, 14 + 4u'), enemies at (22 + 4u, 14 + 4u'), health full, cd 0, last_action 4.
+ *      One step: (1) a dead ally's action becomes 4; a value that is no action, or an attack on a dead enemy or on one
+ *      farther than the ally's range, is executed as 4.  (2) A living enemy takes the closest living ally within its
+ *      sight (ties to the lowest index): within its range it attacks it (5 + ally), otherwise it moves along the axis
+ *      with the larger |delta| (ties to x) towards it; with no ally in sight it moves the same way towards (16, 16) and
+ *      stops once both |delta| < 0.5.  Both from the state at the start of the step.  (3) Eight sub-steps of 1/16 time
+ *      units: MOVE - a living unit with action 0..3 adds speed / 16 to one coordinate; with walls_cause_death a mover
+ *      whose new coordinate leaves [0, 32] dies; positions are clipped to [0, 32]; FIRE - unit u fires at its target v
+ *      iff both are alive after the move, d2(u, v) <= range_u^2 and cd_u = 0; DAMAGE - health = max(0, health - the sum
+ *      of the damage of the units firing at it), for all targets at once; COOLDOWN - a unit that fired sets cd to its
+ *      type's value, every other unit alive after the move counts cd down to 0.  (4) Team reward, repeated per agent:
+ *      (sum over enemies k, ascending, of fl(lost health_k / max health_k)) / Ne, plus 1 iff every enemy is dead and an
+ *      ally lives.  (5) step_count += 1; terminated = a side is wiped out; done = terminated | step_count >=
+ *      time_limit; info_won = done & (every enemy dead & an ally alive).  (6) last_action = the action executed.
+ *      Outputs, on the new state: agents_view (E, A, A + 11 (U - 1) + 10) = the one-hot agent id, then for a living
+ *      viewer i one block per other ally (ascending) and per enemy, [health / max, dx / sight_i, dy / sight_i,
+ *      (last_action + 1) / (5 + max(A, Ne)), cd / type cd, type one-hot (6)] with (dx, dy) = other - viewer, all zero
+ *      if the other is dead or farther than sight_i, the last_action entry zero for enemies unless see_enemy_actions;
+ *      then the own block [health / max, x / 32, y / 32, cd / type cd, type one-hot (6)]; a dead viewer has zeros after
+ *      the id.  global_state (E, 1, 12 U): per unit the own block and a team one-hot (ally, enemy), zero for the dead.
+ *      action_mask (E, A, 5 + Ne) u8: a dead ally only 4; a living one 0..4 and 5 + k iff enemy k is alive and in
+ *      range.  obs_step_count, reward, done (E, A); info_* (E); info_won (E) u8 may be NULL.
+ *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL, info_won is not written); a
+ *      terminal step regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`,
+ *      counter (env_offset + e, t + *t_base, block, "SMAX"); t_base (a device word, may be NULL) is added on the device,
+ *      so the step replays from a captured graph.  No host state, no synchronisation. */
+int mava_smax_step(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit, int see_enemy_actions,
+                   int walls_cause_death, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset,
+                   int is_reset, float* pos, float* health, int32_t* cd, int32_t* last_action, int32_t* step_count,
+                   float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                   float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                   float* info_return, int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won,
+                   const int32_t* action, mava_stream_t s);
+
+/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
+ * (E, A, obs_dim) / real_mask (E, A, 5 + Ne) observe the state the rules produced BEFORE any auto-reset, and terminated
+ * (E) says that a side was wiped out - a time-limit end alone is a truncation.  None of the three is written on a reset
+ * call (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
+int mava_smax_step_real_next(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit,
+                             int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t,
+                             const uint32_t* t_base, uint32_t env_offset, int is_reset, float* pos, float* health,
+                             int32_t* cd, int32_t* last_action, int32_t* step_count, float* run_return,
+                             int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                             float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward,
+                             uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
+                             uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
+                             uint8_t* terminated, mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments

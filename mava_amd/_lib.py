@@ -69,6 +69,8 @@ _SIGNATURES = {
     "mava_connector_step_real_next": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 22 + [vp],
     "mava_cleaner_step": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 18 + [vp],
     "mava_cleaner_step_real_next": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
+    "mava_smax_step": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 20 + [vp],
+    "mava_smax_step_real_next": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
     "mava_rec_q_step_f32": [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, u64, u32, u32, vp, vp, vp],
     "mava_replay_add_f32": [i32] * 6 + [vp] * 16 + [vp],
     "mava_replay_sample_f32": [i32] * 5 + [u32, i32, i32, i32, u64, u32] + [vp] * 17 + [vp],

@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "rware.hip",
     "connector.hip",
     "cleaner.hip",
+    "smax.hip",
     "q_learning.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",

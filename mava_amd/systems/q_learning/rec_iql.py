@@ -4,7 +4,7 @@
 train for the updates of one evaluation interval, log MISC {timestep, epsilon}, ACT episode metrics when an episode
 completed, TRAIN losses (skipped while the buffer is below the train gate), EVAL with the greedy (eps = 0) policy,
 checkpoint, and finally ABSOLUTE with the best parameters.  Runs on env=lbf (the default here; the reference's default is
-smax, which has no learnable counterpart in this project) and env=rware_native; environments without a pre-reset
+smax, here env=smax_native), env=rware_native, env=connector and env=cleaner; environments without a pre-reset
 observation (the synthetic stand-ins) are refused.
 
     python -m mava_amd.systems.q_learning.rec_iql env/scenario=10x10-3p-3f system.total_timesteps=200000
@@ -43,10 +43,10 @@ def _check_config(config: Config) -> None:
     qn = config.network.get("q_network", None)
     if qn is None or not (_learner._default_torso(qn.get("pre_torso")) and _learner._default_torso(qn.get("post_torso"))):
         raise NotImplementedError("rec_iql runs network/rnn.yaml's q_network torsos only (MLPTorso [128] relu)")
-    native_rware = config.env.get("env_name", None) == "RobotWarehouse" and bool(config.env.get("native", False))
-    if config.env.get("env_name", None) not in ("LevelBasedForaging", "MaConnector", "Cleaner") and not native_rware:
+    native = config.env.get("env_name", None) in ("RobotWarehouse", "Smax") and bool(config.env.get("native", False))
+    if config.env.get("env_name", None) not in ("LevelBasedForaging", "MaConnector", "Cleaner") and not native:
         raise ValueError(f"rec_iql needs an environment that returns its pre-reset observation (env=lbf, "
-                         f"env=rware_native, env=connector, env=cleaner); "
+                         f"env=rware_native, env=connector, env=cleaner, env=smax_native); "
                          f"{config.env.get('env_name', None)} runs on the synthetic stand-in, which does not")
 
 
