@@ -388,6 +388,7 @@ static int rec_step_impl(const float* actor_params, int actor_din, int n_actions
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 163840));                   \
       attr_set = true;                                                                                           \
     }                                                                                                            \
+    g_rec_step_last_instance = rec_step_instance_id(1, NOA, ta + tc > 256 ? 1 : 0);                              \
     hipLaunchKernelGGL(rec_step_kernel<NOA>, dim3(nba + nbc), dim3(256), lb, s, a, c, nba, so);                  \
   } while (0)
   if (noa == 8) LAUNCH(8);
@@ -397,6 +398,11 @@ static int rec_step_impl(const float* actor_params, int actor_din, int n_actions
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }
+
+// Diagnostic (not part of include/mava_hip.h, like mava_debug_rollout_last_instance): which acting-step kernel instance the
+// last launch of this process used (rec_step_task.h), so that a parity test can tell the f16x2 kernel from its f32 fallback.
+int g_rec_step_last_instance = 0;
+extern "C" int mava_debug_rec_step_last_instance(void) { return g_rec_step_last_instance; }
 
 extern "C" int mava_rec_step_f32(const float* actor_params, int actor_din, int n_actions, const float* agents_view,
                                  const uint8_t* action_mask, const uint8_t* done_a, const float* h_actor_in,

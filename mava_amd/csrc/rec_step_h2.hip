@@ -558,6 +558,7 @@ int launch_step(const NetH2& a, const NetH2& c, int ga, int gc, const RecStepOut
     MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)rec_step_h2_kernel<NOA, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
     attr_set = true;
   }
+  g_rec_step_last_instance = rec_step_instance_id(2, NOA, RT);
   hipLaunchKernelGGL((rec_step_h2_kernel<NOA, RT>), dim3(ga + gc), dim3(256), lb, s, a, c, ga, so);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;

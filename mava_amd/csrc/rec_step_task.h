@@ -27,6 +27,12 @@ struct RecStepOut {
   float min_scale;       // continuous head: scale = softplus(log_std) + min_scale
 };
 
+// Diagnostic (rec_step.hip: mava_debug_rec_step_last_instance): the kernel instance the last acting-step launch of this
+// process used, FAMILY * 1000 + NOA * 10 + K.  FAMILY 1 = rec_step_kernel<NOA> (exact f32; K = 1 when the CUs are shared out
+// between the two networks, more than 256 tiles, else 0), FAMILY 2 = rec_step_h2_kernel<NOA, RT> (K = RT).  Written on the
+// host at dispatch; a refused launch leaves it unchanged.
+extern int g_rec_step_last_instance;
+inline int rec_step_instance_id(int family, int noa, int k) { return family * 1000 + noa * 10 + k; }
 
 // rec_step_h2.hip.  Returns MAVA_OK, 1 when the shape is not instantiated (the caller runs the f32 kernel), or an error.
 int mava_rec_step_h2_launch(const RecNet& actor, const RecNet& critic, const void* pack_a, const void* pack_c,
