@@ -457,6 +457,47 @@ int mava_smax_step_real_next(int E, int A, int Ne, uint64_t ally_types, uint64_t
                              uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
                              uint8_t* terminated, mava_stream_t s);
 
+/* ---- Spread environment step (mava_amd/csrc/spread.hip; rules in DESIGN.md "Spread", stated in tests/spread_model.py,
+ *      which is the contract).  This project's own continuous-action task, modelled on MPE simple_spread; it restates no
+ *      environment of the reference.  E environments of A agents and A landmarks (2 <= A <= 8) in [-1, 1]^2.  Actions
+ *      (E, A, 2) f32.  State (struct of arrays, advanced in place): agent_pos, landmark_pos (E, A, 2) f32 (x, y),
+ *      step_count (E, A) and the RecordEpisodeMetrics words, as mava_lbf_step.  All float arithmetic is f32, one rounded
+ *      operation at a time.  Reset: agent i uses draws 2i, 2i + 1 and landmark l draws 2A + 2l, 2A + 2l + 1 ("draw n" =
+ *      word n % 4 of Philox block n / 4); a coordinate is 2u - 1 with u = (word >> 8) 2^-24.
+ *      One step: (1) c = fmin(fmax(a, -1), 1) per component, p = fmin(fmax(p + fl(0.1 c), -1), 1); there are no
+ *      velocities.  (2) Team reward, repeated per agent: with d(p, q) = sqrt(fl(fl(dx dx) + fl(dy dy))), near_l = min
+ *      over agents of d(agent, landmark l), n = the number of agent pairs u < v with d < 0.15:
+ *      -fl((sum over l, ascending, of near_l) / A) - fl(fl(0.5 n) / A), the divisions being products with fl(1 / A).
+ *      (3) step_count += 1; terminated = 0 (the rules never end an episode); done = step_count >= time_limit.
+ *      Outputs, on the new state: agents_view (E, A, [A +] 2 + 2A + 2(A - 1)) = the one-hot agent id (only with
+ *      add_agent_id), the own position, the landmarks minus self (ascending), the other agents minus self (ascending,
+ *      skipping self).  global_state (E, 1, 4A): the agent positions, then the landmark positions.  action_mask
+ *      (E, A, 2) u8: all ones.  obs_step_count, reward, done (E, A); info_* (E).
+ *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a step that reaches the time
+ *      limit regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`, counter
+ *      (env_offset + e, t + *t_base, block, "SPRD"); t_base (a device word, may be NULL) is added on the device, so the
+ *      step replays from a captured graph.  No host state, no synchronisation. */
+int mava_spread_step(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                     uint32_t env_offset, int is_reset, float* agent_pos, float* landmark_pos, int32_t* step_count,
+                     float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                     float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                     float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
+                     mava_stream_t s);
+
+/* The same step plus the pre-reset observation for an off-policy replay, as mava_lbf_step_real_next: real_view
+ * (E, A, obs_dim) / real_mask (E, A, 2) observe the state the rules produced BEFORE any auto-reset; terminated (E) is
+ * always 0 - a time-limit end is a truncation; real_state (E, 1, 4A), which may be NULL, is the pre-reset global_state
+ * (ff_masac's next state).  None of them is written on a reset call (they may then be NULL); otherwise they must not
+ * alias agents_view / action_mask / global_state. */
+int mava_spread_step_real_next(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t,
+                               const uint32_t* t_base, uint32_t env_offset, int is_reset, float* agent_pos,
+                               float* landmark_pos, int32_t* step_count, float* run_return, int32_t* run_length,
+                               float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                               uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                               float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
+                               float* real_view, uint8_t* real_mask, uint8_t* terminated, float* real_state,
+                               mava_stream_t s);
+
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
  *      launch (mava_amd/csrc/rollout_h2.hip): every workgroup owns 64 / A environments for all T steps (environments
@@ -665,6 +706,71 @@ int mava_q_td_loss_f32(int L, int Rp, int n_actions, int n_real, const float* q,
 /* Target network update (:411-418): hard = 0: target = tau * online + (1 - tau) * target (optax.incremental_update);
  * hard = 1: target = online (optax.periodic_update on a step where it fires; the caller decides when). */
 int mava_target_update_f32(long n, const float* online, float* target, float tau, int hard, mava_stream_t s);
+
+/* ---- soft actor-critic (ff_isac / ff_masac): mava/systems/sac/ff_isac.py:245-384, ff_masac.py,
+ *      mava/utils/centralised_training.py (mava_amd/csrc/sac.hip).  The actor (ContinuousActionHead with
+ *      independent_std = False) and the two Q networks (torso -> Dense(1) on [state | action]) run on the general layer
+ *      path; these kernels produce and consume its T32 matrices.  Buffer fields, sampled batches, actions and noise are
+ *      row-major; the rows of a batch are b * A + agent, `rows` is a multiple of 32 and the rows from n_real on are padding:
+ *      every kernel writes zeros there.  A (rows x 1) T32 matrix (a Q value) is a plain vector.
+ *
+ * Item replay, fbx.make_item_buffer(add_batches=True) (ff_isac.py:171-176, :257-258): a ring of `capacity` items, an item
+ * being one env's transition for all agents: obs (A, O), action (A, D), reward (A), done (A) u8, next_obs (A, O) and, with
+ * S > 0 (MASAC), global_state and next_global_state (S), stored once per item.  Add writes the E items of one acting step to
+ * slots (head + e) mod capacity (E <= capacity); its `done` is one flag per env (E), stored for every agent. */
+int mava_sac_replay_add_f32(int E, int A, int O, int D, int S, int capacity, int head, const float* obs, const float* action,
+                            const float* reward, const uint8_t* done, const float* next_obs, const float* gs,
+                            const float* next_gs, float* b_obs, float* b_action, float* b_reward, uint8_t* b_done,
+                            float* b_next_obs, float* b_gs, float* b_next_gs, mava_stream_t s);
+/* Sample B items with replacement (:395): item b draws word 0 of the Philox block with key `seed` and counter
+ * (b, counter, 0, "SACB"); k = floor(word * filled / 2^32) with filled = min(n_added, capacity) (n_added: items added so
+ * far); the item is slot (n_added - filled + k) mod capacity (k counts from the oldest).  Gathers to rows b * A + agent of
+ * obs / next_obs (Rp, O), action (Rp, D), reward / done (Rp) (padding: zeros, done 1), gs / next_gs (B, S), and writes
+ * the chosen slots to index (B). */
+int mava_sac_replay_sample_f32(int A, int O, int D, int S, int capacity, uint32_t n_added, int B, int Rp, uint64_t seed,
+                               uint32_t counter, const float* b_obs, const float* b_action, const float* b_reward,
+                               const uint8_t* b_done, const float* b_next_obs, const float* b_gs, const float* b_next_gs,
+                               float* obs, float* action, float* reward, uint8_t* done, float* next_obs, float* gs,
+                               float* next_gs, int32_t* index, mava_stream_t s);
+/* Reparameterised sample (pi.sample + pi.log_prob of :291-293, :310-312, :369-371, :425-426): mean / log_std T32
+ * (rows x action_dim), scale = softplus(log_std) + min_scale, eps = the standard normal of (row_offset + row, step,
+ * component) in the stream "SACN" of key `seed`, action = tanh(mean + scale eps), log_prob = the sum over components of
+ * TanhTransformedDistribution.log_prob(action) (clip to +-0.999, tail masses beyond it).  action / eps (rows, action_dim),
+ * log_prob (rows); log_prob and eps may be NULL.  1 <= action_dim <= 16. */
+int mava_sac_sample_f32(int rows, int n_real, int action_dim, float min_scale, const float* mean, const float* log_std,
+                        uint64_t seed, uint32_t step, uint32_t row_offset, float* action, float* log_prob, float* eps,
+                        mava_stream_t s);
+/* The Q-network input [state | action block] as a T32 matrix of x_ld >= O + W features per tile (zeros past O + W, as
+ * mava_rec_gather_t32_f32's k_pad); row r reads state row r / x_share of the
+ * row-major (., O) array (x_share = A for a global state stored once per item).  joint 0 (ISAC): W = action_dim, the row's
+ * own action - action_new when given, else action.  joint 1 (MASAC): W = A action_dim, the actions of all agents of the
+ * row's item from `action` (get_joint_action); with action_new the row's OWN slot comes from action_new
+ * (get_updated_joint_actions).  action / action_new (rows, action_dim). */
+int mava_sac_concat_f32(int rows, int n_real, int O, int x_share, int A, int action_dim, int joint, const float* state,
+                        const float* action, const float* action_new, float* x, int x_ld, mava_stream_t s);
+/* update_q (:305-340): target = reward + (1 - done) gamma (min(q1_target, q2_target) - exp(log_alpha[agent])
+ * log_prob_next), agent = row % A; dq1 = 2 (q1 - target) / n_real * grad_scale, dq2 likewise; target (rows, may be NULL);
+ * partials (nblk, 4): per-block sums of [q1_loss, q2_loss, mean q1, mean q2] (their sum over blocks is the value). */
+int mava_sac_q_loss_f32(int rows, int n_real, int A, const float* q1, const float* q2, const float* q1_target,
+                        const float* q2_target, const float* log_prob_next, const float* reward, const uint8_t* done,
+                        const float* log_alpha, float gamma, float grad_scale, float* dq1, float* dq2, float* target,
+                        float* partials, int nblk, mava_stream_t s);
+/* actor_loss_fn (:284-299) differentiated through the sample: L = mean(exp(log_alpha) logp - min(q1, q2)).  Inputs: the
+ * sample (mean, log_std T32; eps, action row-major), q1 / q2, and dx1 / dx2: T32 (rows x K) gradients of sum(q1) / sum(q2)
+ * w.r.t. the Q input in units of q_scale, whose features [action_offset (+ agent * action_dim when joint), + action_dim)
+ * are the row's own action.  Unclipped components: d logp / d mean = 2 a, d logp / d scale = -1 / scale + 2 a eps; clipped
+ * ones (|a| >= 0.999): the tail mass's derivatives alone.  The Q path carries (1 - a^2) and goes to the smaller of q1, q2.
+ * Writes dmean / dlog_std T32 (rows x action_dim) times grad_scale (dlog_std w.r.t. the raw log_std: times sigmoid) and
+ * partials (nblk, 2): per-block sums of [actor loss, mean log_prob]. */
+int mava_sac_actor_grad_f32(int rows, int n_real, int A, int action_dim, float min_scale, const float* mean,
+                            const float* log_std, const float* eps, const float* action, const float* log_alpha,
+                            const float* q1, const float* q2, const float* dx1, const float* dx2, int K, int action_offset,
+                            int joint, float q_scale, float grad_scale, float* dmean, float* dlog_std, float* partials,
+                            int nblk, mava_stream_t s);
+/* alpha_loss_fn (:301-302): loss = mean over (B, A) of -exp(log_alpha[a]) (log_prob + target_entropy).  grad (A) =
+ * d loss / d log_alpha; loss_parts (A): each agent's share (their sum is the loss). */
+int mava_sac_alpha_loss_f32(int n_real, int A, const float* log_prob, const float* log_alpha, float target_entropy,
+                            float* grad, float* loss_parts, mava_stream_t s);
 
 /* T32 <-> row-major conversion of a (rows x N) matrix. */
 int mava_t32_convert_f32(const float* src, int N, int rows, int to_t32, float* dst, mava_stream_t s);

@@ -71,11 +71,20 @@ _SIGNATURES = {
     "mava_cleaner_step_real_next": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
     "mava_smax_step": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 20 + [vp],
     "mava_smax_step_real_next": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
+    "mava_spread_step": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 17 + [vp],
+    "mava_spread_step_real_next": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
     "mava_rec_q_step_f32": [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, u64, u32, u32, vp, vp, vp],
     "mava_replay_add_f32": [i32] * 6 + [vp] * 16 + [vp],
     "mava_replay_sample_f32": [i32] * 5 + [u32, i32, i32, i32, u64, u32] + [vp] * 17 + [vp],
     "mava_q_td_loss_f32": [i32, i32, i32, i32] + [vp] * 7 + [f32, f32, vp, vp, i32, vp],
     "mava_target_update_f32": [lng, vp, vp, f32, i32, vp],
+    "mava_sac_replay_add_f32": [i32] * 7 + [vp] * 14 + [vp],
+    "mava_sac_replay_sample_f32": [i32] * 5 + [u32, i32, i32, u64, u32] + [vp] * 15 + [vp],
+    "mava_sac_sample_f32": [i32, i32, i32, f32, vp, vp, u64, u32, u32, vp, vp, vp, vp],
+    "mava_sac_concat_f32": [i32] * 7 + [vp] * 4 + [i32, vp],
+    "mava_sac_q_loss_f32": [i32] * 3 + [vp] * 8 + [f32, f32] + [vp] * 4 + [i32, vp],
+    "mava_sac_actor_grad_f32": [i32] * 4 + [f32] + [vp] * 9 + [i32, i32, i32, f32, f32] + [vp] * 3 + [i32, vp],
+    "mava_sac_alpha_loss_f32": [i32, i32, vp, vp, f32, vp, vp, vp],
     "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18 + [vp, vp, f32, f32, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],

@@ -32,7 +32,9 @@ HIP_SOURCES = [
     "connector.hip",
     "cleaner.hip",
     "smax.hip",
+    "spread.hip",
     "q_learning.hip",
+    "sac.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",
     "rec_gru.hip",

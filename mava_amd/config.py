@@ -73,8 +73,8 @@ def compose(config_name: str = "default_ff_mappo", overrides: Optional[Iterable[
         k = k.lstrip("+")
         if k in ("env/scenario", "env.scenario") and "." not in v and v in groups["scenario"]:
             scenario = v
-        elif k in choice and k in groups and any(c in groups[k] for c in (v, f"ppo/{v}", f"q_learning/{v}")):
-            choice[k] = next(c for c in (v, f"ppo/{v}", f"q_learning/{v}") if c in groups[k])
+        elif k in choice and k in groups and any(c in groups[k] for c in (v, f"ppo/{v}", f"q_learning/{v}", f"sac/{v}")):
+            choice[k] = next(c for c in (v, f"ppo/{v}", f"q_learning/{v}", f"sac/{v}") if c in groups[k])
         else:
             dotted.append(ov.lstrip("+"))
     cfg = Config()

@@ -7,7 +7,7 @@ use - writes straight into trajectory slots owned by the learner.  The step kern
 
     E, A, *scenario, seed, t, t_base, env_offset, is_reset, *own state, step_count, run_return, run_length, ep_return,
     ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done, info_return, info_length,
-    info_terminal, [info_won,] action, [*step_tail_args,] [real_view, real_mask, terminated,] stream
+    info_terminal, [info_won,] action, [*step_tail_args,] [real_view, real_mask, terminated, [*real_extra_keys,]] stream
 
 so `BatchedEnv.step_into` assembles it once.  A subclass states `State`, `action_dim`, `step_symbols`, `obs_dim`,
 `state_dim`, `alloc_own_state` and `step_args`, validates its scenario in `__init__` and reads it from the config in its
@@ -50,6 +50,7 @@ class BatchedEnv:
     implicit_agent_id = False  # True: no one-hot id in agents_view (system.add_agent_id is ignored)
     reports_win = False  # True: the symbols take info_won after info_terminal, reset / step add extras["won_episode"]
     step_tail_args: tuple = ()  # arguments of the plain symbol after `action`
+    real_extra_keys: tuple = ()  # keys of real_obs whose pointers follow `terminated` in the _real_next symbol (None if absent)
     State: type  # the state tuple: COMMON_STATE, then the fields of alloc_own_state in its order
     action_dim: int
     step_symbols: Tuple[str, Optional[str]]  # (mava_X_step, mava_X_step_real_next)
@@ -125,7 +126,8 @@ class BatchedEnv:
         if info_won is not None and not self.reports_win:
             raise ValueError(f"{type(self).__name__}.step_into: this environment reports no win")
         off = self.env_offset if env_offset is None else env_offset
-        real = () if real_obs is None else (ptr(real_obs["agents_view"]), ptr(real_obs["action_mask"]), ptr(terminated))
+        real = () if real_obs is None else (ptr(real_obs["agents_view"]), ptr(real_obs["action_mask"]), ptr(terminated),
+                                            *(ptr(real_obs.get(k, None)) for k in self.real_extra_keys))
         won = (ptr(info_won),) if self.reports_win else ()
         scenario, own = self.step_args(state)
         self._call(self.step_symbols[1 if real else 0], (

@@ -230,16 +230,17 @@ class GenericNet:
         return GenericWorkspace(self, rows, device, training)
 
     def forward(self, flat: torch.Tensor, ws: "GenericWorkspace", x_ext: Optional[torch.Tensor], x_share: int, idx, Rm: int, E: int,
-                A: int, T: int = 1, x_t32: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+                A: int, T: int = 1, x_t32: Optional[torch.Tensor] = None, x_t32_ld: Optional[int] = None) -> List[torch.Tensor]:
         """x_ext: external row-major (T, E, A / x_share, din) source, gathered like mava_rec_dense_f32's row-major input
         (batch row q = t*Rm + m, m = local_env*A + agent, env = idx[local_env] or identity); or x_t32: the input already as a
-        T32 matrix of din features (the recurrent post torso reads the hidden states).  Returns the heads' T32 outputs, or
+        T32 matrix of din features per tile, or x_t32_ld >= din of them (the recurrent post torso reads the hidden states, the SAC
+        Q networks their [state | action] rows).  Returns the heads' T32 outputs, or
         [features] for a torso without heads."""
         L, s = lib(), stream_ptr()
         rows = T * Rm
         assert rows == ws.rows
         if x_t32 is not None:
-            ws.x_src, ws.x_src_ld = x_t32, self.din
+            ws.x_src, ws.x_src_ld = x_t32, int(x_t32_ld or self.din)
         else:
             check(L.mava_rec_gather_t32_f32(ptr(x_ext), ptr(idx), Rm, E, A, x_share, self.din, self.din, rows, ws.kp, ptr(ws.xin), s),
                   "gather")

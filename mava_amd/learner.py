@@ -104,6 +104,9 @@ class FFLearner:
         action_head = make_action_head(config.network.get("action_head", None), env.action_dim)
         self.continuous = type(action_head).__name__ == "ContinuousActionHead"
         self.min_scale = float(getattr(action_head, "min_scale", 1e-3))
+        # a discrete env reads the action index; of the continuous ones only an env with `continuous_actions` reads the
+        # f32 action vector (the synthetic stand-in ignores it)
+        self._env_reads_action = not self.continuous or getattr(env, "continuous_actions", False)
         for u in range(self.U):
             rep_env = env.clone(env_offset=getattr(env, "env_offset", 0) + (self.rank * self.U + u) * self.E)
             self.reps.append(_Replica(rep_env, self.T, self.n_upd, centralised_critic, self.device, self.continuous))
@@ -417,7 +420,7 @@ class FFLearner:
                 last = t == self.T - 1
                 self._timed("env_step", rep.env.step_into, rep.state, step + 1, rep.obs_slot(t + 1), rep.reward[t], rep.done[t],
                             rep.cur_return[t], rep.cur_length[t], rep.cur_terminal[t], t_base=self.step_dev,
-                            action=None if self.continuous else rep.action[t])
+                            action=rep.action[t] if self._env_reads_action else None)
                 if last:
                     rep.last_reward.copy_(rep.reward[t])
                     rep.last_done.copy_(rep.done[t])

@@ -96,6 +96,8 @@ class RecLearner:
         action_head = make_action_head(config.network.get("action_head", None), env.action_dim)
         self.continuous = type(action_head).__name__ == "ContinuousActionHead"
         self.min_scale = float(getattr(action_head, "min_scale", 1e-3))
+        # of the continuous envs only one with `continuous_actions` reads the f32 action vector (FFLearner.__init__)
+        self._env_reads_action = not self.continuous or getattr(env, "continuous_actions", False)
         # ContinuousActionHead(independent_std=False): the log_std layer is a second head of the actor's post-torso, which then
         # runs on the general layer kernels (mava_amd/generic_networks.py) whatever its torsos are
         self.dep_std = self.continuous and not getattr(action_head, "independent_std", True)
@@ -301,7 +303,7 @@ class RecLearner:
                     rep.h_actor, rep.h_actor_next = rep.h_actor_next, rep.h_actor
                     rep.h_critic, rep.h_critic_next = rep.h_critic_next, rep.h_critic
                     rep.env.step_into(rep.state, step + 1, rep.obs_slot(t + 1), rep.reward[t], rep.done[t], rep.info_return[n, t],
-                                      rep.info_length[n, t], rep.info_terminal[n, t], action=None if self.continuous else rep.action[t])
+                                      rep.info_length[n, t], rep.info_terminal[n, t], action=rep.action[t] if self._env_reads_action else None)
                     continue
                 rep.done_in[t].copy_(rep.dones)
                 d1 = rep.done_in[t : t + 1]
@@ -341,7 +343,7 @@ class RecLearner:
                     n_c = E if self.critic_agg else EA
                     rep.h_critic[: n_c * self.Hd].copy_(self.critic_network.last_hidden(ws, 1, n_c))
                 rep.env.step_into(rep.state, step + 1, rep.obs_slot(t + 1), rep.reward[t], rep.done[t], rep.info_return[n, t],
-                                  rep.info_length[n, t], rep.info_terminal[n, t], action=None if self.continuous else rep.action[t])
+                                  rep.info_length[n, t], rep.info_terminal[n, t], action=rep.action[t] if self._env_reads_action else None)
                 rep.dones.copy_(rep.done[t])
                 if t == self.T - 1:
                     rep.last_reward.copy_(rep.reward[t])

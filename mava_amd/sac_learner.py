@@ -1,0 +1,440 @@
+"""Soft actor-critic (ff_isac / ff_masac) behind Mava's learner contract.
+
+Reference: mava/systems/sac/ff_isac.py:58-208 (init), :211-488 (make_update_fns) and ff_masac.py, which differs in the Q
+input alone: [global_state | joint action] instead of [agents_view | own action] (mava/utils/centralised_training.py).
+One update step = `rollout_length` acting steps that store Transitions in a device item buffer (:245-260, :418-429), then
+`epochs` train steps (:387-416): sample a batch, update_q (:305-340), and - when the env-step counter `t` entering the
+update step is a multiple of policy_update_delay, a test that does not change inside the epochs (:399-400, :459-462) -
+update_actor_and_alpha (:342-384), which repeats its update policy_update_delay times with the same noise (:348-349).
+
+The networks run on the general layer path (mava_amd/generic_networks.py): GenericActor with ContinuousActionHead(
+independent_std=False) (:113-116) and GenericNet with a Dense(1) head for Q (mava/networks.py:210-235).  Kernels per act
+step: the actor's layer products, mava_sac_sample_f32, the env's _real_next symbol, mava_sac_replay_add_f32.  Per train
+step: mava_sac_replay_sample_f32; the actor on next_obs, mava_sac_sample_f32, mava_sac_concat_f32 and the two target Q
+passes; mava_sac_concat_f32, the two online Q passes, mava_sac_q_loss_f32, two backward chains, mava_clip_adam over
+[q1 | q2] and mava_target_update_f32; and per actor update the actor pass, mava_sac_sample_f32, mava_sac_concat_f32, two Q
+passes forward and backward for dQ/da (their parameter gradients go to scratch), mava_sac_actor_grad_f32, the actor's
+backward chain, mava_clip_adam, then (autotune) the actor pass again, mava_sac_sample_f32, mava_sac_alpha_loss_f32 and
+mava_clip_adam on log_alpha.  The policy-delay test, the buffer head and the noise counters are host arithmetic on step
+counts: nothing synchronises the host per step or per epoch.
+
+`done` of a stored transition is the env's `terminated` flag (a time-limit end is a truncation and keeps the bootstrap),
+which is what the reference's `~discount` is under Jumanji's truncation.
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Any, Dict, List, Optional
+
+import torch
+
+from . import ops, parallel
+from ._lib import launch, lib, ptr, stream_ptr
+from .generic_networks import CNNTorso, GenericActor, GenericNet, torso_from_config
+from .guards import check_f16_range
+from .networks import make_action_head
+from .systems.sac.types import LearnerState, OptStates, QVals, QValsAndTarget, SacParams, Transition
+from .types import AdamState, ExperimentOutput, Observation, ObservationGlobalState
+
+ADAM_EPS = 1e-8  # optax.adam's default (ff_isac.py:146-152), not PPO's 1e-5
+TRAIN_KEY_TAG = 0x545241494E  # "TRAIN": xor-ed into the key of the train steps' noise, apart from the acting noise
+LOSS_BLOCKS = 8
+
+
+def _pad32(n: int) -> int:
+    return -(-n // 32) * 32
+
+
+class QNetwork:
+    """mava/networks.py:210-235 FeedForwardQNet over GenericNet: torso([state | action]) -> Dense(1, orthogonal(1.0))."""
+
+    def __init__(self, torso, input_dim: int, centralised_critic: bool = False):
+        self.centralised_critic = centralised_critic
+        self.net = GenericNet(torso, input_dim, [("critic", 1, 1.0)])
+        self.din, self.ld = int(input_dim), _pad32(int(input_dim))
+
+    @property
+    def num_params(self) -> int:
+        return self.net.num_params
+
+    def init_flat(self, seed: int, device=None) -> torch.Tensor:
+        return self.net.init_flat(seed, device)
+
+    def tree(self, flat: torch.Tensor, lead=()) -> Dict[str, Any]:
+        return {"params": {"torso": self.net.torso_tree(flat, lead), "critic": self.net.head_leaf(flat, 0, lead)}}
+
+    def flat_from_tree(self, tree: Dict[str, Any], out: torch.Tensor) -> torch.Tensor:
+        self.net.load_torso_tree(tree["params"]["torso"], out)
+        self.net.load_head_leaf(tree["params"]["critic"], 0, out)
+        return out
+
+
+class SACLearner:
+    def __init__(self, env, config, centralised: bool, device: Optional[torch.device] = None):
+        self.config, self.centralised = config, bool(centralised)
+        name = "ff_masac" if centralised else "ff_isac"
+        s, arch, net = config.system, config.arch, config.network
+        self.device = d = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.rank, self.world = parallel.rank_world()
+        if self.world > 1:
+            raise NotImplementedError(f"{name} runs on one device (multi-GPU is not implemented)")
+        if int(s.update_batch_size) != 1:
+            raise NotImplementedError(f"{name} supports update_batch_size == 1 only")
+        if not (getattr(env, "continuous_actions", False) and getattr(env, "emits_real_next_obs", False)):
+            raise ValueError(f"{name} needs an environment with continuous actions that returns its pre-reset observation "
+                             f"(env=spread); {type(env).__name__} is not one")
+        head = make_action_head(dict(net.get("action_head", None) or {}, independent_std=False), env.action_dim)
+        if type(head).__name__ != "ContinuousActionHead":
+            raise ValueError(f"{name} needs a ContinuousActionHead (network=continuous_mlp), got {type(head).__name__}")
+        actor_torso, q_torso = torso_from_config(net.actor_network.pre_torso), torso_from_config(net.critic_network.pre_torso)
+        if isinstance(q_torso, CNNTorso):
+            raise NotImplementedError(f"{name}: a CNN critic torso cannot read [state | action] rows (use an MLPTorso)")
+        if centralised and not getattr(env, "add_global_state", False):
+            raise ValueError("Global state must be provided to the centralised critic.")  # networks.py:223-224
+        self.E, self.T, self.K = int(arch.num_envs), int(s.rollout_length), int(s.epochs)
+        if env.num_envs != self.E:
+            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
+        self.B, self.cap = int(s.batch_size), int(s.buffer_size)
+        if self.cap < self.E:
+            raise ValueError(f"buffer_size={self.cap} cannot hold one acting step of num_envs={self.E} items")
+        self.delay = int(s.policy_update_delay)
+        if self.delay < 1:
+            raise ValueError("Need to have a policy update delay > 0.")  # ff_isac.py:347
+        self.n_upd = int(s.get("num_updates_per_eval", 1))
+        self.env = env
+        self.A, self.D, self.O = env.num_agents, env.action_dim, env.obs_dim
+        self.S = env.state_dim if centralised else 0
+        config.system.num_agents = self.A
+        E, A, O, D, S = self.E, self.A, self.O, self.D, self.S
+        self.EA, self.BA = E * A, self.B * A
+        self.Rpa, self.Rp = _pad32(self.EA), _pad32(self.BA)  # acting / sampled rows, padded to the 32-row tiles
+        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
+        if self.matmul_mode not in ("f16x2", "f32"):
+            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
+        self.ctx = ops.Ctx(self.matmul_mode)
+        self.min_scale = float(head.min_scale)
+        self.actor_network = GenericActor(actor_torso, head, O, getattr(env, "obs_shape", None))
+        self.actor_network.ctx = self.ctx
+        self.Kq = (S + A * D) if centralised else (O + D)  # ff_masac.py:108-128 / ff_isac.py:106-125
+        self.a_off = S if centralised else O
+        self.q_network = QNetwork(q_torso, self.Kq, centralised)
+        self.q_network.net.ctx = self.ctx
+        Pa, Pq = self.Pa, self.Pq = self.actor_network.num_params, self.q_network.num_params
+        z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=d)
+        # parameters, Adam moments and gradients: the actor; [q1 | q2] online and target; log_alpha (A)
+        self.pa, self.ma, self.va, self.ga = z(Pa), z(Pa), z(Pa), z(Pa)
+        self.pq, self.pqt, self.mq, self.vq, self.gq = z(2 * Pq), z(2 * Pq), z(2 * Pq), z(2 * Pq), z(2 * Pq)
+        self.log_alpha, self.ml, self.vl, self.gl = z(A), z(A), z(A), z(A)
+        self.count = z(3, dtype=torch.int32)  # Adam steps of the actor, Q and alpha chains
+        self.scratch = z(Pq)  # the Q parameter gradients of the actor step: computed, never used
+        u8 = torch.uint8
+        # ---- acting: ping-pong current / next observation (rows padded with zeros)
+        self.view = [z(self.Rpa, O) for _ in range(2)]
+        self.gs = [z(E, 1, env.state_dim) for _ in range(2)]
+        self.mask = z(E, A, D, dtype=u8)
+        self.sc = [z(E, A, dtype=torch.int32) for _ in range(2)]
+        self.action = z(self.Rpa, D)
+        self.reward, self.done_step = z(E, A), z(E, A, dtype=u8)
+        self.term = z(E, dtype=u8)
+        self.real_view, self.real_mask, self.real_gs = z(E, A, O), z(E, A, D, dtype=u8), z(E, 1, env.state_dim)
+        self.state = env.alloc_state()
+        self.cur = 0
+        self.info_return = z(self.n_upd, self.T, E)
+        self.info_length = z(self.n_upd, self.T, E, dtype=torch.int32)
+        self.info_terminal = z(self.n_upd, self.T, E, dtype=u8)
+        self.ws_act = self.actor_network.net.workspace(self.Rpa, d, training=False)
+        # ---- item buffer (fbx.make_item_buffer(add_batches=True), :171-176) and one sampled batch
+        cap, B, Rp = self.cap, self.B, self.Rp
+        gs_buf = lambda n: z(n, S) if S else None
+        self.buf = Transition(obs=(z(cap, A, O), gs_buf(cap)), action=z(cap, A, D), reward=z(cap, A), done=z(cap, A, dtype=u8),
+                              next_obs=(z(cap, A, O), gs_buf(cap)))
+        self.smp = Transition(obs=(z(Rp, O), gs_buf(B)), action=z(Rp, D), reward=z(Rp), done=z(Rp, dtype=u8),
+                              next_obs=(z(Rp, O), gs_buf(B)))
+        self.index = z(B, dtype=torch.int32)
+        # ---- training workspaces and row vectors
+        an, qn = self.actor_network.net, self.q_network.net
+        self.ws_pi = an.workspace(Rp, d, training=True)    # the actor pass the actor gradient goes back through
+        self.ws_pi_inf = an.workspace(Rp, d, training=False)  # next_obs (update_q) and obs again (alpha): no backward
+        self.ws_q = [qn.workspace(Rp, d, training=True) for _ in range(2)]
+        self.ws_qt = qn.workspace(Rp, d, training=False)
+        self.x_q, self.x_next = z(Rp * self.q_network.ld), z(Rp * self.q_network.ld)
+        self.dx = [z(Rp * self.Kq) for _ in range(2)]
+        self.new_action, self.eps, self.logp = z(Rp, D), z(Rp, D), z(Rp)
+        self.q_t = [z(Rp) for _ in range(2)]
+        self.target = z(Rp)
+        self.ones = z(Rp)
+        self.ones[: self.BA] = 1.0  # d sum(q) / d q on the real rows: the head gradient of the dQ/da passes
+        self.q_partials, self.pi_partials = z(LOSS_BLOCKS, 4), z(LOSS_BLOCKS, 2)
+        self.alpha_parts = z(A)
+        # per (update, epoch): q1_loss, q2_loss, mean q1, mean q2, actor_loss, alpha_loss
+        self.train_metrics = z(self.n_upd, self.K, 6)
+        # the backward chains run in units of a power of two near the row count (f16 range, as in RecLearner)
+        self.grad_scale = float(2 ** math.ceil(math.log2(Rp)))
+        self.seed = int(s.seed)
+        self.gamma, self.tau = float(s.gamma), float(s.tau)
+        self.policy_lr, self.q_lr, self.alpha_lr = float(s.policy_lr), float(s.q_lr), float(s.alpha_lr)
+        self.max_grad_norm = float(s.max_grad_norm)
+        self.autotune = bool(s.autotune)
+        self.init_alpha = float(s.init_alpha)
+        self.target_entropy = -float(s.target_entropy_scale) * D  # :128
+        self.explore_steps = int(s.explore_steps) // E  # acting steps with random actions (:470)
+        self.t = 0           # env steps taken (num_envs per act step): what the policy-delay test reads
+        self.act_steps = 0   # act steps taken: the env's Philox counter and the acting noise's
+        self.n_added = 0     # items stored
+        self.t_train = 0     # train steps taken: counter of the sampler and of the train noise
+        self._learn_calls = 0
+        self._explore_gen = torch.Generator(device=d)
+        self.debug: Optional[Dict[str, List[Any]]] = None  # tests: clones of gradients / noise / indices when set
+
+    # ------------------------------------------------------------------------------------ setup
+    def init_params(self, actor_seed: int, q_seeds) -> None:
+        """:104-125, :132-136: four Q keys (the targets start apart from the online networks), zero or log(init_alpha)."""
+        self.pa.copy_(self.actor_network.init_flat(actor_seed))
+        Pq = self.Pq
+        for dst, k in ((self.pq[:Pq], 0), (self.pq[Pq:], 1), (self.pqt[:Pq], 2), (self.pqt[Pq:], 3)):
+            dst.copy_(self.q_network.init_flat(int(q_seeds[k])))
+        self.log_alpha.fill_(0.0 if self.autotune else math.log(self.init_alpha))
+        for t in (self.ma, self.va, self.mq, self.vq, self.ml, self.vl, self.count):
+            t.zero_()
+        self._explore_gen.manual_seed(self.seed)
+
+    def _obs_slot(self, k: int) -> Dict[str, torch.Tensor]:
+        E, A = self.E, self.A
+        return {"agents_view": self.view[k][: self.EA].view(E, A, self.O), "global_state": self.gs[k], "action_mask": self.mask,
+                "step_count": self.sc[k]}
+
+    def reset_envs(self) -> None:
+        self.cur = 0
+        self.env.step_into(self.state, 0, self._obs_slot(0), is_reset=True)
+
+    # ------------------------------------------------------------------------------------ pieces
+    def _pi(self, ws, obs_rows: torch.Tensor, rows: int, n_real: int, seed: int, step: int, action, logp, eps) -> None:
+        """pi = actor(obs); action = pi.sample(key); log_prob = pi.log_prob(action) - with the noise kept."""
+        mean, log_std = self.actor_network.net.forward(self.pa, ws, obs_rows.view(1, rows, 1, self.O), 1, None, rows, rows, 1)
+        launch("sac_sample", lib().mava_sac_sample_f32, rows, n_real, self.D, self.min_scale, ptr(mean), ptr(log_std),
+               seed & (2**64 - 1), step & 0xFFFFFFFF, 0, ptr(action), ptr(logp), ptr(eps), stream_ptr())
+
+    def _concat(self, x: torch.Tensor, nxt: bool, action, action_new) -> None:
+        sm = self.smp
+        side = sm.next_obs if nxt else sm.obs
+        state, share = (side[1], self.A) if self.centralised else (side[0], 1)
+        launch("sac_concat", lib().mava_sac_concat_f32, self.Rp, self.BA, self.S if self.centralised else self.O, share, self.A,
+               self.D, int(self.centralised), ptr(state), ptr(action), ptr(action_new), ptr(x), self.q_network.ld, stream_ptr())
+
+    def _q(self, flat: torch.Tensor, ws, x: torch.Tensor) -> torch.Tensor:
+        Rp = self.Rp
+        return self.q_network.net.forward(flat, ws, None, 1, None, Rp, Rp, 1, x_t32=x, x_t32_ld=self.q_network.ld)[0]
+
+    def _adam(self, p, g, m, v, chain: int, lr: float) -> None:
+        """optax.chain(clip_by_global_norm(max_grad_norm), adam(lr)) (:144-153)."""
+        ops.clip_adam(p, g, m, v, self.count[chain : chain + 1], [0, p.numel()], [lr], grad_scale=1.0, max_norm=self.max_grad_norm,
+                      eps=ADAM_EPS)
+
+    # ------------------------------------------------------------------------------------ acting
+    def _step(self, info, action_rows: torch.Tensor) -> None:
+        """:245-260: step the envs with `action_rows` (Rpa, D), add the transitions.  `info`: the (E,) episode-metric slots."""
+        E, A, EA = self.E, self.A, self.EA
+        c, nx = self.cur, 1 - self.cur
+        real = {"agents_view": self.real_view, "action_mask": self.real_mask, "global_state": self.real_gs if self.S else None}
+        self.env.step_into(self.state, self.act_steps + 1, self._obs_slot(nx), self.reward, self.done_step, *info,
+                           action=action_rows[:EA].view(E, A, self.D), real_obs=real, terminated=self.term)
+        b = self.buf
+        launch("sac_replay_add", lib().mava_sac_replay_add_f32, E, A, self.O, self.D, self.S, self.cap, self.n_added % self.cap,
+               ptr(self.view[c]), ptr(action_rows), ptr(self.reward), ptr(self.term), ptr(self.real_view),
+               ptr(self.gs[c]) if self.S else None, ptr(self.real_gs) if self.S else None, ptr(b.obs[0]), ptr(b.action),
+               ptr(b.reward), ptr(b.done), ptr(b.next_obs[0]), ptr(b.obs[1]), ptr(b.next_obs[1]), stream_ptr())
+        self.cur = nx
+        self.n_added += E
+        self.t += E
+        self.act_steps += 1
+
+    def _act_step(self, n: int, t: int) -> None:
+        """:418-429."""
+        self._pi(self.ws_act, self.view[self.cur], self.Rpa, self.EA, self.seed, self.act_steps, self.action, None, None)
+        if self.debug is not None:
+            self.debug["actions"].append(self.action[: self.EA].clone())
+        self._step((self.info_return[n, t], self.info_length[n, t], self.info_terminal[n, t]), self.action)
+
+    def explore(self) -> Dict[str, torch.Tensor]:
+        """:431-444, :470-478: explore_steps // num_envs steps with actions uniform in [0, 1) (jax.random.uniform's default
+        range - the reference does not map it to the action range)."""
+        E, d, n = self.E, self.device, self.explore_steps
+        ret, ln = torch.zeros((max(n, 1), E), device=d), torch.zeros((max(n, 1), E), dtype=torch.int32, device=d)
+        tm = torch.zeros((max(n, 1), E), dtype=torch.uint8, device=d)
+        for k in range(n):
+            self.action[: self.EA].copy_(torch.rand((self.EA, self.D), generator=self._explore_gen, device=d))
+            self._step((ret[k], ln[k], tm[k]), self.action)
+        return {"episode_return": ret, "episode_length": ln, "is_terminal_step": tm.bool()}
+
+    # ------------------------------------------------------------------------------------ training
+    def _update_q(self, n: int, k: int) -> None:
+        """:305-340."""
+        L_, s, sm = lib(), stream_ptr(), self.smp
+        Rp, BA, Pq = self.Rp, self.BA, self.Pq
+        key = self.seed ^ TRAIN_KEY_TAG
+        self._pi(self.ws_pi_inf, sm.next_obs[0], Rp, BA, key, 3 * self.t_train, self.new_action, self.logp, self.eps)
+        if self.debug is not None:
+            self.debug["eps_q"].append(self.eps.clone())
+        self._concat(self.x_next, True, self.new_action, None)
+        for i in range(2):
+            self.q_t[i].copy_(self._q(self.pqt[i * Pq : (i + 1) * Pq], self.ws_qt, self.x_next)[:Rp])
+        self._concat(self.x_q, False, sm.action, None)
+        q = [self._q(self.pq[i * Pq : (i + 1) * Pq], self.ws_q[i], self.x_q) for i in range(2)]
+        launch("sac_q_loss", L_.mava_sac_q_loss_f32, Rp, BA, self.A, ptr(q[0]), ptr(q[1]), ptr(self.q_t[0]), ptr(self.q_t[1]),
+               ptr(self.logp), ptr(sm.reward), ptr(sm.done), ptr(self.log_alpha), self.gamma, self.grad_scale,
+               ptr(self.ws_q[0].dout[0]), ptr(self.ws_q[1].dout[0]), ptr(self.target), ptr(self.q_partials), LOSS_BLOCKS, s)
+        ops.slab_reduce(self.q_partials, 4, self.train_metrics[n, k, :4])
+        for i in range(2):
+            self.q_network.net.backward(self.pq[i * Pq : (i + 1) * Pq], self.ws_q[i], [self.ws_q[i].dout[0]],
+                                        self.gq[i * Pq : (i + 1) * Pq], accumulate=False, grad_scale=self.grad_scale)
+        if self.debug is not None:
+            self.debug["g_q"].append(self.gq.clone())
+            self.debug["target"].append(self.target.clone())
+        self._adam(self.pq, self.gq, self.mq, self.vq, 1, self.q_lr)
+        launch("target_update", L_.mava_target_update_f32, 2 * Pq, ptr(self.pq), ptr(self.pqt), self.tau, 0, s)  # :331-333
+
+    def _update_actor_and_alpha(self, n: int, k: int) -> None:
+        """:342-384: policy_update_delay repetitions on the same batch with the same two noise draws."""
+        L_, s, sm = lib(), stream_ptr(), self.smp
+        Rp, BA, Pq, A, D = self.Rp, self.BA, self.Pq, self.A, self.D
+        key = self.seed ^ TRAIN_KEY_TAG
+        an, ws = self.actor_network.net, self.ws_pi
+        for _ in range(self.delay):
+            self._pi(ws, sm.obs[0], Rp, BA, key, 3 * self.t_train + 1, self.new_action, None, self.eps)
+            self._concat(self.x_q, False, sm.action if self.centralised else self.new_action,
+                         self.new_action if self.centralised else None)
+            q = []
+            for i in range(2):  # Q(obs, new action) and d sum(Q) / d input; the parameter gradients are discarded
+                q.append(self._q(self.pq[i * Pq : (i + 1) * Pq], self.ws_q[i], self.x_q))
+                self.q_network.net.backward(self.pq[i * Pq : (i + 1) * Pq], self.ws_q[i], [self.ones], self.scratch, accumulate=False,
+                                            grad_scale=1.0, dx_out=self.dx[i])
+            mean, log_std = ws.out[0], ws.out[1]
+            launch("sac_actor_grad", L_.mava_sac_actor_grad_f32, Rp, BA, A, D, self.min_scale, ptr(mean), ptr(log_std), ptr(self.eps),
+                   ptr(self.new_action), ptr(self.log_alpha), ptr(q[0]), ptr(q[1]), ptr(self.dx[0]), ptr(self.dx[1]), self.Kq,
+                   self.a_off, int(self.centralised), 1.0, self.grad_scale, ptr(ws.dout[0]), ptr(ws.dout[1]), ptr(self.pi_partials),
+                   LOSS_BLOCKS, s)
+            ops.slab_reduce(self.pi_partials, 1, self.train_metrics[n, k, 4:5])
+            an.backward(self.pa, ws, [ws.dout[0], ws.dout[1]], self.ga, accumulate=False, grad_scale=self.grad_scale)
+            if self.debug is not None:
+                self.debug["g_actor"].append(self.ga.clone())
+                self.debug["eps_actor"].append(self.eps.clone())
+            self._adam(self.pa, self.ga, self.ma, self.va, 0, self.policy_lr)
+            if self.autotune:  # :367-381: the log-prob under the UPDATED actor, with `key` itself as the noise key
+                self._pi(self.ws_pi_inf, sm.obs[0], Rp, BA, key, 3 * self.t_train + 2, self.new_action, self.logp, self.eps)
+                launch("sac_alpha_loss", L_.mava_sac_alpha_loss_f32, BA, A, ptr(self.logp), ptr(self.log_alpha), self.target_entropy,
+                       ptr(self.gl), ptr(self.alpha_parts), s)
+                ops.slab_reduce(self.alpha_parts.view(A, 1), 1, self.train_metrics[n, k, 5:6])
+                if self.debug is not None:
+                    self.debug["g_alpha"].append(self.gl.clone())
+                    self.debug["eps_alpha"].append(self.eps.clone())
+                self._adam(self.log_alpha, self.gl, self.ml, self.vl, 2, self.alpha_lr)
+
+    def _train_step(self, n: int, k: int, t: int) -> None:
+        """:387-416 with `t` the env-step counter entering the update step."""
+        b, sm = self.buf, self.smp
+        launch("sac_replay_sample", lib().mava_sac_replay_sample_f32, self.A, self.O, self.D, self.S, self.cap,
+               self.n_added & 0xFFFFFFFF, self.B, self.Rp, self.seed & (2**64 - 1), self.t_train & 0xFFFFFFFF, ptr(b.obs[0]),
+               ptr(b.action), ptr(b.reward), ptr(b.done), ptr(b.next_obs[0]), ptr(b.obs[1]), ptr(b.next_obs[1]), ptr(sm.obs[0]),
+               ptr(sm.action), ptr(sm.reward), ptr(sm.done), ptr(sm.next_obs[0]), ptr(sm.obs[1]), ptr(sm.next_obs[1]),
+               ptr(self.index), stream_ptr())
+        if self.debug is not None:
+            self.debug["index"].append(self.index.clone())
+        self._update_q(n, k)
+        if t % self.delay == 0:
+            self._update_actor_and_alpha(n, k)
+        else:
+            self.train_metrics[n, k, 4:].zero_()  # :403-407
+        self.t_train += 1
+
+    def update(self, n: int) -> None:
+        """:450-466: rollout_length act steps, then `epochs` train steps that all see the `t` from before the act steps."""
+        t = self.t
+        for k in range(self.T):
+            self._act_step(n, k)
+        for k in range(self.K):
+            self._train_step(n, k, t)
+
+    # ---------------------------------------------------------------------------- state views
+    def params(self, lead=(1, 1)) -> SacParams:
+        Pq, an, qn = self.Pq, self.actor_network, self.q_network
+        qv = lambda flat: QVals(qn.tree(flat[:Pq], lead), qn.tree(flat[Pq:], lead))
+        return SacParams(an.tree(self.pa, lead), QValsAndTarget(qv(self.pq), qv(self.pqt)), self.log_alpha.expand(*lead, 1, self.A))
+
+    def learner_state(self) -> LearnerState:
+        lead = (1, 1)
+        Pq, an, qn = self.Pq, self.actor_network, self.q_network
+        E, A, c = self.E, self.A, self.cur
+        view, mask, sc = self.view[c][: self.EA].view(1, 1, E, A, self.O), self.mask.view(1, 1, E, A, self.D).bool(), self.sc[c].view(1, 1, E, A)
+        if self.centralised:
+            obs = ObservationGlobalState(view, mask, self.gs[c].view(1, 1, E, 1, -1).expand(1, 1, E, A, -1), sc)
+        else:
+            obs = Observation(view, mask, sc)
+        cnt = lambda i: self.count[i].expand(1, 1)
+        qm = lambda flat: QVals(qn.tree(flat[:Pq], lead), qn.tree(flat[Pq:], lead))
+        opt = OptStates(AdamState(cnt(0), an.tree(self.ma, lead), an.tree(self.va, lead)),
+                        AdamState(cnt(1), qm(self.mq), qm(self.vq)),
+                        AdamState(cnt(2), self.ml.expand(1, 1, 1, A), self.vl.expand(1, 1, 1, A)))
+        env_state = {"step_count": self.state.step_count, "episode_return": self.state.ep_return,
+                     "episode_length": self.state.ep_length}
+        buffer_state = {"experience": self.buf, "current_index": self.n_added % self.cap, "is_full": self.n_added >= self.cap}
+        return LearnerState(obs, env_state, buffer_state, self.params(lead), opt, torch.tensor([[self.t]], dtype=torch.int64),
+                            torch.tensor([[[self.seed, self.act_steps]]], dtype=torch.int64))
+
+    def adopt(self, state: LearnerState) -> None:
+        """Make the parameters equal to `state.params` (no-op for trees that alias them), e.g. a restored checkpoint.
+        Environment, buffer and optimiser state stay with the learner."""
+        p = state.params
+        leaf = self.actor_network.first_leaf(p.actor)
+        if isinstance(leaf, torch.Tensor) and leaf.data_ptr() == self.pa.data_ptr():
+            return
+        to = lambda tree: _tree_to(tree, self.device)
+        Pq = self.Pq
+        self.actor_network.flat_from_tree(to(p.actor), self.pa)
+        for flat, qv in ((self.pq, p.q.online), (self.pqt, p.q.targets)):
+            self.q_network.flat_from_tree(to(qv.q1), flat[:Pq])
+            self.q_network.flat_from_tree(to(qv.q2), flat[Pq:])
+        self.log_alpha.copy_(torch.as_tensor(p.log_alpha).reshape(-1)[-self.A:].to(self.device))
+
+    def learn(self, state: LearnerState) -> ExperimentOutput:
+        self.adopt(state)
+        if self.matmul_mode == "f16x2":
+            check_f16_range(torch.cat([self.pa, self.pq]), [self.view[self.cur]], self.train_metrics if self._learn_calls else None,
+                            type(self).__name__)
+        self._learn_calls += 1
+        for n in range(self.n_upd):
+            self.update(n)
+        episode_metrics = {
+            "episode_return": self.info_return.unsqueeze(1).unsqueeze(0),
+            "episode_length": self.info_length.unsqueeze(1).unsqueeze(0),
+            "is_terminal_step": self.info_terminal.unsqueeze(1).unsqueeze(0).bool(),
+        }
+        tm = self.train_metrics
+        train_metrics = {"q1_loss": tm[..., 0], "q2_loss": tm[..., 1], "loss": tm[..., 0] + tm[..., 1], "q1_a_vals": tm[..., 2],
+                         "q2_a_vals": tm[..., 3], "actor_loss": tm[..., 4], "alpha_loss": tm[..., 5]}
+        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
+
+
+def _tree_to(tree: Any, device) -> Any:
+    if isinstance(tree, torch.Tensor):
+        return tree.to(device)
+    if isinstance(tree, dict):
+        return {k: _tree_to(v, device) for k, v in tree.items()}
+    return tree
+
+
+def learner_setup(env, keys, config, centralised: bool, device=None):
+    """Counterpart of init + make_update_fns (ff_isac.py:58-208, :211-488): (learn, actor_network, initial LearnerState).
+    `keys` = (key, actor key, four Q keys...).  `learn(state)` runs num_updates_per_eval update steps; `learn.explore()`
+    fills the buffer with random actions first (:526-527)."""
+    learner = SACLearner(env, config, centralised, device)
+    learner.seed = int(keys[0])
+    learner.init_params(int(keys[1]), [int(k) for k in keys[2:6]])
+    learner.reset_envs()
+
+    def learn(learner_state: LearnerState) -> ExperimentOutput:
+        return learner.learn(learner_state)
+
+    learn.learner = learner  # type: ignore[attr-defined]
+    learn.explore = learner.explore  # type: ignore[attr-defined]
+    return learn, learner.actor_network, learner.learner_state()

@@ -1,0 +1,34 @@
+"""ff_isac: independent soft actor-critic: each agent's Q network reads its own view and its own action (mava/systems/sac/ff_isac.py).
+
+`learner_setup(env, keys, config)` (init + make_update_fns) and `run_experiment(config, log=None)`: explore with random
+actions, then per evaluation interval train, log MISC / ACT / TRAIN (the losses and log_alpha), EVAL, checkpoint SacParams,
+and finally ABSOLUTE with the best actor.  Runs on env=spread, the one environment here with continuous actions.
+
+    python -m mava_amd.systems.sac.ff_isac system.total_timesteps=200000
+"""
+from __future__ import annotations
+
+from ... import sac_learner as _learner
+from . import _runner
+
+CENTRALISED_CRITIC = False
+
+
+def learner_setup(env, keys, config, device=None):
+    return _learner.learner_setup(env, keys, config, CENTRALISED_CRITIC, device)
+
+
+def _check_config(config) -> None:
+    _runner.check_config(config, "ff_isac")
+
+
+def run_experiment(config, log=None) -> float:
+    return _runner.run_experiment(config, CENTRALISED_CRITIC, log=log)
+
+
+if __name__ == "__main__":
+    import sys
+
+    from ...config import compose
+
+    print(run_experiment(compose("default_ff_isac_spread", sys.argv[1:])))

@@ -1,0 +1,35 @@
+"""ff_masac: multi-agent soft actor-critic: a centralised Q network on the global state and the joint action
+(mava/utils/centralised_training.py), the env made with add_global_state=True (mava/systems/sac/ff_masac.py).
+
+`learner_setup(env, keys, config)` (init + make_update_fns) and `run_experiment(config, log=None)`: explore with random
+actions, then per evaluation interval train, log MISC / ACT / TRAIN (the losses and log_alpha), EVAL, checkpoint SacParams,
+and finally ABSOLUTE with the best actor.  Runs on env=spread, the one environment here with continuous actions.
+
+    python -m mava_amd.systems.sac.ff_masac system.total_timesteps=200000
+"""
+from __future__ import annotations
+
+from ... import sac_learner as _learner
+from . import _runner
+
+CENTRALISED_CRITIC = True
+
+
+def learner_setup(env, keys, config, device=None):
+    return _learner.learner_setup(env, keys, config, CENTRALISED_CRITIC, device)
+
+
+def _check_config(config) -> None:
+    _runner.check_config(config, "ff_masac")
+
+
+def run_experiment(config, log=None) -> float:
+    return _runner.run_experiment(config, CENTRALISED_CRITIC, log=log)
+
+
+if __name__ == "__main__":
+    import sys
+
+    from ...config import compose
+
+    print(run_experiment(compose("default_ff_masac_spread", sys.argv[1:])))
