@@ -707,6 +707,34 @@ int mava_q_td_loss_f32(int L, int Rp, int n_actions, int n_real, const float* q,
  * hard = 1: target = online (optax.periodic_update on a step where it fires; the caller decides when). */
 int mava_target_update_f32(long n, const float* online, float* target, float tau, int hard, mava_stream_t s);
 
+/* ---- value decomposition (rec_qmix / rec_vdn, mava/systems/q_learning/rec_qmix.py; mava_amd/csrc/qmix.hip).  Agent rows
+ *      are t * Rp + b * A + j as above (Rp a multiple of 32 with B * A <= Rp); a MIXER row is t * Bp + b with
+ *      Bp = ceil32(B), padding where b >= B.  All matrices are T32.
+ * The mixer's state: state / next_state (T32, L * Bp rows x k_pad features, k_pad >= A * O) from the time-major sample
+ * obs / next_obs (>= L, Rp, O): row (t, b), feature j * O + f = obs[t, b * A + j, f]; padding rows and the features from
+ * A * O on are 0.  A pure gather (bit exact).  The outputs must not alias each other or an input. */
+int mava_qmix_state_t32_f32(int L, int B, int A, int O, int Rp, int k_pad, const float* obs, const float* next_obs, float* state,
+                            float* next_state, mava_stream_t s);
+/* TD loss through the mixer in one launch.  q / q_next_online / q_next_target: T32 (L * Rp x n_actions); action / reward /
+ * terminal_next (L, Rp), next_mask (L, Rp, n_actions) as for mava_q_td_loss_f32.  Per real mixer row: qa_j = q[action_j],
+ * a*_j = first argmax of where(next_mask, q_next_online, finfo.min), qnext_j = q_next_target[a*_j], r = mean_j reward,
+ * terminal = agent 0's flag, y = r + (1 - terminal) * gamma * Q_tot_target(qnext), loss = mean (Q_tot(qa) - y)^2 over the
+ * N = L * B real mixer rows.  mode 1 (qmix): Q_tot = sum_k elu(sum_j qa_j |w1[j * Em + k]| + b1[k]) |w2[k]| + b2 with the
+ * hypernet outputs w1 (L * Bp x A * Em), b1, w2 (x Em), b2 (x 1), pre-abs, and the target ones likewise; mode 0 (vdn):
+ * Q_tot = sum_j qa_j, every hypernet pointer may be NULL and Em is ignored.  Outputs in units of grad_scale: dq (T32, every
+ * element written: 0 off the taken action and on padding agent rows) and, in mode 1, d_w1 / d_b1 / d_w2 / d_b2 (T32, the
+ * gradient w.r.t. the pre-abs outputs; d|x|/dx = 0 at 0; padding mixer rows 0).  partials (nblk, 3): per-block sums of
+ * (q_loss, mean_q, mean_target) already divided by N; a block without rows writes zeros.  The gradients do not depend on
+ * nblk.  Refused: A outside [1, 16], Em outside [1, 64] (mode 1), n_actions outside [1, 32], Rp not a multiple of 32 holding
+ * B * A, nblk outside [1, 4096], a NULL pointer (hypernet pointers in mode 1), dq aliasing a Q input, a hypernet gradient
+ * aliasing its input. */
+int mava_qmix_td_f32(int mode, int L, int B, int A, int Rp, int n_actions, int Em, const float* q, const float* q_next_online,
+                     const float* q_next_target, const int32_t* action, const float* reward, const uint8_t* terminal_next,
+                     const uint8_t* next_mask, const float* w1, const float* b1, const float* w2, const float* b2,
+                     const float* w1_target, const float* b1_target, const float* w2_target, const float* b2_target, float gamma,
+                     float grad_scale, float* dq, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* partials, int nblk,
+                     mava_stream_t s);
+
 /* ---- soft actor-critic (ff_isac / ff_masac): mava/systems/sac/ff_isac.py:245-384, ff_masac.py,
  *      mava/utils/centralised_training.py (mava_amd/csrc/sac.hip).  The actor (ContinuousActionHead with
  *      independent_std = False) and the two Q networks (torso -> Dense(1) on [state | action]) run on the general layer

@@ -78,6 +78,8 @@ _SIGNATURES = {
     "mava_replay_sample_f32": [i32] * 5 + [u32, i32, i32, i32, u64, u32] + [vp] * 17 + [vp],
     "mava_q_td_loss_f32": [i32, i32, i32, i32] + [vp] * 7 + [f32, f32, vp, vp, i32, vp],
     "mava_target_update_f32": [lng, vp, vp, f32, i32, vp],
+    "mava_qmix_state_t32_f32": [i32] * 6 + [vp] * 4 + [vp],
+    "mava_qmix_td_f32": [i32] * 7 + [vp] * 15 + [f32, f32] + [vp] * 6 + [i32, vp],
     "mava_sac_replay_add_f32": [i32] * 7 + [vp] * 14 + [vp],
     "mava_sac_replay_sample_f32": [i32] * 5 + [u32, i32, i32, u64, u32] + [vp] * 15 + [vp],
     "mava_sac_sample_f32": [i32, i32, i32, f32, vp, vp, u64, u32, u32, vp, vp, vp, vp],

@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "smax.hip",
     "spread.hip",
     "q_learning.hip",
+    "qmix.hip",
     "sac.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",
