@@ -843,6 +843,51 @@ int mava_t32_col2im_f32(const float* dcol, int src_flat, long samples, int Hin, 
 /* jax.lax.collapse(x, -3): T32 (samples*P x C) -> T32 (samples x P*C) (to_flat = 1) and back (0) */
 int mava_t32_flatten_f32(const float* src, long samples, int P, int C, int to_flat, float* dst, mava_stream_t s);
 
+/* ---- Multi-Agent Transformer (ff_mat; csrc/mat.hip): what sits between the dense products of the encoder and the
+ *      decoder.  All matrices T32 with `rows` a multiple of 32; agent row b * A + j belongs to sample b, rows past B * A
+ *      (valid_rows) are padding and come out exact zero.  Sums in f64, storage f32, no atomics; outputs bit-identical for
+ *      any n_blocks. */
+/* y = concat_heads(softmax(q k^T / sqrt(D / n_head)) v) over the A <= 32 agents of each sample, D / n_head <= 128; with
+ * `causal` agent i sees the keys j <= i.  q may come from another matrix than k and v (cross-attention).  p (or NULL):
+ * T32 (rows x n_head * A) receives the probabilities, feature h * A + j, exact zero above the diagonal when causal. */
+int mava_mat_attn_fwd_f32(const float* q, const float* k, const float* v, long rows, int D, int B, int A, int n_head,
+                          int causal, float* y, float* p, int n_blocks, mava_stream_t s);
+/* dq, dk, dv from dy and the saved q, k, v (linear in dy: a grad_scale passes through).  The probabilities are computed
+ * again in f64 from q and k: the softmax backward cancels, and the f32 copy in p is not accurate enough for it. */
+int mava_mat_attn_bwd_f32(const float* dy, const float* q, const float* k, const float* v, long rows, int D, int B, int A,
+                          int n_head, int causal, float* dq, float* dk, float* dv, int n_blocks, mava_stream_t s);
+/* y = LayerNorm(x + res) * scale + bias over the last axis (flax: eps 1e-6, biased variance); res may be NULL, any N >= 1;
+ * xhat (T32) and rstd (rows) are saved for the backward pass (both NULL for inference). */
+int mava_mat_ln_fwd_f32(const float* x, const float* res, const float* scale, const float* bias, int N, long rows,
+                        long valid_rows, float* y, float* xhat, float* rstd, int n_blocks, mava_stream_t s);
+/* dx (= dres) and per-block slabs (n_slab, slab_stride >= 2 N) of out_scale * [dscale (N) | dbias (N)], to be summed by
+ * mava_slab_reduce_f32; a block without tiles writes exact zeros. */
+int mava_mat_ln_bwd_f32(const float* dy, const float* xhat, const float* rstd, const float* scale, int N, long rows,
+                        long valid_rows, float out_scale, float* dx, float* slab, long slab_stride, int n_slab, mava_stream_t s);
+/* flax nn.gelu (tanh approximation) on n floats, and dx = dy * gelu'(x) */
+int mava_mat_gelu_f32(const float* x, long n, float* y, mava_stream_t s);
+int mava_mat_gelu_bwd_f32(const float* dy, const float* x, long n, float* dx, mava_stream_t s);
+/* The decoder's input, T32 (rows x n_pad), n_pad = ceil32(n_actions + 1): row (b, 0) = e_0, row (b, i) = [0 | onehot(action[
+ * sample, i - 1])] for 1 <= i <= known, zero rows after that (acting: known = agents decoded so far; training: A - 1).
+ * action: (samples, A) i32; sample = idx[b], or b when idx is NULL. */
+int mava_mat_shift_onehot_f32(const int32_t* action, const int32_t* idx, int B, int A, int n_actions, int known, long rows,
+                              int n_pad, float* out, mava_stream_t s);
+/* One step of the autoregressive decode: agent `agent` of each of the B samples draws from the masked Categorical of its
+ * T32 logits row (rows x n_actions, n_actions <= 64; mask (B, A, n_actions) u8 or NULL) exactly as mava_seq_sample_f32
+ * does for row b * A + agent - same masking, same Philox counters - and writes action / log_prob[b * A + agent]. */
+int mava_mat_sample_f32(int B, int A, int agent, int n_actions, const float* logits, const uint8_t* mask, uint64_t seed,
+                        uint32_t step, uint32_t row_offset, int greedy, int32_t* action, float* log_prob, mava_stream_t s);
+/* mava_seq_actor_loss_f32's and mava_seq_critic_loss_f32's formulas on a minibatch of Bm (t, env) samples whose A agent
+ * rows are contiguous: row b * A + j reads the (samples, A[, n_actions]) trajectory arrays at sample idx[b].  Means over
+ * the Bm * A agent rows; adv_stats from mava_adv_stats_f64 over the same rows.  Writes dlogits (T32) and dvalues (rows),
+ * both times grad_scale (dvalues includes vf_coef), zero on padding rows, and loss_partials (n_blocks, 3) =
+ * [actor_loss, entropy, value_loss] partial means. */
+int mava_mat_loss_f32(int Bm, int A, int n_actions, long rows, const int32_t* idx, const float* logits, const float* values,
+                      const uint8_t* mask, const int32_t* action, const float* old_log_prob, const float* advantages,
+                      const float* old_value, const float* targets, const double* adv_stats, int n_stats, float clip_eps,
+                      float ent_coef, float vf_coef, float grad_scale, float* dlogits, float* dvalues, float* loss_partials,
+                      int n_blocks, mava_stream_t s);
+
 /* ---- exchange step: replaces the jax.lax.pmean calls of mava/systems/ppo/ff_mappo.py:224-238
  *      (actor and critic (grads, loss_info) over the "batch" and "device" axes) for a host without torch.distributed.
  *      One process per GPU: rank 0 obtains a 128-byte id (mava_comm_unique_id) and hands it to the other ranks by any

@@ -118,6 +118,15 @@ _SIGNATURES = {
     "mava_rec_step_packed_f32": [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, i32, u64, u32, u32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp],
     "mava_seq_sample_f32": [i32, i32, vp, vp, u64, u32, u32, i32, vp, vp, vp],
     "mava_t32_convert_f32": [vp, i32, i32, i32, vp, vp],
+    "mava_mat_attn_fwd_f32": [vp, vp, vp, lng, i32, i32, i32, i32, i32, vp, vp, i32, vp],
+    "mava_mat_attn_bwd_f32": [vp, vp, vp, vp, lng, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp],
+    "mava_mat_ln_fwd_f32": [vp, vp, vp, vp, i32, lng, lng, vp, vp, vp, i32, vp],
+    "mava_mat_ln_bwd_f32": [vp, vp, vp, vp, i32, lng, lng, f32, vp, vp, lng, i32, vp],
+    "mava_mat_gelu_f32": [vp, lng, vp, vp],
+    "mava_mat_gelu_bwd_f32": [vp, vp, lng, vp, vp],
+    "mava_mat_shift_onehot_f32": [vp, vp, i32, i32, i32, i32, lng, i32, vp, vp],
+    "mava_mat_sample_f32": [i32, i32, i32, i32, vp, vp, u64, u32, u32, i32, vp, vp, vp],
+    "mava_mat_loss_f32": [i32, i32, i32, lng, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp, vp, i32, vp],
 }
 _RESTYPES = {"mava_last_error": C.c_char_p, "mava_rec_step_pack_bytes": C.c_long, "mava_ppo_finish_workspace_bytes": C.c_size_t}
 

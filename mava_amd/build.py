@@ -44,6 +44,7 @@ HIP_SOURCES = [
     "rec_step_h2.hip",
     "rec_out_h2.hip",
     "generic_layers.hip",
+    "mat.hip",
 ]
 CPP_SOURCES = ["api.cpp", "comm.cpp"]
 

@@ -1,0 +1,602 @@
+"""Multi-Agent Transformer learner (ff_mat; Wen et al. 2022, mava.systems.mat) behind Mava's LearnerFn contract.
+
+The reference checkout has no MAT: nothing here is pinned against upstream; the contract is the float64 model in
+tests/mat_model.py (DESIGN.md 3.25 says which upstream conventions were followed from memory).
+
+Network (discrete actions).  One sample is one (t, env) pair with its A agents in order; D = network.n_embd.
+  encoder:  x = LN(GELU(Dense(LN_O(obs))));  n_block x { x = LN(x + Attn(x, x));  x = LN(x + MLP(x)) };  rep = x;
+            value = Dense(1)(LN(GELU(Dense(rep))))
+  decoder:  x = LN(GELU(Dense_nobias(shifted one-hot)));  n_block x { x = LN(x + Attn(x, x, causal));
+            x = LN(rep + Attn(q = rep, kv = x, causal));  x = LN(x + MLP(x)) };  logits = Dense(nA)(LN(GELU(Dense(x))))
+Acting is autoregressive: A decoder passes per env step, pass i samples agent i (mava_mat_sample_f32) and the next pass
+sees its action in the shifted one-hot.  Training is one teacher-forced pass.
+
+Every matrix is T32 with the E * A (acting) or Bm * A (minibatch) agent rows padded to a multiple of 32; the dense products
+are GenericNet._dense / _xty (mava_rec_dense_f32 / mava_rec_xty_f32: system.matmul_mode, grad_scale), everything between
+them is csrc/mat.hip.  Forward and backward are one tape of layer objects: the backward pass walks it in reverse, a layer
+writes the gradient of an input that has none yet and adds to one that has (the dense launch's `accumulate`), and the
+residual input of a LayerNorm shares the gradient buffer of the branch it was added to.
+
+Parameters: one flat vector [encoder | decoder], one global-norm clip and one Adam (ops.clip_adam, one segment).
+"""
+from __future__ import annotations
+
+import math
+import os
+from typing import Any, Dict, List, Optional, Tuple
+
+import torch
+
+from . import ops, parallel
+from ._lib import MavaHipError, launch, lib, ptr, stream_ptr
+from .generic_networks import GenericMLPTorso, GenericNet
+from .guards import check_f16_range
+from .learner import _Replica
+from .networks import _orthogonal_
+from .types import AdamState, ExperimentOutput, LearnerState, Observation, TimeStep
+
+MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
+
+
+def check_supported(*, num_agents: int, n_actions: int, n_embd: int, n_head: int, continuous: bool, world: int,
+                    update_batch_size: int) -> None:
+    """ff_mat's refusals: a MavaHipError with the reason, before anything is allocated or launched."""
+    if continuous:
+        raise MavaHipError("ff_mat: a continuous action head is not implemented (discrete actions only)")
+    if not 1 <= num_agents <= MAX_AGENTS:
+        raise MavaHipError(f"ff_mat: the attention kernels take 1..{MAX_AGENTS} agents, the environment has {num_agents}")
+    if n_embd < 32 or n_embd % 32 or n_embd > MAX_EMBED:
+        raise MavaHipError(f"ff_mat: network.n_embd must be a multiple of 32 up to {MAX_EMBED}, got {n_embd}")
+    if n_head < 1 or n_embd % n_head:
+        raise MavaHipError(f"ff_mat: network.n_embd={n_embd} must be a multiple of network.n_head={n_head}")
+    if not 1 <= n_actions <= MAX_ACTIONS:
+        raise MavaHipError(f"ff_mat: at most {MAX_ACTIONS} actions, the environment has {n_actions}")
+    if world > 1:
+        raise MavaHipError(f"ff_mat runs on one GPU, the process group has {world} ranks")
+    if update_batch_size != 1:
+        raise MavaHipError(f"ff_mat: system.update_batch_size must be 1, got {update_batch_size}")
+
+
+def _attn_leaves(D: int) -> List[Tuple[Tuple[str, ...], Tuple[int, ...], Any]]:
+    out = []
+    for name in ("query", "key", "value", "proj"):
+        out += [((name, "kernel"), (D, D), math.sqrt(2.0)), ((name, "bias"), (D,), 0.0)]
+    return out
+
+
+def _ln_leaves(name: str, N: int):
+    return [((name, "scale"), (N,), "ones"), ((name, "bias"), (N,), 0.0)]
+
+
+def _dense_leaves(name: str, K: int, N: int, scale: float, bias: bool = True):
+    out = [((name, "kernel"), (K, N), scale)]
+    return out + ([((name, "bias"), (N,), 0.0)] if bias else [])
+
+
+def param_spec(O: int, nA: int, D: int, n_block: int):
+    """[(tree path, shape, init)] of the flat vector [encoder | decoder]; init: an orthogonal scale, 0.0 or "ones"."""
+    r2 = math.sqrt(2.0)
+    enc = _ln_leaves("obs_ln", O) + _dense_leaves("obs_dense", O, D, r2) + _ln_leaves("ln", D)
+    for i in range(n_block):
+        b = f"block_{i}"
+        blk = [(("attn",) + p, s, k) for p, s, k in _attn_leaves(D)] + _ln_leaves("ln1", D)
+        blk += _dense_leaves("mlp_0", D, D, r2) + _dense_leaves("mlp_1", D, D, r2) + _ln_leaves("ln2", D)
+        enc += [((b,) + p, s, k) for p, s, k in blk]
+    enc += _dense_leaves("head_dense", D, D, r2) + _ln_leaves("head_ln", D) + _dense_leaves("head_out", D, 1, 0.01)
+    dec = _dense_leaves("act_dense", nA + 1, D, r2, bias=False) + _ln_leaves("ln", D)
+    for i in range(n_block):
+        b = f"block_{i}"
+        blk = [(("attn1",) + p, s, k) for p, s, k in _attn_leaves(D)] + _ln_leaves("ln1", D)
+        blk += [(("attn2",) + p, s, k) for p, s, k in _attn_leaves(D)] + _ln_leaves("ln2", D)
+        blk += _dense_leaves("mlp_0", D, D, r2) + _dense_leaves("mlp_1", D, D, r2) + _ln_leaves("ln3", D)
+        dec += [((b,) + p, s, k) for p, s, k in blk]
+    dec += _dense_leaves("head_dense", D, D, r2) + _ln_leaves("head_ln", D) + _dense_leaves("head_out", D, nA, 0.01)
+    return [(("encoder",) + p, s, k) for p, s, k in enc] + [(("decoder",) + p, s, k) for p, s, k in dec]
+
+
+class MATParams(dict):
+    """{"encoder": ..., "decoder": ...}.  The experiment driver and the evaluator address the acting parameters of a
+    system as `params.actor_params`: for MAT that is the whole tree."""
+
+    @property
+    def actor_params(self) -> "MATParams":
+        return self
+
+
+class MATNet:
+    """Shapes, flat layout and trees of the network."""
+
+    def __init__(self, O: int, nA: int, A: int, D: int, n_head: int, n_block: int):
+        self.O, self.nA, self.A, self.D, self.H, self.n_block = int(O), int(nA), int(A), int(D), int(n_head), int(n_block)
+        self.spec = param_spec(self.O, self.nA, self.D, self.n_block)
+        self.off: Dict[Tuple[str, ...], int] = {}
+        off = 0
+        for path, shape, _ in self.spec:
+            self.off[path], off = off, off + math.prod(shape)
+        self.num_params = off
+
+    def init_flat(self, seed: int) -> torch.Tensor:
+        gen = torch.Generator().manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        flat = torch.zeros(self.num_params, dtype=torch.float32)
+        for path, shape, init in self.spec:
+            v = flat[self.off[path] : self.off[path] + math.prod(shape)].view(shape)
+            if init == "ones":
+                v.fill_(1.0)
+            elif init != 0.0:
+                _orthogonal_(v, float(init), gen)
+        return flat
+
+    def tree(self, flat: torch.Tensor, lead: Tuple[int, ...] = ()) -> MATParams:
+        out = MATParams()
+        for path, shape, _ in self.spec:
+            node = out
+            for k in path[:-1]:
+                node = node.setdefault(k, {})
+            v = flat[self.off[path] : self.off[path] + math.prod(shape)].view(shape)
+            node[path[-1]] = v.expand(*lead, *shape) if lead else v
+        return out
+
+    def flat_from_tree(self, tree: Dict[str, Any], out: torch.Tensor) -> torch.Tensor:
+        for path, shape, _ in self.spec:
+            leaf = tree
+            for k in path:
+                leaf = leaf[k]
+            leaf = torch.as_tensor(leaf)
+            while leaf.dim() > len(shape):
+                leaf = leaf[0]
+            out[self.off[path] : self.off[path] + math.prod(shape)].view(shape).copy_(leaf)
+        return out
+
+    def first_leaf(self, tree: Dict[str, Any]) -> torch.Tensor:
+        return tree["encoder"]["obs_ln"]["scale"]
+
+
+class _Buf:
+    """A T32 (rows x N) matrix with `ld` features per tile, and its gradient during a backward pass."""
+
+    def __init__(self, rows: int, N: int, device, ld: Optional[int] = None, t: Optional[torch.Tensor] = None):
+        self.rows, self.N, self.ld = rows, N, int(ld or N)
+        self.t = t if t is not None else torch.zeros(rows * self.ld, device=device)
+        self.grad: Optional[torch.Tensor] = None
+        self._own: Optional[torch.Tensor] = None
+
+    def own(self) -> torch.Tensor:
+        if self._own is None:
+            self._own = torch.zeros(self.rows * self.N, device=self.t.device)
+        return self._own
+
+
+class _Graph:
+    """The tape of one pass shape: `rows` padded agent rows of B samples.  add_* append a layer and return its output."""
+
+    def __init__(self, net: MATNet, B: int, device, training: bool, ctx):
+        self.net, self.B, self.A, self.training, self.device = net, int(B), net.A, training, device
+        self.valid = self.B * self.A
+        self.rows = -(-self.valid // 32) * 32
+        self.nblk = max(1, min(256, self.rows // 32))
+        self.prod = GenericNet(GenericMLPTorso([net.D]), net.D, [])  # the product launches of the general layer path
+        self.prod.ctx = ctx
+        self.bufs: List[_Buf] = []
+        if training:
+            self.slabs = torch.zeros((self.nblk, 128 * 128 + 128 + 8), device=device)
+            self.ln_slab = torch.zeros((self.nblk, 2 * max(net.O, net.D)), device=device)
+
+    def buf(self, N: int, ld: Optional[int] = None) -> _Buf:
+        b = _Buf(self.rows, N, self.device, ld)
+        self.bufs.append(b)
+        return b
+
+    def _p(self, flat: torch.Tensor, path: Tuple[str, ...], n: int) -> torch.Tensor:
+        o = self.net.off[path]
+        return flat[o : o + n]
+
+    # ---- layers: (forward closure, backward closure) pairs appended to a tape
+    def dense(self, tape, x: _Buf, path: Tuple[str, ...], K: int, N: int, bias: bool = True, x_grad: bool = True) -> _Buf:
+        y = self.buf(N)
+        wp, bp = path + ("kernel",), path + ("bias",)
+
+        def fwd(flat):
+            self.prod._dense(x.t.data_ptr(), x.ld, K, self._p(flat, wp, K * N), self._p(flat, bp, N) if bias else None, y.t, N,
+                             self.rows, what="mat_dense")
+
+        def bwd(flat, g, inv):
+            self.prod._xty(x.t.data_ptr(), x.ld, K, y.grad, N, self.rows, self.slabs, self._p(g, wp, K * N),
+                           self._p(g, bp, N) if bias else None, inv, False)
+            if not x_grad:
+                return
+            wt = self._p(flat, wp, K * N).view(K, N).t().contiguous()
+            first = x.grad is None
+            if first:
+                x.grad = x.own()
+            self.prod._dense(y.grad.data_ptr(), N, N, wt, None, x.grad, K, self.rows, accumulate=not first, what="mat_dense_bwd")
+
+        tape.append((fwd, bwd))
+        return y
+
+    def ln(self, tape, x: _Buf, res: Optional[_Buf], path: Tuple[str, ...], N: int) -> _Buf:
+        y = self.buf(N)
+        xhat = torch.zeros(self.rows * N, device=self.device) if self.training else None
+        rstd = torch.zeros(self.rows, device=self.device) if self.training else None
+        sp, bp = path + ("scale",), path + ("bias",)
+        L = lib()
+
+        def fwd(flat):
+            launch("mat_ln", L.mava_mat_ln_fwd_f32, ptr(x.t), ptr(res.t) if res is not None else None, ptr(self._p(flat, sp, N)),
+                   ptr(self._p(flat, bp, N)), N, self.rows, self.valid, ptr(y.t), ptr(xhat), ptr(rstd), self.nblk, stream_ptr())
+
+        def bwd(flat, g, inv):
+            assert x.grad is None, "a LayerNorm's main input has one consumer"
+            x.grad = x.own()
+            launch("mat_ln_bwd", L.mava_mat_ln_bwd_f32, ptr(y.grad), ptr(xhat), ptr(rstd), ptr(self._p(flat, sp, N)), N, self.rows,
+                   self.valid, inv, ptr(x.grad), ptr(self.ln_slab), self.ln_slab.shape[1], self.ln_slab.shape[0], stream_ptr())
+            ops.slab_reduce(self.ln_slab, N, self._p(g, sp, N))
+            ops.slab_reduce_cols(self.ln_slab, N, N, self._p(g, bp, N))
+            if res is not None:
+                if res.grad is None:
+                    res.grad = x.grad  # d(x + res): one buffer serves both (x's producer reads it before res's others add)
+                else:
+                    res.grad.add_(x.grad)
+
+        tape.append((fwd, bwd))
+        return y
+
+    def gelu(self, tape, x: _Buf) -> _Buf:
+        y = self.buf(x.N)
+        n = self.rows * x.N
+        L = lib()
+
+        def fwd(flat):
+            launch("mat_gelu", L.mava_mat_gelu_f32, ptr(x.t), n, ptr(y.t), stream_ptr())
+
+        def bwd(flat, g, inv):
+            assert x.grad is None
+            x.grad = x.own()
+            launch("mat_gelu_bwd", L.mava_mat_gelu_bwd_f32, ptr(y.grad), ptr(x.t), n, ptr(x.grad), stream_ptr())
+
+        tape.append((fwd, bwd))
+        return y
+
+    def attention(self, tape, q_in: _Buf, kv_in: _Buf, path: Tuple[str, ...], causal: bool) -> _Buf:
+        D, H, A = self.net.D, self.net.H, self.A
+        q = self.dense(tape, q_in, path + ("query",), D, D)
+        k = self.dense(tape, kv_in, path + ("key",), D, D)
+        v = self.dense(tape, kv_in, path + ("value",), D, D)
+        y = self.buf(D)
+        L = lib()
+
+        def fwd(flat):
+            launch("mat_attn", L.mava_mat_attn_fwd_f32, ptr(q.t), ptr(k.t), ptr(v.t), self.rows, D, self.B, A, H, int(causal), ptr(y.t),
+                   None, self.nblk, stream_ptr())
+
+        def bwd(flat, g, inv):
+            for b in (q, k, v):
+                assert b.grad is None
+                b.grad = b.own()
+            launch("mat_attn_bwd", L.mava_mat_attn_bwd_f32, ptr(y.grad), ptr(q.t), ptr(k.t), ptr(v.t), self.rows, D, self.B, A, H,
+                   int(causal), ptr(q.grad), ptr(k.grad), ptr(v.grad), self.nblk, stream_ptr())
+
+        tape.append((fwd, bwd))
+        return self.dense(tape, y, path + ("proj",), D, D)
+
+    def mlp(self, tape, x: _Buf, base: Tuple[str, ...]) -> _Buf:
+        D = self.net.D
+        return self.dense(tape, self.gelu(tape, self.dense(tape, x, base + ("mlp_0",), D, D)), base + ("mlp_1",), D, D)
+
+    def head(self, tape, x: _Buf, base: Tuple[str, ...], n_out: int) -> _Buf:
+        D = self.net.D
+        h = self.ln(tape, self.gelu(tape, self.dense(tape, x, base + ("head_dense",), D, D)), None, base + ("head_ln",), D)
+        return self.dense(tape, h, base + ("head_out",), D, n_out)
+
+
+class MATPass(_Graph):
+    """Encoder and decoder tapes for B samples, with the gathered observations and the shifted one-hot as inputs."""
+
+    def __init__(self, net: MATNet, B: int, device, training: bool, ctx):
+        super().__init__(net, B, device, training, ctx)
+        O, nA, D = net.O, net.nA, net.D
+        self.Np = -(-(nA + 1) // 32) * 32
+        self.obs = self.buf(O)
+        self.onehot = self.buf(nA + 1, ld=self.Np)
+        # sample ids of the rows, padded with sample 0 so that the gather of the padding rows stays inside the source
+        self.idx = torch.zeros(-(-self.rows // self.A) + 1, dtype=torch.int32, device=device)
+        enc: list = []
+        e = self.gelu(enc, self.dense(enc, self.ln(enc, self.obs, None, ("encoder", "obs_ln"), O), ("encoder", "obs_dense"), O, D))
+        x = self.ln(enc, e, None, ("encoder", "ln"), D)
+        for i in range(net.n_block):
+            b = ("encoder", f"block_{i}")
+            x = self.ln(enc, self.attention(enc, x, x, b + ("attn",), False), x, b + ("ln1",), D)
+            x = self.ln(enc, self.mlp(enc, x, b), x, b + ("ln2",), D)
+        self.rep = x
+        self.value = self.head(enc, x, ("encoder",), 1)
+        dec: list = []
+        x = self.ln(dec, self.gelu(dec, self.dense(dec, self.onehot, ("decoder", "act_dense"), nA + 1, D, bias=False, x_grad=False)), None,
+                    ("decoder", "ln"), D)
+        for i in range(net.n_block):
+            b = ("decoder", f"block_{i}")
+            x = self.ln(dec, self.attention(dec, x, x, b + ("attn1",), True), x, b + ("ln1",), D)
+            x = self.ln(dec, self.attention(dec, self.rep, x, b + ("attn2",), True), self.rep, b + ("ln2",), D)
+            x = self.ln(dec, self.mlp(dec, x, b), x, b + ("ln3",), D)
+        self.logits = self.head(dec, x, ("decoder",), nA)
+        self.enc, self.dec = enc, dec
+
+    def gather_obs(self, agents_view: torch.Tensor, n_samples: int) -> None:
+        """agents_view: (n_samples, A, O) row-major; row b * A + j of the pass reads sample idx[b]."""
+        net = self.net
+        launch("mat_gather", lib().mava_rec_gather_t32_f32, ptr(agents_view), ptr(self.idx), self.rows, n_samples, net.A, 1, net.O, net.O,
+               self.rows, net.O, ptr(self.obs.t), stream_ptr())
+
+    def shift_onehot(self, action: torch.Tensor, known: int, use_idx: bool) -> None:
+        launch("mat_onehot", lib().mava_mat_shift_onehot_f32, ptr(action), ptr(self.idx) if use_idx else None, self.B, self.A,
+               self.net.nA, known, self.rows, self.Np, ptr(self.onehot.t), stream_ptr())
+
+    def encode(self, flat: torch.Tensor) -> None:
+        for fwd, _ in self.enc:
+            fwd(flat)
+
+    def decode(self, flat: torch.Tensor) -> None:
+        for fwd, _ in self.dec:
+            fwd(flat)
+
+    def backward(self, flat: torch.Tensor, g: torch.Tensor, dlogits: torch.Tensor, dvalues: torch.Tensor, grad_scale: float) -> None:
+        for b in self.bufs:
+            b.grad = None
+        self.logits.grad, self.value.grad = dlogits, dvalues
+        inv = 1.0 / grad_scale
+        for _, bwd in reversed(self.enc + self.dec):
+            bwd(flat, g, inv)
+
+    def act(self, flat: torch.Tensor, agents_view: torch.Tensor, mask: torch.Tensor, action: torch.Tensor, log_prob: torch.Tensor,
+            seed: int, step: int, row_offset: int, greedy: bool, value_out: Optional[torch.Tensor] = None) -> None:
+        """One env step for the B samples of (B, A, O) agents_view: encoder, then A decoder passes; pass i samples agent i.
+        Launches: 1 + len(enc) + A * (2 + len(dec)) (+ 1 copy of the values)."""
+        self.gather_obs(agents_view, self.B)
+        self.encode(flat)
+        if value_out is not None:
+            value_out.view(-1).copy_(self.value.t[: self.valid])
+        for i in range(self.A):
+            self.shift_onehot(action, i, False)
+            self.decode(flat)
+            launch("mat_sample", lib().mava_mat_sample_f32, self.B, self.A, i, self.net.nA, ptr(self.logits.t), ptr(mask),
+                   seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action), ptr(log_prob), stream_ptr())
+
+
+class _MATPolicy:
+    """What MATActor.apply returns: the evaluator calls mode() or sample(seed=generator); either runs the autoregressive
+    decode on the learner's acting path."""
+
+    def __init__(self, actor: "MATActor", flat: torch.Tensor, observation):
+        self.actor, self.flat, self.observation = actor, flat, observation
+
+    def _run(self, greedy: bool, seed: int) -> torch.Tensor:
+        return self.actor.act(self.flat, self.observation, greedy, seed)
+
+    def mode(self) -> torch.Tensor:
+        return self._run(True, 0)
+
+    def sample(self, seed: Optional[torch.Generator] = None) -> torch.Tensor:
+        s = int(torch.randint(0, 2**62, (1,), generator=seed, device=seed.device if seed is not None else "cpu").item())
+        return self._run(False, s)
+
+
+class MATActor:
+    """actor_network of the system: apply(params, observation) -> a policy over the joint action (E, A)."""
+
+    def __init__(self, net: MATNet, ctx, device):
+        self.net, self.ctx, self.device = net, ctx, device
+        self._passes: Dict[int, MATPass] = {}
+        self._flat = torch.zeros(net.num_params, device=device)
+        self._calls = 0
+
+    def pass_for(self, B: int) -> MATPass:
+        if B not in self._passes:
+            p = MATPass(self.net, B, self.device, False, self.ctx)
+            p.idx[:B].copy_(torch.arange(B, dtype=torch.int32))
+            self._passes[B] = p
+        return self._passes[B]
+
+    def apply(self, params: Any, observation) -> _MATPolicy:
+        flat = params if isinstance(params, torch.Tensor) else self.net.flat_from_tree(params, self._flat)
+        return _MATPolicy(self, flat, observation)
+
+    def act(self, flat: torch.Tensor, observation, greedy: bool, seed: int) -> torch.Tensor:
+        av = observation.agents_view
+        B = int(av.shape[0])
+        av = av.reshape(B, self.net.A, self.net.O).float().contiguous()
+        mask = observation.action_mask.reshape(B, self.net.A, self.net.nA).to(torch.uint8).contiguous()
+        action = torch.zeros((B, self.net.A), dtype=torch.int32, device=av.device)
+        log_prob = torch.zeros((B, self.net.A), device=av.device)
+        self.pass_for(B).act(flat, av, mask, action, log_prob, seed, self._calls, 0, greedy)
+        self._calls += 1
+        return action
+
+
+class MATLearner:
+    def __init__(self, env, config, device: Optional[torch.device] = None):
+        self.config = config
+        s, arch, net = config.system, config.arch, config.network
+        self.rank, self.world = parallel.rank_world()
+        head = net.get("action_head", None) or {}
+        self.D, self.H, self.n_block = int(net.get("n_embd", 64)), int(net.get("n_head", 1)), int(net.get("n_block", 1))
+        check_supported(num_agents=int(env.num_agents), n_actions=int(env.action_dim), n_embd=self.D, n_head=self.H,
+                        continuous="ContinuousActionHead" in str(dict(head).get("_target_", "")), world=self.world,
+                        update_batch_size=int(s.update_batch_size))
+        if self.n_block < 1:
+            raise ValueError(f"network.n_block must be >= 1, got {self.n_block}")
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.E, self.U, self.T = int(arch.num_envs), 1, int(s.rollout_length)
+        self.K, self.M = int(s.ppo_epochs), int(s.num_minibatches)
+        if (self.T * self.E) % self.M:
+            raise ValueError("rollout_length * num_envs must be divisible by num_minibatches")
+        if env.num_envs != self.E:
+            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
+        self.n_upd = int(s.get("num_updates_per_eval", 1))
+        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
+        if self.matmul_mode not in ("f16x2", "f32"):
+            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
+        self.ctx = ops.Ctx(self.matmul_mode)
+        rep_env = env.clone(env_offset=getattr(env, "env_offset", 0))
+        self.rep = _Replica(rep_env, self.T, self.n_upd, False, self.device, False)
+        self.reps = [self.rep]
+        self.A, self.nA, self.O = rep_env.num_agents, rep_env.action_dim, rep_env.obs_dim  # (image observations: their flat row)
+        if self.O > 1024:
+            raise MavaHipError(f"ff_mat: observations of up to 1024 features (mava_rec_gather_t32_f32), got {self.O}")
+        config.system.num_agents = self.A
+        self.net = MATNet(self.O, self.nA, self.A, self.D, self.H, self.n_block)
+        self.P = self.net.num_params
+        d = self.device
+        self.p, self.m, self.v = (torch.zeros(self.P, device=d) for _ in range(3))
+        self.g = torch.zeros(self.P + 4, device=d)  # [gradient | actor_loss, entropy, value_loss, pad]
+        self.count = torch.zeros(2, dtype=torch.int32, device=d)
+        # actor_lr is the single learning rate of the one Adam; critic_lr is accepted and unused (encoder and decoder
+        # share one optimiser, as upstream MAT does)
+        self.lr = float(s.actor_lr)
+        self.Bm = self.T * self.E // self.M  # (t, env) samples per minibatch
+        self.actor_network = MATActor(self.net, self.ctx, d)
+        self.roll = self.actor_network.pass_for(self.E)
+        self.train = MATPass(self.net, self.Bm, d, True, self.ctx)
+        rows = self.train.rows
+        self.grad_scale = float(2 ** math.ceil(math.log2(rows)))
+        self.dlogits = torch.zeros(rows * self.nA, device=d)
+        self.dvalues = torch.zeros(rows, device=d)
+        self.loss_blocks = max(1, min(256, -(-rows // 256)))
+        self.partials = torch.zeros((self.loss_blocks, 3), device=d)
+        self.stats = torch.zeros((lib().mava_adv_stats_blocks(), 2), dtype=torch.float64, device=d)
+        self.train_metrics = torch.zeros((self.n_upd, self.K, self.M, 4), device=d)
+        self.perm_count = 0
+        self.t_global = 0
+        self.seed = int(s.seed)
+        self._learn_calls = 0
+        self.debug: Optional[Dict[str, list]] = None  # tests: {"grads": [], "perms": [], "state": []} records every minibatch (and "slot0")
+
+    # ------------------------------------------------------------------------------------ setup
+    def init_params(self, seed: int) -> None:
+        self.p.copy_(self.net.init_flat(seed))
+        self.m.zero_()
+        self.v.zero_()
+        self.count.zero_()
+
+    def reset_envs(self) -> None:
+        rep = self.rep
+        rep.env.step_into(rep.state, 0, rep.obs_slot(0), is_reset=True)
+        self.t_global = 0
+        self.perm_count = 0
+
+    # ---------------------------------------------------------------------------- state views
+    def learner_state(self) -> LearnerState:
+        lead, rep = (1, 1), self.rep
+        opt = AdamState(self.count[0].expand(1, 1), self.net.tree(self.m, lead), self.net.tree(self.v, lead))
+        key = torch.tensor([[[self.seed, self.t_global]]], dtype=torch.int64)
+        st = lambda t: t.unsqueeze(0).unsqueeze(0)
+        obs = Observation(st(rep.agents_view[0]), st(rep.action_mask[0]).bool(), st(rep.step_count[0]))
+        done = st(rep.last_done)
+        ts = TimeStep(torch.where(done[..., 0].bool(), 2, 1).to(torch.int8), st(rep.last_reward), 1.0 - done.float(), obs, {})
+        env_state = {"step_count": st(rep.state.step_count), "episode_return": st(rep.state.ep_return),
+                     "episode_length": st(rep.state.ep_length)}
+        return LearnerState(self.net.tree(self.p, lead), opt, key, env_state, ts)
+
+    def adopt(self, state: LearnerState) -> None:
+        leaf = self.net.first_leaf(state.params)
+        if not isinstance(leaf, torch.Tensor) or leaf.data_ptr() != self.p.data_ptr():
+            to = lambda tree: _tree_to(tree, self.p.device)
+            self.net.flat_from_tree(to(state.params), self.p)
+            self.net.flat_from_tree(to(state.opt_states.mu), self.m)
+            self.net.flat_from_tree(to(state.opt_states.nu), self.v)
+            self.count[0] = int(torch.as_tensor(state.opt_states.count).reshape(-1)[0])
+
+    # ------------------------------------------------------------------------------------ update
+    def _rollout(self, n: int) -> None:
+        rep, T = self.rep, self.T
+        for t in range(T):
+            step = self.t_global + t
+            self.roll.act(self.p, rep.agents_view[t], rep.action_mask[t], rep.action[t], rep.log_prob[t], self.seed, step, 0, False,
+                          value_out=rep.value[t])
+            rep.env.step_into(rep.state, step + 1, rep.obs_slot(t + 1), rep.reward[t], rep.done[t], rep.info_return[n, t],
+                              rep.info_length[n, t], rep.info_terminal[n, t], action=rep.action[t])
+        rep.last_reward.copy_(rep.reward[T - 1])
+        rep.last_done.copy_(rep.done[T - 1])
+        self.t_global += T
+
+    def _bootstrap_and_gae(self) -> None:
+        s, rep, T, EA = self.config.system, self.rep, self.T, self.E * self.A
+        self.roll.gather_obs(rep.agents_view[T], self.E)
+        self.roll.encode(self.p)
+        rep.last_val.view(-1).copy_(self.roll.value.t[:EA])
+        ops.gae(rep.reward.view(T, EA), rep.value.view(T, EA), rep.done.view(T, EA), rep.last_val.view(EA), float(s.gamma),
+                float(s.gae_lambda), out=(rep.adv.view(T, EA), rep.tgt.view(T, EA)), ctx=self.ctx)
+
+    def _minibatch(self, n: int, k: int, mb: int, perm: torch.Tensor) -> None:
+        s, rep, tr, T, Bm = self.config.system, self.rep, self.train, self.T, self.Bm
+        if self.debug is not None:
+            self.debug["state"].append((self.p.clone(), self.m.clone(), self.v.clone()))
+        tr.idx[:Bm].copy_(perm[mb * Bm : (mb + 1) * Bm])
+        tr.gather_obs(rep.agents_view[:T], T * self.E)
+        tr.shift_onehot(rep.action, self.A - 1, True)
+        tr.encode(self.p)
+        tr.decode(self.p)
+        ops.adv_stats(rep.adv.view(-1), tr.idx, 0, Bm, self.A, out=self.stats)
+        launch("mat_loss", lib().mava_mat_loss_f32, Bm, self.A, self.nA, tr.rows, ptr(tr.idx), ptr(tr.logits.t), ptr(tr.value.t),
+               ptr(rep.action_mask[:T]), ptr(rep.action), ptr(rep.log_prob), ptr(rep.adv), ptr(rep.value), ptr(rep.tgt), ptr(self.stats),
+               self.stats.shape[0], float(s.clip_eps), float(s.ent_coef), float(s.vf_coef), self.grad_scale, ptr(self.dlogits),
+               ptr(self.dvalues), ptr(self.partials), self.loss_blocks, stream_ptr())
+        ops.slab_reduce(self.partials, 3, self.g[self.P : self.P + 3])
+        tr.backward(self.p, self.g, self.dlogits, self.dvalues, self.grad_scale)
+        if self.debug is not None:
+            self.debug["grads"].append(self.g.clone())
+        ops.clip_adam(self.p, self.g, self.m, self.v, self.count, [0, self.P], [self.lr], grad_scale=1.0,
+                      max_norm=float(s.max_grad_norm), decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
+                      num_updates=int(s.get("num_updates", 1) or 1), loss_sums=self.g[self.P :], vf_coef=float(s.vf_coef),
+                      ent_coef=float(s.ent_coef), metrics_out=self.train_metrics[n, k, mb])
+
+    def update(self, n: int) -> None:
+        self._rollout(n)
+        self._bootstrap_and_gae()
+        for k in range(self.K):
+            perm = ops.permutation(self.T * self.E, self.seed, self.perm_count)
+            self.perm_count += 1
+            if self.debug is not None:
+                self.debug["perms"].append(perm.clone())
+            for mb in range(self.M):
+                self._minibatch(n, k, mb, perm)
+        rep = self.rep
+        if self.debug is not None:  # slot 0 of the trajectory is about to become the next rollout's first observation
+            self.debug["slot0"] = (rep.agents_view[0].clone(), rep.action_mask[0].clone())
+        for buf in (rep.agents_view, rep.global_state, rep.action_mask, rep.step_count):
+            buf[0].copy_(buf[self.T])
+
+    def learn(self, learner_state: LearnerState) -> ExperimentOutput:
+        self.adopt(learner_state)
+        if self.matmul_mode == "f16x2":
+            check_f16_range(self.p, [self.rep.agents_view[0]], self.train_metrics if self._learn_calls else None, type(self).__name__)
+        self._learn_calls += 1
+        for n in range(self.n_upd):
+            self.update(n)
+        rep = self.rep
+        episode_metrics = {"episode_return": rep.info_return.unsqueeze(1).unsqueeze(0),
+                           "episode_length": rep.info_length.unsqueeze(1).unsqueeze(0),
+                           "is_terminal_step": rep.info_terminal.unsqueeze(1).unsqueeze(0).bool()}
+        tm = self.train_metrics.unsqueeze(1).unsqueeze(0)
+        train_metrics = {"total_loss": tm[..., 0], "value_loss": tm[..., 1], "actor_loss": tm[..., 2], "entropy": tm[..., 3]}
+        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
+
+
+def _tree_to(tree: Any, device) -> Any:
+    if isinstance(tree, torch.Tensor):
+        return tree.to(device)
+    if isinstance(tree, dict):
+        return {k: _tree_to(v, device) for k, v in tree.items()}
+    return tree
+
+
+def learner_setup(env, keys, config, device=None):
+    """(learn, actor_network, initial LearnerState), as mava_amd/learner.py::learner_setup; keys[1] seeds the parameters."""
+    key, net_key = int(keys[0]), int(keys[1])
+    learner = MATLearner(env, config, device)
+    learner.seed = key
+    learner.init_params(net_key)
+    learner.reset_envs()
+
+    def learn(learner_state: LearnerState) -> ExperimentOutput:
+        return learner.learn(learner_state)
+
+    learn.learner = learner  # type: ignore[attr-defined]
+    return learn, learner.actor_network, learner.learner_state()
