@@ -17,19 +17,20 @@ env row holds max(min_buffer_size, sample_sequence_length + 1) steps, and t_trai
 from __future__ import annotations
 
 import math
-import os
-from typing import Any, Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
-from . import ops, parallel
+from . import ops
 from ._lib import launch, lib, ptr, stream_ptr
-from .guards import check_f16_range
 from .learner import NUM_CU
+from .learner_common import bind_learn
 from .networks import MLPTorso
+from .replay_learner import ReplayLearner
 from .rec_networks import H, RecQNetwork, RecWorkspace, t32_to_rows
 from .systems.q_learning.types import LearnerState, QNetParams, Transition
-from .types import AdamState, ExperimentOutput, Observation
+from .types import AdamState, Observation
+from .utils.tree import tree_to
 
 
 def _default_torso(c) -> bool:
@@ -43,16 +44,10 @@ def epsilon(t: int, eps_min: float, eps_decay: float) -> float:
     return max(float(eps_min), 1.0 - (float(t) / float(eps_decay)) * (1.0 - float(eps_min)))
 
 
-class IQLLearner:
-    def __init__(self, env, config, device: Optional[torch.device] = None):
-        self.config = config
-        s, arch = config.system, config.arch
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.rank, self.world = parallel.rank_world()
-        if self.world > 1:
-            raise NotImplementedError("rec_iql runs on one device (multi-GPU is not implemented)")
-        if int(s.update_batch_size) != 1:
-            raise NotImplementedError("rec_iql supports update_batch_size == 1 only")
+class IQLLearner(ReplayLearner):
+    name = "rec_iql"
+
+    def _refuse(self, env, config) -> None:
         net = config.network
         if int(net.get("hidden_state_dim", 128)) != H:
             raise ValueError(f"rec_iql needs network.hidden_state_dim == {H} (the fused acting step and the scans)")
@@ -62,31 +57,24 @@ class IQLLearner:
         if not getattr(env, "emits_real_next_obs", False):
             raise ValueError(f"rec_iql needs an environment that returns its pre-reset observation (env=lbf); "
                              f"{type(env).__name__} does not")
-        self.E, self.T, self.K = int(arch.num_envs), int(s.rollout_length), int(s.epochs)
-        if env.num_envs != self.E:
-            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
+
+    def _buffer_sizes(self, s) -> None:
         self.B, self.L = int(s.sample_batch_size), int(s.sample_sequence_length)
         self.S = self.L + 1  # rec_iql.py:167: sample_sequence_length + 1 consecutive steps
         self.cap = int(s.buffer_size)
         if self.cap < self.S:
             raise ValueError(f"buffer_size={self.cap} cannot hold a window of sample_sequence_length + 1 = {self.S} steps")
         self.min_fill = max(int(s.min_buffer_size), self.S)
-        self.n_upd = int(s.get("num_updates_per_eval", 1))
-        self.env = env
-        self.A, self.nA, self.O = env.num_agents, env.action_dim, env.obs_dim
-        config.system.num_agents = self.A
+
+    def __init__(self, env, config, device: Optional[torch.device] = None):
+        super().__init__(env, config, device)  # the shared refusals, then the two hooks above, then the scaffolding
+        s, qn = config.system, config.network.get("q_network", None)
+        self.nA = env.action_dim
         E, A, O, nA = self.E, self.A, self.O, self.nA
-        self.EA = E * A
-        self.Rpa = -(-self.EA // 32) * 32          # acting rows, padded to the kernels' 32-row tiles
-        self.Rp = -(-(self.B * A) // 32) * 32      # sampled rows per time step
-        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
-        if self.matmul_mode not in ("f16x2", "f32"):
-            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
-        self.ctx = ops.Ctx(self.matmul_mode)
         cfg = lambda c: {k: v for k, v in dict(c).items() if k != "_target_"}
         self.q_network = RecQNetwork(MLPTorso(**cfg(qn["pre_torso"])), MLPTorso(**cfg(qn["post_torso"])), nA, O)
         self.q_network.ctx = self.ctx
-        P = self.P = self.q_network.num_params
+        P = self.P = self.Pq = self.q_network.num_params  # (a subclass appends its own parameters after the first Pq)
         d = self.device
         # online / target parameters, Adam moments (optax.chain(clip_by_global_norm, adam(q_lr, eps=1e-5)), :136-140)
         self.p, self.pt = torch.zeros(P, device=d), torch.zeros(P, device=d)
@@ -106,11 +94,6 @@ class IQLLearner:
         self.real_mask = torch.zeros((E, A, nA), dtype=u8, device=d)
         self.gs = torch.empty((E, 1, env.state_dim), device=d)
         self.sc = [torch.zeros((E, A), dtype=torch.int32, device=d) for _ in range(2)]
-        self.state = env.alloc_state()
-        self.cur = 0
-        self.info_return = torch.zeros((self.n_upd, self.T, E), device=d)
-        self.info_length = torch.zeros((self.n_upd, self.T, E), dtype=torch.int32, device=d)
-        self.info_terminal = torch.zeros((self.n_upd, self.T, E), dtype=u8, device=d)
         # ---- replay buffer: every field (E, capacity, A, ...), allocated once (size)
         cap = self.cap
         self.buf = Transition(obs=(torch.zeros((E, cap, A, O), device=d), torch.zeros((E, cap, A, nA), dtype=u8, device=d)),
@@ -147,12 +130,9 @@ class IQLLearner:
         self.hard_update, self.update_period = bool(s.hard_update), int(s.update_period)
         self.q_lr, self.max_grad_norm = float(s.q_lr), float(s.max_grad_norm)
         self.eps_min, self.eps_decay = float(s.eps_min), float(s.eps_decay)
-        self.t_act = 0       # env steps taken (num_envs per act step): the epsilon schedule's t
-        self.act_steps = 0   # act steps taken: Philox counter of the exploration draws
-        self.n_added = 0     # steps stored per env row
-        self.t_train = 0     # train steps taken (optax.periodic_update's step; sampler counter)
-        self._learn_calls = 0
-        self.debug: Optional[Dict[str, List[torch.Tensor]]] = None  # tests: {"grads", "pairs", "actions"} clones when set
+        # env steps taken (num_envs per act step): the epsilon schedule's t.  Of the base's counters, n_added counts the
+        # steps stored per env row and t_train is optax.periodic_update's step too; debug takes {"grads", "pairs", "actions"}
+        self.t_act = 0
 
     # ------------------------------------------------------------------------------------ setup
     def init_params(self, q_seed: int) -> None:
@@ -170,8 +150,7 @@ class IQLLearner:
 
     def reset_envs(self) -> None:
         """rec_iql.py:178-190: first observation, terminal / term_or_trunc False, zero hidden state."""
-        self.cur = 0
-        self.env.step_into(self.state, 0, self._obs_slot(0), is_reset=True)
+        super().reset_envs()
         for t in self.tot + self.term + self.h:
             t.zero_()
 
@@ -193,8 +172,8 @@ class IQLLearner:
         if self.debug is not None:
             self.debug["actions"].append(act.clone())
         self.env.step_into(self.state, self.act_steps + 1, self._obs_slot(nx), self.reward, self.tot[nx][:EA].view(E, A),
-                           self.info_return[n, t], self.info_length[n, t], self.info_terminal[n, t], action=act,
-                           real_obs={"agents_view": self.real_view, "action_mask": self.real_mask}, terminated=self.term[nx])
+                           *self._info(n, t), action=act, real_obs={"agents_view": self.real_view, "action_mask": self.real_mask},
+                           terminated=self.term[nx])
         b = self.buf
         launch("replay_add", L_.mava_replay_add_f32, E, A, self.O, self.nA, self.cap, self.n_added % self.cap,
                ptr(self.view[c]), ptr(self.mask[c]), ptr(self.action), ptr(self.reward), ptr(self.term[c]), ptr(self.tot[c]),
@@ -205,31 +184,44 @@ class IQLLearner:
         self.t_act += E
         self.act_steps += 1
 
-    def _train_step(self, n: int, k: int) -> None:
-        """rec_iql.py:325-463: sample, three passes, double-Q TD loss, clip + Adam, target update."""
-        L_, s = lib(), stream_ptr()
-        Lq, Rp, net = self.L, self.Rp, self.q_network
+    def _sample_batch(self) -> None:
+        """rec_iql.py:325-340: B windows of S consecutive steps into `smp`, time-major."""
         b, sm = self.buf, self.smp
-        launch("replay_sample", L_.mava_replay_sample_f32, self.E, self.A, self.O, self.nA, self.cap, self.n_added, self.B, self.S,
-               Rp, self.seed & (2**64 - 1), self.t_train & 0xFFFFFFFF, ptr(b.obs[0]), ptr(b.obs[1]), ptr(b.action),
+        launch("replay_sample", lib().mava_replay_sample_f32, self.E, self.A, self.O, self.nA, self.cap, self.n_added, self.B,
+               self.S, self.Rp, self.seed & (2**64 - 1), self.t_train & 0xFFFFFFFF, ptr(b.obs[0]), ptr(b.obs[1]), ptr(b.action),
                ptr(b.reward), ptr(b.terminal), ptr(b.term_or_trunc), ptr(b.next_obs[0]), ptr(b.next_obs[1]), ptr(sm.obs[0]),
                ptr(sm.obs[1]), ptr(sm.action), ptr(sm.reward), ptr(sm.terminal), ptr(sm.term_or_trunc), ptr(sm.next_obs[0]),
-               ptr(sm.next_obs[1]), ptr(self.pairs), s)
+               ptr(sm.next_obs[1]), ptr(self.pairs), stream_ptr())
         if self.debug is not None:
             self.debug["pairs"].append(self.pairs.clone())
-        # data_first = [:, :-1], data_next = [:, 1:] (:375-388); the padded batch is Rp single-agent envs, identity idx
+
+    def _q_passes(self, pq: torch.Tensor, pqt: torch.Tensor):
+        """The three recurrent passes from a zero hidden state: online Q on obs (kept for the backward pass), online and
+        target Q on next_obs (the target's into q_target).  data_first = [:, :-1], data_next = [:, 1:] (:375-388); the
+        padded batch is Rp single-agent envs, identity idx."""
+        Lq, Rp, net, sm = self.L, self.Rp, self.q_network, self.smp
         obs, next_obs = sm.obs[0], sm.next_obs[0]
         tot_first, tot_next = sm.term_or_trunc[:Lq], sm.term_or_trunc[1:]
-        q = net.forward_sequence(self.p, self.ws, obs, 1, tot_first, self.h0, True, None, Lq, Rp, Rp, 1, training=True)
-        qn = net.forward_sequence(self.p, self.ws_next, next_obs, 1, tot_next, self.h0, True, None, Lq, Rp, Rp, 1, training=False)
-        net.forward_sequence(self.pt, self.ws_next, next_obs, 1, tot_next, self.h0, True, None, Lq, Rp, Rp, 1, training=False,
+        q = net.forward_sequence(pq, self.ws, obs, 1, tot_first, self.h0, True, None, Lq, Rp, Rp, 1, training=True)
+        qn = net.forward_sequence(pq, self.ws_next, next_obs, 1, tot_next, self.h0, True, None, Lq, Rp, Rp, 1, training=False)
+        net.forward_sequence(pqt, self.ws_next, next_obs, 1, tot_next, self.h0, True, None, Lq, Rp, Rp, 1, training=False,
                              y_out=self.q_target)
-        launch("q_td_loss", L_.mava_q_td_loss_f32, Lq, Rp, self.nA, self.B * self.A, ptr(q), ptr(qn), ptr(self.q_target),
-               ptr(sm.action), ptr(sm.reward), ptr(sm.terminal[1:]), ptr(sm.next_obs[1]), self.gamma, self.grad_scale,
-               ptr(self.ws.dy), ptr(self.partials), self.loss_blocks, s)
+        return q, qn
+
+    def _loss(self, n: int, k: int, q: torch.Tensor, qn: torch.Tensor) -> None:
+        """The double-Q TD loss per agent (:390-411): dLoss/dQ into ws.dy, the metrics into train_metrics[n, k]."""
+        sm = self.smp
+        launch("q_td_loss", lib().mava_q_td_loss_f32, self.L, self.Rp, self.nA, self.B * self.A, ptr(q), ptr(qn),
+               ptr(self.q_target), ptr(sm.action), ptr(sm.reward), ptr(sm.terminal[1:]), ptr(sm.next_obs[1]), self.gamma,
+               self.grad_scale, ptr(self.ws.dy), ptr(self.partials), self.loss_blocks, stream_ptr())
         ops.slab_reduce(self.partials, 3, self.train_metrics[n, k])
-        net.backward_sequence(self.p, self.ws, obs, 1, tot_first, None, Lq, Rp, Rp, 1, self.slabs, self.g, accumulate=False,
-                              grad_scale=self.grad_scale)
+
+    def _backward_and_apply(self, pq: torch.Tensor) -> None:
+        """The Q network's backward pass into g[:Pq], clip + Adam over all P parameters, then the target update."""
+        L_, s = lib(), stream_ptr()
+        Lq, Rp, sm = self.L, self.Rp, self.smp
+        self.q_network.backward_sequence(pq, self.ws, sm.obs[0], 1, sm.term_or_trunc[:Lq], None, Lq, Rp, Rp, 1, self.slabs,
+                                         self.g[: self.Pq], accumulate=False, grad_scale=self.grad_scale)
         if self.debug is not None:
             self.debug["grads"].append(self.g.clone())
         ops.clip_adam(self.p, self.g, self.m, self.v, self.count, [0, self.P], [self.q_lr], grad_scale=1.0,
@@ -240,6 +232,15 @@ class IQLLearner:
         else:  # optax.incremental_update(new, old, tau)
             launch("target_update", L_.mava_target_update_f32, self.P, ptr(self.p), ptr(self.pt), self.tau, 0, s)
         self.t_train += 1
+
+    def _train_step(self, n: int, k: int) -> None:
+        """rec_iql.py:325-463: sample, three passes, the TD loss (a subclass mixes the agents' Q-values in its own),
+        clip + Adam, target update."""
+        self._sample_batch()
+        pq = self.p[: self.Pq]
+        q, qn = self._q_passes(pq, self.pt[: self.Pq])
+        self._loss(n, k, q, qn)
+        self._backward_and_apply(pq)
 
     def can_train(self) -> bool:
         """The train gate: every env row holds max(min_buffer_size, sample_sequence_length + 1) steps."""
@@ -264,13 +265,9 @@ class IQLLearner:
         obs = Observation(self.view[c][:EA].view(1, 1, E, A, self.O), self.mask[c][:EA].view(1, 1, E, A, self.nA).bool(),
                           self.sc[c].view(1, 1, E, A))
         hs = t32_to_rows(self.h[0], H, self.Rpa)[:EA].view(1, 1, E, A, H)
-        env_state = {"step_count": self.state.step_count, "episode_return": self.state.ep_return,
-                     "episode_length": self.state.ep_length}
-        buffer_state = {"experience": self.buf, "current_index": self.n_added % self.cap,
-                        "is_full": self.n_added >= self.cap}
         scalar = lambda v: torch.tensor([[v]], dtype=torch.int64)
         return LearnerState(obs, self.term[c].view(1, 1, E, 1).bool(), self.tot[c][:EA].view(1, 1, E, A)[..., :1].bool(), hs,
-                            env_state, scalar(self.t_act), scalar(self.t_train), opt, buffer_state, params,
+                            self.env_state(), scalar(self.t_act), scalar(self.t_train), opt, self.buffer_state(), params,
                             torch.tensor([[[self.seed, self.act_steps]]], dtype=torch.int64))
 
     def adopt(self, state: LearnerState) -> None:
@@ -278,37 +275,19 @@ class IQLLearner:
         restored from a checkpoint.  Environment, buffer and optimiser state stay with the learner."""
         leaf = state.params.online["params"]["pre_torso"]["Dense_0"]["kernel"]
         if not isinstance(leaf, torch.Tensor) or leaf.data_ptr() != self.p.data_ptr():
-            to = lambda tree: _tree_to(tree, self.p.device)
+            to = lambda tree: tree_to(tree, self.p.device)
             self.q_network.flat_from_tree(to(state.params.online), self.p)
             self.q_network.flat_from_tree(to(state.params.target), self.pt)
 
-    def learn(self, state: LearnerState) -> ExperimentOutput:
-        self.adopt(state)
-        if self.matmul_mode == "f16x2":
-            check_f16_range(self.p, [self.view[self.cur]], self.train_metrics if self._learn_calls else None, type(self).__name__)
-        self._learn_calls += 1
-        self.trained = [False] * self.n_upd
-        for n in range(self.n_upd):
-            self.update(n)
-        episode_metrics = {
-            "episode_return": self.info_return.unsqueeze(1).unsqueeze(0),
-            "episode_length": self.info_length.unsqueeze(1).unsqueeze(0),
-            "is_terminal_step": self.info_terminal.unsqueeze(1).unsqueeze(0).bool(),
-        }
-        rows = [n for n in range(self.n_upd) if self.trained[n]]
-        train_metrics: Dict[str, torch.Tensor] = {}
-        if rows:  # no train step ran: no TRAIN metrics (run_experiment skips the event)
-            tm = self.train_metrics[rows]
-            train_metrics = {"q_loss": tm[..., 0], "mean_q": tm[..., 1], "mean_target": tm[..., 2]}
-        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
+    def _guard_tensors(self):
+        return self.p, [self.view[self.cur]]
 
-
-def _tree_to(tree: Any, device) -> Any:
-    if isinstance(tree, torch.Tensor):
-        return tree.to(device)
-    if isinstance(tree, dict):
-        return {k: _tree_to(v, device) for k, v in tree.items()}
-    return tree
+    def _train_metrics(self) -> Dict[str, torch.Tensor]:
+        rows = [n for n in range(self.n_upd) if self.trained[n]]  # (update(n) sets trained[n] for every n of a learn() call)
+        if not rows:  # no train step ran: no TRAIN metrics (run_experiment skips the event)
+            return {}
+        tm = self.train_metrics[rows]
+        return {"q_loss": tm[..., 0], "mean_q": tm[..., 1], "mean_target": tm[..., 2]}
 
 
 def learner_setup(env, keys, config, device=None):
@@ -319,9 +298,4 @@ def learner_setup(env, keys, config, device=None):
     learner.seed = key
     learner.init_params(q_key)
     learner.reset_envs()
-
-    def learn(learner_state: LearnerState) -> ExperimentOutput:
-        return learner.learn(learner_state)
-
-    learn.learner = learner  # type: ignore[attr-defined]
-    return learn, learner.q_network, learner.learner_state()
+    return bind_learn(learner), learner.q_network, learner.learner_state()

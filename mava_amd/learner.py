@@ -32,6 +32,7 @@ import torch
 
 from . import ops, parallel
 from .guards import check_f16_range
+from .learner_common import bind_learn, matmul_ctx
 from .networks import FeedForwardActor, FeedForwardValueNet, MLPTorso, make_action_head
 from .types import (AdamState, ExperimentOutput, LearnerState, Observation, ObservationGlobalState, OptStates, Params,
                     TimeStep)
@@ -187,13 +188,10 @@ class FFLearner:
         # Arithmetic of the matrix products (not a Mava key): "f16x2" (default) = every operand split into two f16
         # terms, three f16 MFMAs per product with f32 accumulation (ppo_train_h2.hip, rollout_h2.hip: ~22 mantissa bits
         # per operand, the 1e-4 gradient parity tests run on it) for the shapes those kernels instantiate; "f32" = the
-        # exact-f32 MFMA kernels everywhere.  system.matmul_mode / MAVA_MATMUL select it.
-        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
-        if self.matmul_mode not in ("f16x2", "f32"):
-            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
+        # exact-f32 MFMA kernels everywhere (learner_common.matmul_ctx).
         # the library keeps no process-wide settings: arithmetic mode, critic aggregation and the kernels' own workspaces
         # belong to this learner's context handle (include/mava_hip.h mava_ctx_*)
-        self.ctx = ops.Ctx(self.matmul_mode, critic_aggregation=os.environ.get("MAVA_CRITIC_AGGREGATION", "1") != "0")
+        self.matmul_mode, self.ctx = matmul_ctx(s, critic_aggregation=os.environ.get("MAVA_CRITIC_AGGREGATION", "1") != "0")
         # MAVA_TRAIN_VARIANT=1: the four-wave gradient kernels only (A/B measurements against the eight-wave actor kernel)
         self.ctx.set(self.ctx.TRAIN_VARIANT, int(os.environ.get("MAVA_TRAIN_VARIANT", "0")))
         for net_ in (self.actor_network, self.critic_network):
@@ -673,11 +671,7 @@ def learner_setup(env, keys, config, centralised_critic: bool, device=None):
     learner.init_params(actor_key, critic_key)
     parallel.broadcast_(learner.p, src=0)
     learner.reset_envs()
-    def learn(learner_state: LearnerState) -> ExperimentOutput:
-        return learner.learn(learner_state)
-
-    learn.learner = learner  # type: ignore[attr-defined]  (handle for tests / bench)
-    return learn, learner.actor_network, learner.learner_state()
+    return bind_learn(learner), learner.actor_network, learner.learner_state()
 
 
 def get_final_step_metrics(metrics: Dict[str, torch.Tensor]) -> Tuple[Dict[str, torch.Tensor], bool]:

@@ -22,7 +22,6 @@ Parameters: one flat vector [encoder | decoder], one global-norm clip and one Ad
 from __future__ import annotations
 
 import math
-import os
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -32,8 +31,10 @@ from ._lib import MavaHipError, launch, lib, ptr, stream_ptr
 from .generic_networks import GenericMLPTorso, GenericNet
 from .guards import check_f16_range
 from .learner import _Replica
+from .learner_common import bind_learn, episode_metrics, matmul_ctx, pad32
 from .networks import _orthogonal_
 from .types import AdamState, ExperimentOutput, LearnerState, Observation, TimeStep
+from .utils.tree import tree_to
 
 MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
 
@@ -172,7 +173,7 @@ class _Graph:
     def __init__(self, net: MATNet, B: int, device, training: bool, ctx):
         self.net, self.B, self.A, self.training, self.device = net, int(B), net.A, training, device
         self.valid = self.B * self.A
-        self.rows = -(-self.valid // 32) * 32
+        self.rows = pad32(self.valid)
         self.nblk = max(1, min(256, self.rows // 32))
         self.prod = GenericNet(GenericMLPTorso([net.D]), net.D, [])  # the product launches of the general layer path
         self.prod.ctx = ctx
@@ -294,7 +295,7 @@ class MATPass(_Graph):
     def __init__(self, net: MATNet, B: int, device, training: bool, ctx):
         super().__init__(net, B, device, training, ctx)
         O, nA, D = net.O, net.nA, net.D
-        self.Np = -(-(nA + 1) // 32) * 32
+        self.Np = pad32(nA + 1)
         self.obs = self.buf(O)
         self.onehot = self.buf(nA + 1, ld=self.Np)
         # sample ids of the rows, padded with sample 0 so that the gather of the padding rows stays inside the source
@@ -430,10 +431,7 @@ class MATLearner:
         if env.num_envs != self.E:
             raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
         self.n_upd = int(s.get("num_updates_per_eval", 1))
-        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
-        if self.matmul_mode not in ("f16x2", "f32"):
-            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
-        self.ctx = ops.Ctx(self.matmul_mode)
+        self.matmul_mode, self.ctx = matmul_ctx(s)
         rep_env = env.clone(env_offset=getattr(env, "env_offset", 0))
         self.rep = _Replica(rep_env, self.T, self.n_upd, False, self.device, False)
         self.reps = [self.rep]
@@ -497,7 +495,7 @@ class MATLearner:
     def adopt(self, state: LearnerState) -> None:
         leaf = self.net.first_leaf(state.params)
         if not isinstance(leaf, torch.Tensor) or leaf.data_ptr() != self.p.data_ptr():
-            to = lambda tree: _tree_to(tree, self.p.device)
+            to = lambda tree: tree_to(tree, self.p.device)
             self.net.flat_from_tree(to(state.params), self.p)
             self.net.flat_from_tree(to(state.opt_states.mu), self.m)
             self.net.flat_from_tree(to(state.opt_states.nu), self.v)
@@ -571,20 +569,10 @@ class MATLearner:
         for n in range(self.n_upd):
             self.update(n)
         rep = self.rep
-        episode_metrics = {"episode_return": rep.info_return.unsqueeze(1).unsqueeze(0),
-                           "episode_length": rep.info_length.unsqueeze(1).unsqueeze(0),
-                           "is_terminal_step": rep.info_terminal.unsqueeze(1).unsqueeze(0).bool()}
+        ep_metrics = episode_metrics(rep.info_return, rep.info_length, rep.info_terminal)
         tm = self.train_metrics.unsqueeze(1).unsqueeze(0)
         train_metrics = {"total_loss": tm[..., 0], "value_loss": tm[..., 1], "actor_loss": tm[..., 2], "entropy": tm[..., 3]}
-        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
-
-
-def _tree_to(tree: Any, device) -> Any:
-    if isinstance(tree, torch.Tensor):
-        return tree.to(device)
-    if isinstance(tree, dict):
-        return {k: _tree_to(v, device) for k, v in tree.items()}
-    return tree
+        return ExperimentOutput(self.learner_state(), ep_metrics, train_metrics)
 
 
 def learner_setup(env, keys, config, device=None):
@@ -594,9 +582,4 @@ def learner_setup(env, keys, config, device=None):
     learner.seed = key
     learner.init_params(net_key)
     learner.reset_envs()
-
-    def learn(learner_state: LearnerState) -> ExperimentOutput:
-        return learner.learn(learner_state)
-
-    learn.learner = learner  # type: ignore[attr-defined]
-    return learn, learner.actor_network, learner.learner_state()
+    return bind_learn(learner), learner.actor_network, learner.learner_state()

@@ -27,10 +27,12 @@ from . import ops, parallel
 from ._lib import check, launch, lib, ptr, stream_ptr
 from .guards import check_f16_range
 from .learner import NUM_CU, _Replica
+from .learner_common import bind_learn, matmul_ctx
 from .networks import MLPTorso, make_action_head
 from .rec_networks import H, RecurrentActor, RecurrentValueNet, RecWorkspace, rows_to_t32, t32_to_rows
 from .types import (AdamState, ExperimentOutput, HiddenStates, Observation, ObservationGlobalState, OptStates, Params,
                     RNNLearnerState, TimeStep)
+from .utils.tree import tree_to
 
 
 class _RecReplica(_Replica):
@@ -83,10 +85,7 @@ class RecLearner:
             raise ValueError("num_envs must be divisible by num_minibatches (rec_mappo.py:354-357)")
         self.n_upd = int(s.get("num_updates_per_eval", 1))
         # arithmetic of the dense / X^T Y products on T32 operands: "f16x2" (default, rec_dense_h2.hip) or "f32"
-        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
-        if self.matmul_mode not in ("f16x2", "f32"):
-            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
-        self.ctx = ops.Ctx(self.matmul_mode)  # this learner's context handle (include/mava_hip.h mava_ctx_*): no process-wide mode
+        self.matmul_mode, self.ctx = matmul_ctx(s)
         if env.num_envs != self.E:
             raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
         if centralised_critic and not getattr(env, "add_global_state", False):
@@ -496,7 +495,7 @@ class RecLearner:
         pa = next(iter(state.params.actor_params["params"]["pre_torso"].values()))["kernel"]  # Dense_0 | Conv_0: the flat buffer's start
         if not isinstance(pa, torch.Tensor) or pa.data_ptr() != self.p.data_ptr():
             dev = self.p.device
-            to = lambda tree: self._tree_to(tree, dev)
+            to = lambda tree: tree_to(tree, dev)
             self.actor_network.flat_from_tree(to(state.params.actor_params), self.p[: self.Pa])
             self.critic_network.flat_from_tree(to(state.params.critic_params), self.p[self.Pa :])
             for i, (net, sl, st) in enumerate(((self.actor_network, slice(0, self.Pa), state.opt_states.actor_opt_state),
@@ -504,14 +503,6 @@ class RecLearner:
                 net.flat_from_tree(to(st.mu), self.m[sl])
                 net.flat_from_tree(to(st.nu), self.v[sl])
                 self.count[i] = int(torch.as_tensor(st.count).reshape(-1)[0])
-
-    @staticmethod
-    def _tree_to(tree, device):
-        if isinstance(tree, torch.Tensor):
-            return tree.to(device)
-        if isinstance(tree, dict):
-            return {k: RecLearner._tree_to(v, device) for k, v in tree.items()}
-        return tree
 
     def learn(self, learner_state: RNNLearnerState) -> ExperimentOutput:
         self.adopt(learner_state)
@@ -540,9 +531,4 @@ def learner_setup(env, keys, config, centralised_critic: bool, device=None):
     learner.init_params(actor_key, critic_key)
     parallel.broadcast_(learner.p, src=0)
     learner.reset_envs()
-
-    def learn(learner_state: RNNLearnerState) -> ExperimentOutput:
-        return learner.learn(learner_state)
-
-    learn.learner = learner  # type: ignore[attr-defined]
-    return learn, learner.actor_network, learner.learner_state()
+    return bind_learn(learner), learner.actor_network, learner.learner_state()

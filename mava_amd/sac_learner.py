@@ -24,26 +24,23 @@ which is what the reference's `~discount` is under Jumanji's truncation.
 from __future__ import annotations
 
 import math
-import os
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, Optional
 
 import torch
 
-from . import ops, parallel
+from . import ops
 from ._lib import launch, lib, ptr, stream_ptr
 from .generic_networks import CNNTorso, GenericActor, GenericNet, torso_from_config
-from .guards import check_f16_range
+from .learner_common import bind_learn, pad32
 from .networks import make_action_head
+from .replay_learner import ReplayLearner
 from .systems.sac.types import LearnerState, OptStates, QVals, QValsAndTarget, SacParams, Transition
-from .types import AdamState, ExperimentOutput, Observation, ObservationGlobalState
+from .types import AdamState, Observation, ObservationGlobalState
+from .utils.tree import tree_to
 
 ADAM_EPS = 1e-8  # optax.adam's default (ff_isac.py:146-152), not PPO's 1e-5
 TRAIN_KEY_TAG = 0x545241494E  # "TRAIN": xor-ed into the key of the train steps' noise, apart from the acting noise
 LOSS_BLOCKS = 8
-
-
-def _pad32(n: int) -> int:
-    return -(-n // 32) * 32
 
 
 class QNetwork:
@@ -52,7 +49,7 @@ class QNetwork:
     def __init__(self, torso, input_dim: int, centralised_critic: bool = False):
         self.centralised_critic = centralised_critic
         self.net = GenericNet(torso, input_dim, [("critic", 1, 1.0)])
-        self.din, self.ld = int(input_dim), _pad32(int(input_dim))
+        self.din, self.ld = int(input_dim), pad32(int(input_dim))
 
     @property
     def num_params(self) -> int:
@@ -70,49 +67,39 @@ class QNetwork:
         return out
 
 
-class SACLearner:
-    def __init__(self, env, config, centralised: bool, device: Optional[torch.device] = None):
-        self.config, self.centralised = config, bool(centralised)
-        name = "ff_masac" if centralised else "ff_isac"
-        s, arch, net = config.system, config.arch, config.network
-        self.device = d = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.rank, self.world = parallel.rank_world()
-        if self.world > 1:
-            raise NotImplementedError(f"{name} runs on one device (multi-GPU is not implemented)")
-        if int(s.update_batch_size) != 1:
-            raise NotImplementedError(f"{name} supports update_batch_size == 1 only")
+class SACLearner(ReplayLearner):
+    def _refuse(self, env, config) -> None:
+        """The system's own refusals; keeps what they build on the way: the action head and the two torsos."""
+        name, net, centralised = self.name, config.network, self.centralised
         if not (getattr(env, "continuous_actions", False) and getattr(env, "emits_real_next_obs", False)):
             raise ValueError(f"{name} needs an environment with continuous actions that returns its pre-reset observation "
                              f"(env=spread); {type(env).__name__} is not one")
-        head = make_action_head(dict(net.get("action_head", None) or {}, independent_std=False), env.action_dim)
+        self._head = head = make_action_head(dict(net.get("action_head", None) or {}, independent_std=False), env.action_dim)
         if type(head).__name__ != "ContinuousActionHead":
             raise ValueError(f"{name} needs a ContinuousActionHead (network=continuous_mlp), got {type(head).__name__}")
-        actor_torso, q_torso = torso_from_config(net.actor_network.pre_torso), torso_from_config(net.critic_network.pre_torso)
-        if isinstance(q_torso, CNNTorso):
+        self._torsos = torso_from_config(net.actor_network.pre_torso), torso_from_config(net.critic_network.pre_torso)
+        if isinstance(self._torsos[1], CNNTorso):
             raise NotImplementedError(f"{name}: a CNN critic torso cannot read [state | action] rows (use an MLPTorso)")
         if centralised and not getattr(env, "add_global_state", False):
             raise ValueError("Global state must be provided to the centralised critic.")  # networks.py:223-224
-        self.E, self.T, self.K = int(arch.num_envs), int(s.rollout_length), int(s.epochs)
-        if env.num_envs != self.E:
-            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
+
+    def _buffer_sizes(self, s) -> None:
         self.B, self.cap = int(s.batch_size), int(s.buffer_size)
         if self.cap < self.E:
             raise ValueError(f"buffer_size={self.cap} cannot hold one acting step of num_envs={self.E} items")
         self.delay = int(s.policy_update_delay)
         if self.delay < 1:
             raise ValueError("Need to have a policy update delay > 0.")  # ff_isac.py:347
-        self.n_upd = int(s.get("num_updates_per_eval", 1))
-        self.env = env
-        self.A, self.D, self.O = env.num_agents, env.action_dim, env.obs_dim
+
+    def __init__(self, env, config, centralised: bool, device: Optional[torch.device] = None):
+        self.centralised = bool(centralised)
+        self.name = "ff_masac" if centralised else "ff_isac"
+        super().__init__(env, config, device)  # the shared refusals, then the two hooks above, then the scaffolding
+        s, d, head, (actor_torso, q_torso) = config.system, self.device, self._head, self._torsos
+        self.D = env.action_dim
         self.S = env.state_dim if centralised else 0
-        config.system.num_agents = self.A
         E, A, O, D, S = self.E, self.A, self.O, self.D, self.S
-        self.EA, self.BA = E * A, self.B * A
-        self.Rpa, self.Rp = _pad32(self.EA), _pad32(self.BA)  # acting / sampled rows, padded to the 32-row tiles
-        self.matmul_mode = str(s.get("matmul_mode", None) or os.environ.get("MAVA_MATMUL", "f16x2"))
-        if self.matmul_mode not in ("f16x2", "f32"):
-            raise ValueError(f"system.matmul_mode must be 'f16x2' or 'f32', got {self.matmul_mode!r}")
-        self.ctx = ops.Ctx(self.matmul_mode)
+        self.BA = self.B * A
         self.min_scale = float(head.min_scale)
         self.actor_network = GenericActor(actor_torso, head, O, getattr(env, "obs_shape", None))
         self.actor_network.ctx = self.ctx
@@ -138,11 +125,6 @@ class SACLearner:
         self.reward, self.done_step = z(E, A), z(E, A, dtype=u8)
         self.term = z(E, dtype=u8)
         self.real_view, self.real_mask, self.real_gs = z(E, A, O), z(E, A, D, dtype=u8), z(E, 1, env.state_dim)
-        self.state = env.alloc_state()
-        self.cur = 0
-        self.info_return = z(self.n_upd, self.T, E)
-        self.info_length = z(self.n_upd, self.T, E, dtype=torch.int32)
-        self.info_terminal = z(self.n_upd, self.T, E, dtype=u8)
         self.ws_act = self.actor_network.net.workspace(self.Rpa, d, training=False)
         # ---- item buffer (fbx.make_item_buffer(add_batches=True), :171-176) and one sampled batch
         cap, B, Rp = self.cap, self.B, self.Rp
@@ -179,13 +161,10 @@ class SACLearner:
         self.init_alpha = float(s.init_alpha)
         self.target_entropy = -float(s.target_entropy_scale) * D  # :128
         self.explore_steps = int(s.explore_steps) // E  # acting steps with random actions (:470)
-        self.t = 0           # env steps taken (num_envs per act step): what the policy-delay test reads
-        self.act_steps = 0   # act steps taken: the env's Philox counter and the acting noise's
-        self.n_added = 0     # items stored
-        self.t_train = 0     # train steps taken: counter of the sampler and of the train noise
-        self._learn_calls = 0
+        # env steps taken (num_envs per act step): what the policy-delay test reads.  Of the base's counters, n_added
+        # counts the items stored and t_train is the train noise's counter too
+        self.t = 0
         self._explore_gen = torch.Generator(device=d)
-        self.debug: Optional[Dict[str, List[Any]]] = None  # tests: clones of gradients / noise / indices when set
 
     # ------------------------------------------------------------------------------------ setup
     def init_params(self, actor_seed: int, q_seeds) -> None:
@@ -203,10 +182,6 @@ class SACLearner:
         E, A = self.E, self.A
         return {"agents_view": self.view[k][: self.EA].view(E, A, self.O), "global_state": self.gs[k], "action_mask": self.mask,
                 "step_count": self.sc[k]}
-
-    def reset_envs(self) -> None:
-        self.cur = 0
-        self.env.step_into(self.state, 0, self._obs_slot(0), is_reset=True)
 
     # ------------------------------------------------------------------------------------ pieces
     def _pi(self, ws, obs_rows: torch.Tensor, rows: int, n_real: int, seed: int, step: int, action, logp, eps) -> None:
@@ -254,7 +229,7 @@ class SACLearner:
         self._pi(self.ws_act, self.view[self.cur], self.Rpa, self.EA, self.seed, self.act_steps, self.action, None, None)
         if self.debug is not None:
             self.debug["actions"].append(self.action[: self.EA].clone())
-        self._step((self.info_return[n, t], self.info_length[n, t], self.info_terminal[n, t]), self.action)
+        self._step(self._info(n, t), self.action)
 
     def explore(self) -> Dict[str, torch.Tensor]:
         """:431-444, :470-478: explore_steps // num_envs steps with actions uniform in [0, 1) (jax.random.uniform's default
@@ -375,10 +350,8 @@ class SACLearner:
         opt = OptStates(AdamState(cnt(0), an.tree(self.ma, lead), an.tree(self.va, lead)),
                         AdamState(cnt(1), qm(self.mq), qm(self.vq)),
                         AdamState(cnt(2), self.ml.expand(1, 1, 1, A), self.vl.expand(1, 1, 1, A)))
-        env_state = {"step_count": self.state.step_count, "episode_return": self.state.ep_return,
-                     "episode_length": self.state.ep_length}
-        buffer_state = {"experience": self.buf, "current_index": self.n_added % self.cap, "is_full": self.n_added >= self.cap}
-        return LearnerState(obs, env_state, buffer_state, self.params(lead), opt, torch.tensor([[self.t]], dtype=torch.int64),
+        return LearnerState(obs, self.env_state(), self.buffer_state(), self.params(lead), opt,
+                            torch.tensor([[self.t]], dtype=torch.int64),
                             torch.tensor([[[self.seed, self.act_steps]]], dtype=torch.int64))
 
     def adopt(self, state: LearnerState) -> None:
@@ -388,7 +361,7 @@ class SACLearner:
         leaf = self.actor_network.first_leaf(p.actor)
         if isinstance(leaf, torch.Tensor) and leaf.data_ptr() == self.pa.data_ptr():
             return
-        to = lambda tree: _tree_to(tree, self.device)
+        to = lambda tree: tree_to(tree, self.device)
         Pq = self.Pq
         self.actor_network.flat_from_tree(to(p.actor), self.pa)
         for flat, qv in ((self.pq, p.q.online), (self.pqt, p.q.targets)):
@@ -396,31 +369,13 @@ class SACLearner:
             self.q_network.flat_from_tree(to(qv.q2), flat[Pq:])
         self.log_alpha.copy_(torch.as_tensor(p.log_alpha).reshape(-1)[-self.A:].to(self.device))
 
-    def learn(self, state: LearnerState) -> ExperimentOutput:
-        self.adopt(state)
-        if self.matmul_mode == "f16x2":
-            check_f16_range(torch.cat([self.pa, self.pq]), [self.view[self.cur]], self.train_metrics if self._learn_calls else None,
-                            type(self).__name__)
-        self._learn_calls += 1
-        for n in range(self.n_upd):
-            self.update(n)
-        episode_metrics = {
-            "episode_return": self.info_return.unsqueeze(1).unsqueeze(0),
-            "episode_length": self.info_length.unsqueeze(1).unsqueeze(0),
-            "is_terminal_step": self.info_terminal.unsqueeze(1).unsqueeze(0).bool(),
-        }
+    def _guard_tensors(self):
+        return torch.cat([self.pa, self.pq]), [self.view[self.cur]]
+
+    def _train_metrics(self) -> Dict[str, torch.Tensor]:
         tm = self.train_metrics
-        train_metrics = {"q1_loss": tm[..., 0], "q2_loss": tm[..., 1], "loss": tm[..., 0] + tm[..., 1], "q1_a_vals": tm[..., 2],
-                         "q2_a_vals": tm[..., 3], "actor_loss": tm[..., 4], "alpha_loss": tm[..., 5]}
-        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
-
-
-def _tree_to(tree: Any, device) -> Any:
-    if isinstance(tree, torch.Tensor):
-        return tree.to(device)
-    if isinstance(tree, dict):
-        return {k: _tree_to(v, device) for k, v in tree.items()}
-    return tree
+        return {"q1_loss": tm[..., 0], "q2_loss": tm[..., 1], "loss": tm[..., 0] + tm[..., 1], "q1_a_vals": tm[..., 2],
+                "q2_a_vals": tm[..., 3], "actor_loss": tm[..., 4], "alpha_loss": tm[..., 5]}
 
 
 def learner_setup(env, keys, config, centralised: bool, device=None):
@@ -431,10 +386,6 @@ def learner_setup(env, keys, config, centralised: bool, device=None):
     learner.seed = int(keys[0])
     learner.init_params(int(keys[1]), [int(k) for k in keys[2:6]])
     learner.reset_envs()
-
-    def learn(learner_state: LearnerState) -> ExperimentOutput:
-        return learner.learn(learner_state)
-
-    learn.learner = learner  # type: ignore[attr-defined]
+    learn = bind_learn(learner)
     learn.explore = learner.explore  # type: ignore[attr-defined]
     return learn, learner.actor_network, learner.learner_state()

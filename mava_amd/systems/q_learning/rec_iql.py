@@ -11,17 +11,13 @@ observation (the synthetic stand-ins) are refused.
 """
 from __future__ import annotations
 
-import copy
-import time
 from typing import Any, Callable, Dict, Optional
 
 import torch
 
-from ... import envs as environments
 from ... import iql_learner as _learner
-from ...config import Config, check_total_timesteps
-from ...learner import get_final_step_metrics
-from ..ppo.anakin import _tree_clone, _tree_to, _unreplicate_n_dims
+from ...config import Config
+from .. import off_policy
 from .types import QNetParams
 
 
@@ -50,90 +46,34 @@ def _check_config(config: Config) -> None:
                          f"{config.env.get('env_name', None)} runs on the synthetic stand-in, which does not")
 
 
-def run_experiment(_config: Config, log: Optional[Callable[[Dict[str, Any]], None]] = None) -> float:
-    config = copy.deepcopy(_config)
-    _check_config(config)
-    config.arch.n_devices = 1
-    config = check_total_timesteps(config, 1)
-    s = config.system
-    # rec_iql.py:535-543: env steps per evaluation interval and the updates that take them
-    steps_per_rollout = int(s.total_timesteps // config.arch.num_evaluation)
-    act_steps = int(config.arch.num_envs) * int(s.rollout_length)
-    s.num_updates_per_eval = max(1, steps_per_rollout // act_steps)
+def eval_act(q_network, config: Config, eval_env):
+    """eval_act_fn (:563-578): the epsilon-greedy distribution at eps = 0 (q_network.apply's default), from a zero carry."""
+    from ...evaluator import make_rec_eval_act_fn
 
-    env, eval_env = environments.make(config)
-    seed = int(s.seed)
-    key, q_key, key_e = seed, seed + 1, seed + 2  # stands in for the reference's key splits
-    learn, q_network, learner_state = learner_setup(env, (key, q_key), config)
-
-    from ...evaluator import get_eval_fn, make_rec_eval_act_fn
-    from ...utils.logger import LogEvent, MavaLogger
-
-    # eval_act_fn (:563-578): the epsilon-greedy distribution at eps = 0 (q_network.apply's default): greedy either way
-    act_fn = make_rec_eval_act_fn(q_network.apply, config)
     init_act_state = {"hidden_state": torch.zeros((eval_env.num_envs, eval_env.num_agents, 128), device=eval_env.device)}
-    evaluator = get_eval_fn(eval_env, act_fn, config, absolute_metric=False)
+    return make_rec_eval_act_fn(q_network.apply, config), init_act_state
 
-    ck = config.logger.checkpointing
-    checkpointer = None
-    if bool(ck.save_model):
-        from ...utils.checkpointing import Checkpointer
 
-        checkpointer = Checkpointer(metadata=config.to_container(), model_name=str(config.logger.system_name),
-                                    **{k: (v if v != "" else None) for k, v in dict(ck.save_args).items()})
-    if bool(ck.load_model):
-        from ...utils.checkpointing import Checkpointer
+def q_learning_spec(name: str, check_config, setup) -> off_policy.Spec:
+    """What the Q-learners (rec_iql, rec_qmix, rec_vdn) have in common; `setup(env, keys, config)` is their learner_setup."""
+    def seeded_setup(env, config: Config):
+        seed = int(config.system.seed)  # seed, seed + 1 | evaluations from seed + 2: stands in for the reference's key splits
+        return (*setup(env, (seed, seed + 1), config), (seed, seed + 2))
 
-        loaded = Checkpointer(model_name=str(config.logger.system_name), **{k: v for k, v in dict(ck.load_args).items()})
-        restored, _ = loaded.restore_params(input_params=learner_state.params)
-        learner_state = learner_state._replace(params=_tree_to(restored, eval_env.device))  # learn() adopts online + target
+    return off_policy.Spec(
+        name=name, check_config=check_config, add_global_state=False, setup=seeded_setup, eval_act=eval_act,
+        eval_params=lambda params: params.online,
+        # :604-606: epsilon at the interval's end
+        misc=lambda config, t: {"epsilon": _learner.epsilon(t, config.system.eps_min, config.system.eps_decay)},
+        train_extra=lambda state: {},
+        checkpoint_payload=lambda p: QNetParams(p.online, p.target)._asdict())  # online + target
 
-    logger = MavaLogger(config) if log is None else None
 
-    def emit(event: str, rec: Dict[str, Any], t: int, idx: int) -> None:
-        if logger is not None:
-            logger.log(rec, t, idx, getattr(LogEvent, event))
-        else:
-            out = {k: (float(v.float().mean()) if isinstance(v, torch.Tensor) else v) for k, v in rec.items()}
-            if "won_episode" in out:  # what MavaLogger.calc_winrate makes of it
-                out["win_rate"] = 100.0 * out.pop("won_episode")
-            log({"event": event, "timestep": t, **out})
+SPEC = q_learning_spec("rec_iql", _check_config, learner_setup)
 
-    eval_return, max_return, best_params, t = 0.0, -float("inf"), None, 0
-    n_evals = int(config.arch.num_evaluation)
-    for eval_idx in range(n_evals):
-        torch.cuda.synchronize()
-        start = time.time()
-        out = learn(learner_state)
-        torch.cuda.synchronize()
-        elapsed = time.time() - start
-        learner_state = out.learner_state
-        t = steps_per_rollout * (eval_idx + 1)
-        eps = _learner.epsilon(t, s.eps_min, s.eps_decay)  # :604-606, at the interval's end
-        ep_metrics, ep_completed = get_final_step_metrics(out.episode_metrics)
-        ep_metrics = dict(ep_metrics)
-        ep_metrics["steps_per_second"] = steps_per_rollout / elapsed
-        emit("MISC", {"timestep": t, "epsilon": eps}, t, eval_idx)
-        if ep_completed:
-            emit("ACT", ep_metrics, t, eval_idx)
-        if out.train_metrics:
-            emit("TRAIN", out.train_metrics, t, eval_idx)
-        eval_params = _tree_clone(learner_state.params.online)
-        eval_metrics = evaluator(eval_params, key_e + eval_idx, init_act_state)
-        emit("EVAL", eval_metrics, t, eval_idx)
-        eval_return = float(eval_metrics["episode_return"].float().mean())
-        if bool(config.arch.absolute_metric) and max_return <= eval_return:
-            best_params, max_return = eval_params, eval_return
-        if checkpointer is not None:  # online + target (QNetParams); the replay buffer is not checkpointed
-            p = _unreplicate_n_dims(learner_state.params)
-            checkpointer.save(timestep=t, unreplicated_learner_state={"params": QNetParams(p.online, p.target)._asdict()},
-                              episode_return=eval_return)
-    if bool(config.arch.absolute_metric) and best_params is not None:
-        abs_metrics = get_eval_fn(eval_env, act_fn, config, absolute_metric=True)(best_params, key, init_act_state)
-        emit("ABSOLUTE", abs_metrics, t, n_evals - 1)
-    if logger is not None:
-        logger.stop()
-    return eval_return
+
+def run_experiment(config: Config, log: Optional[Callable[[Dict[str, Any]], None]] = None) -> float:
+    return off_policy.run_experiment(config, SPEC, log)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,7 @@ runs on (env=lbf, the default, env=rware_native, env=connector, env=cleaner, env
 """
 from __future__ import annotations
 
+from .. import off_policy
 from . import _mixer_runner as _runner
 
 MIXER = "qmix"
@@ -22,7 +23,7 @@ def _check_config(config) -> None:
 
 
 def run_experiment(config, log=None) -> float:
-    return _runner.run_experiment(config, MIXER, log=log)
+    return off_policy.run_experiment(config, _runner.spec(MIXER), log)
 
 
 if __name__ == "__main__":

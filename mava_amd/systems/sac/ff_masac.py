@@ -10,6 +10,7 @@ and finally ABSOLUTE with the best actor.  Runs on env=spread, the one environme
 from __future__ import annotations
 
 from ... import sac_learner as _learner
+from .. import off_policy
 from . import _runner
 
 CENTRALISED_CRITIC = True
@@ -24,7 +25,7 @@ def _check_config(config) -> None:
 
 
 def run_experiment(config, log=None) -> float:
-    return _runner.run_experiment(config, CENTRALISED_CRITIC, log=log)
+    return off_policy.run_experiment(config, _runner.spec(CENTRALISED_CRITIC), log)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,8 @@ from typing import Any, Dict, Optional, Tuple, Type
 import torch
 from safetensors.torch import load_file, save_file
 
+from .tree import tree_to
+
 CHECKPOINTER_VERSION = 1.0  # mava/utils/checkpointing.py:35
 
 
@@ -160,3 +162,20 @@ class Checkpointer:
         """The metadata of the checkpoint (:209-212)."""
         with open(os.path.join(self.directory, "metadata.json")) as f:
             return json.load(f)
+
+
+def open_checkpoints(config, params: Any, device, save: bool = True) -> Tuple[Optional[Checkpointer], Any]:
+    """What every experiment loop does with `logger.checkpointing` before it trains (ff_mappo.py:440-459): the
+    Checkpointer to save with (None unless save_model and `save`), and `params` - the ones restored under load_model,
+    moved to `device` (checkpoints hold host tensors), else the argument itself."""
+    ck = config.logger.checkpointing
+    checkpointer = None
+    if bool(ck.save_model) and save:
+        checkpointer = Checkpointer(metadata=config.to_container() if hasattr(config, "to_container") else None,
+                                    model_name=str(config.logger.system_name),
+                                    **{k: (v if v != "" else None) for k, v in dict(ck.save_args).items()})
+    if bool(ck.load_model):
+        loaded = Checkpointer(model_name=str(config.logger.system_name), **{k: v for k, v in dict(ck.load_args).items()})
+        restored, _ = loaded.restore_params(input_params=params)
+        params = tree_to(restored, device)
+    return checkpointer, params
