@@ -15,9 +15,10 @@
 // turns it into the pmean of ff_mappo.py:224-238.
 //
 // MI355X mapping: 77 K parameters = 2.1 MB of traffic, i.e. launch/latency bound.  One launch:
-// every block first reduces the whole (L2-resident) gradient of each network in the same fixed
-// order, so all blocks hold a bit-identical norm with no grid barrier and no atomics, then
-// updates its own slice of p/m/v with 16-byte accesses where alignment allows.
+// every block first reduces the whole (L2-resident) gradient of each network - or the slab reducer's
+// partial sums of it - in the same fixed order, so all blocks hold a bit-identical norm with no grid
+// barrier and no atomics, then updates its own slice of p/m/v; everything a thread reads is requested
+// in one round at the top.
 #include "h2_core.h"
 #include "ctx.h"
 
@@ -43,19 +44,86 @@ __device__ inline double block_sum(double x, double* sh) {
   return t;
 }
 
+// block_sum of two values at once: the same additions per value, one pair of barriers for both
+__device__ inline void block_sum2(double& x, double& y, double (*sh2)[ADAM_THREADS / 64]) {
+  for (int o = 32; o > 0; o >>= 1) {
+    x += __shfl_down(x, o, 64);
+    y += __shfl_down(y, o, 64);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { sh2[0][w] = x; sh2[1][w] = y; }
+  __syncthreads();
+  double t = 0.0, u = 0.0;
+  for (int i = 0; i < ADAM_THREADS / 64; ++i) { t += sh2[0][i]; u += sh2[1][i]; }
+  x = t;
+  y = u;
+}
+
 // Fused tail (mava_ppo_finish_f32): `norm_partials` != null - the squared norms come from the per-block partial sums the slab
 // reducer left behind (n_partial x 2 doubles: segment 0, segment 1) instead of a pass over g; `ticket` != null - the block
 // that finishes LAST (arrival ticket, no grid barrier: a barrier costs more than the kernel boundary it would replace,
-// MI355X_MICROARCH.md price list) increments the step counts and, for PACK > 0, re-splits the wide critic's W1 (PACK =
-// its 16-input steps) from the parameters this launch has just written into `w1_split` for the next gradient launch.
+// MI355X_MICROARCH.md price list) increments the step counts.  For PACK > 0 (the wide critic's 16-input steps) the launch
+// also re-splits that network's W1 into `w1_split` for the next gradient launch: the W1 range of the parameters belongs to
+// PACK_BLOCKS extra blocks (below), which split what they have just computed - no block waits for another.
 struct AdamTail {
   const double* norm_partials;
   int n_partial;
   unsigned int* ticket;
-  int pack_offset;  // start of the network whose W1 is re-split, as an offset into p: the pack reads what this launch wrote
-  int pack_din;     // through p itself, not through a second (restrict) pointer to the same memory
+  int pack_offset;  // start of the network whose W1 is re-split, as an offset into p
+  int pack_din;
   uint4* w1_split;
 };
+
+// One parameter's clip + Adam step, the ONE place it is written: the flat lanes and the pack blocks must give the same bits
+// (a weight belongs to either depending on the launch), and with contraction on the same expression can fuse differently
+// in two contexts.  The roundings are those of the kernel as it always compiled: every product and sum of m and v rounded
+// on its own, one fused multiply-add for the parameter.  (The library is built with -ffp-contract=fast, which fuses whatever
+// it meets and honours no pragma: a product that must be rounded passes through an empty asm statement.  Without them the
+// pack blocks and the flat lanes did differ in p, tests/test_gpu_tail.py.)  `nrm` < 0: no clipping.
+__device__ __forceinline__ float rounded(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ void adam_element(float g_sum, float& pi, float& mi, float& vi, float grad_scale, float nrm,
+                                             float max_norm, float b1, float b2, float bc1, float bc2, float lr, float eps) {
+  float gi = g_sum * grad_scale;
+  if (nrm >= 0.0f) gi = (gi / nrm) * max_norm;
+  const float g1 = rounded((1.0f - b1) * gi);
+  const float g2 = rounded(((1.0f - b2) * gi) * gi);
+  mi = rounded(b1 * mi) + g1;
+  vi = rounded(b2 * vi) + g2;
+  const float mhat = mi / bc1;
+  const float vhat = vi / bc2;
+  const float q = mhat / (sqrtf(vhat) + eps);
+  pi = __builtin_fmaf(-lr, q, pi);
+}
+
+// A thread's batch of N parameters: loaded in one go (addresses of dead entries clamped to a live one), updated, stored.
+template <int N>
+struct AdamBatch {
+  int idx[N];
+  bool live[N];
+  float g[N], p[N], m[N], v[N];
+  __device__ __forceinline__ void load(const float* __restrict__ gp, const float* pp, const float* mp, const float* vp) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      g[u] = gp[idx[u]];
+      m[u] = mp[idx[u]];
+      v[u] = vp[idx[u]];
+      p[u] = pp[idx[u]];
+    }
+  }
+};
+
+// The W1 re-split inside the Adam launch.  pack_w1_body's 256 lanes (wave w, r, h) each run a carry chain over their
+// own 8 * PACK inputs k = 16 s + 8 h + e of feature f = 32 w + r; the chain is serial, the Adam step of those inputs is
+// not (~70 instructions each with four divisions and a root: 144 of them on the chain's own lane would cost more than
+// the whole launch did).  So a pack block owns PACK_CHAINS chains (same w and h, consecutive f): its 256 threads update
+// the chains' PACK_CHAINS x 8 PACK weights (one round of loads), leave the new values in LDS, and its first PACK_CHAINS
+// lanes split them from there.
+constexpr int PACK_CHAINS = 8;
+constexpr int PACK_BLOCKS = 256 / PACK_CHAINS;
 
 template <int PACK>
 __global__ __launch_bounds__(ADAM_THREADS) void clip_adam_kernel(
@@ -64,28 +132,106 @@ __global__ __launch_bounds__(ADAM_THREADS) void clip_adam_kernel(
     float grad_scale, float max_norm, int decay, int steps_per_update, int num_updates, float b1,
     float b2, float eps, const float* __restrict__ loss_sums, float vf_coef, float ent_coef,
     float* __restrict__ metrics_out, AdamTail tail) {
+  constexpr int FLAT_N = 4;                           // parameters per flat thread and batch
+  // a chain's 8 PACK inputs dealt to the block's 256 / PACK_CHAINS threads per chain
+  constexpr int PACK_N = PACK > 0 ? (8 * PACK * PACK_CHAINS + ADAM_THREADS - 1) / ADAM_THREADS : 1;
   __shared__ double sh[ADAM_THREADS / 64];
+  __shared__ double sh2[2][ADAM_THREADS / 64];
   __shared__ float s_clip[MAX_SEG];
   __shared__ float s_bc1[MAX_SEG], s_bc2[MAX_SEG];  // 1 - b^t, evaluated in f64 (no f32 cancellation)
-  __shared__ int s_last;
+  __shared__ float s_lr[MAX_SEG];
+  __shared__ float s_w[PACK > 0 ? 8 * PACK : 1][PACK_CHAINS];  // a pack block's new weights, [input j][chain]
+
+  // The W1 range [w1_lo, w1_lo + w1_n) belongs to the last PACK_BLOCKS blocks of the grid, everything else to the flat lanes
+  const int total = segs.off[n_seg];
+  const int w1_lo = PACK > 0 ? tail.pack_offset : 0;
+  const int w1_n = PACK > 0 ? (tail.pack_din + 1) * MLP_H : 0;
+  const int n_flat = total - w1_n;
+  const int flat_blocks = (int)gridDim.x - (PACK > 0 ? PACK_BLOCKS : 0);
+  const bool pack_block = PACK > 0 && (int)blockIdx.x >= flat_blocks;
+  const int flat_stride = flat_blocks * ADAM_THREADS;
+  auto flat_index = [&](int i) { return (PACK > 0 && i >= w1_lo) ? i + w1_n : i; };
+
+  // ---- one round of loads: everything below that depends on nothing but the launch arguments is requested here, before the
+  // first of it is used - this thread's parameters with their gradient and moments, the counts, and (fused tail) its share
+  // of the norm partials.  The launch is a chain of round trips to memory other XCDs wrote; this makes it one.
+  AdamBatch<FLAT_N> fb;
+  AdamBatch<PACK_N> pb;
+  const int chain = (PACK > 0 && pack_block) ? ((int)blockIdx.x - flat_blocks) * PACK_CHAINS + (threadIdx.x & (PACK_CHAINS - 1)) : 0;
+  int flat_base = blockIdx.x * ADAM_THREADS + threadIdx.x;
+  if (pack_block) {
+    const int f = 32 * (chain >> 6) + (chain & 31), h = (chain & 63) >> 5;
+#pragma unroll
+    for (int u = 0; u < PACK_N; ++u) {
+      const int j = (threadIdx.x / PACK_CHAINS) + (ADAM_THREADS / PACK_CHAINS) * u;  // input j of the chain, see pack_w1_chain
+      const int k = 16 * (j >> 3) + 8 * h + (j & 7);
+      pb.live[u] = j < 8 * PACK && k <= tail.pack_din;
+      pb.idx[u] = w1_lo + min(k, tail.pack_din) * MLP_H + f;
+    }
+    pb.load(g, p, m, v);
+  } else {
+#pragma unroll
+    for (int u = 0; u < FLAT_N; ++u) {
+      const int i = flat_base + u * flat_stride;
+      fb.live[u] = i < n_flat;
+      fb.idx[u] = flat_index(min(i, n_flat - 1));
+    }
+    fb.load(g, p, m, v);
+  }
+  // the step counts: lanes 0 .. 2 n_seg - 1 of the block each raise one b to one t (f64 pow, ~1 us each; thread 0 used to
+  // evaluate all of them in turn), lanes < n_seg also form the learning rate
+  // (the counts through uniform addresses: scalar loads, which do not queue behind the vector loads around them)
+  const bool coef_lane = (int)threadIdx.x < 2 * n_seg;
+  int coef_cnt = 0;
+#pragma unroll
+  for (int k = 0; k < MAX_SEG; ++k) {
+    const int c = k < n_seg ? count[k] : 0;
+    if ((int)(threadIdx.x >> 1) == k) coef_cnt = c;
+  }
+  constexpr int NP = 8;  // norm partial pairs in flight per thread
+  typedef double dbl2 __attribute__((ext_vector_type(2), aligned(8)));
+  dbl2 q[NP];
+  if (tail.norm_partials != nullptr) {
+    const dbl2* np2 = reinterpret_cast<const dbl2*>(tail.norm_partials);
+#pragma unroll
+    for (int u = 0; u < NP; ++u) q[u] = np2[min((int)threadIdx.x + u * ADAM_THREADS, tail.n_partial - 1)];
+  }
+  if (coef_lane) {
+    const int sgi = threadIdx.x >> 1;
+    const double t = (double)(coef_cnt + 1);
+    if (threadIdx.x & 1) s_bc2[sgi] = (float)(1.0 - pow((double)b2, t));
+    else s_bc1[sgi] = (float)(1.0 - pow((double)b1, t));
+    if ((threadIdx.x & 1) == 0) {
+      float lr = segs.lr[sgi];
+      if (decay) {
+        // mava/utils/training.py:36-42: frac = 1 - (count // (epochs*minibatches)) / num_updates
+        const float frac = 1.0f - (float)(coef_cnt / steps_per_update) / (float)num_updates;
+        lr = lr * frac;
+      }
+      s_lr[sgi] = lr;
+    }
+  }
 
   // ---- phase 1: every block computes every segment's norm identically
-  for (int sgi = 0; sgi < n_seg; ++sgi) {
-    const int lo = segs.off[sgi], hi = segs.off[sgi + 1];
-    if (tail.norm_partials != nullptr) {
-      // fixed order: thread t adds partials t, t + 256, ...; then the block sum - bit-identical in every block
-      double a = 0.0;
-      for (int b = threadIdx.x; b < tail.n_partial; b += ADAM_THREADS) a += tail.norm_partials[2 * b + sgi];
-      const double tot = block_sum(a, sh);
-      if (threadIdx.x == 0) {
-        const float nrm = (float)sqrt(tot);
-        s_clip[sgi] = (nrm < max_norm) ? -1.0f : nrm;
-        const double t = (double)(count[sgi] + 1);
-        s_bc1[sgi] = (float)(1.0 - pow((double)b1, t));
-        s_bc2[sgi] = (float)(1.0 - pow((double)b2, t));
-      }
-      continue;
+  if (tail.norm_partials != nullptr) {
+    // (two segments: mava_ppo_finish_f32.)  Fixed order: thread t adds partials t, t + 256, ...; then the block sum -
+    // bit-identical in every block
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int u = 0; u < NP; ++u)
+      if ((int)threadIdx.x + u * ADAM_THREADS < tail.n_partial) { a0 += q[u].x; a1 += q[u].y; }
+    for (int b = threadIdx.x + NP * ADAM_THREADS; b < tail.n_partial; b += ADAM_THREADS) {
+      a0 += tail.norm_partials[2 * b];
+      a1 += tail.norm_partials[2 * b + 1];
     }
+    block_sum2(a0, a1, sh2);
+    if (threadIdx.x < 2) {
+      const float nrm = (float)sqrt(threadIdx.x == 0 ? a0 : a1);
+      s_clip[threadIdx.x] = (nrm < max_norm) ? -1.0f : nrm;
+    }
+  }
+  for (int sgi = 0; tail.norm_partials == nullptr && sgi < n_seg; ++sgi) {
+    const int lo = segs.off[sgi], hi = segs.off[sgi + 1];
     // 16-byte loads, 8 of them in flight per thread: this phase is a chain of L2 round trips (every block reads the
     // whole gradient), ~10 of them at 77 K parameters instead of the ~40 of one float per load
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -131,39 +277,61 @@ __global__ __launch_bounds__(ADAM_THREADS) void clip_adam_kernel(
       const float nrm = (float)sqrt(tot);
       // optax.clip_by_global_norm: trigger = n < c ; else (g / n) * c
       s_clip[sgi] = (nrm < max_norm) ? -1.0f : nrm;
-      const double t = (double)(count[sgi] + 1);
-      s_bc1[sgi] = (float)(1.0 - pow((double)b1, t));
-      s_bc2[sgi] = (float)(1.0 - pow((double)b2, t));
     }
   }
   __syncthreads();
 
+  // ---- arrival ticket, taken as soon as this block has read the counts (the coefficient lanes consumed them before the
+  // barrier above): whoever arrives last increments them at its end.  No other block waits on the ticket, and only this
+  // wave for its round trip (the compiler broadcasts the returned number at once); at the end of the block, behind a fence
+  // over all its stores, it cost 1 us more.
+  unsigned int ticket_no = 0;
+  if (tail.ticket != nullptr && threadIdx.x == 0)
+    ticket_no = __hip_atomic_fetch_add(tail.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+
   // ---- phase 2: slice update
-  const int total = segs.off[n_seg];
-  const int gid = blockIdx.x * ADAM_THREADS + threadIdx.x;
-  const int stride = gridDim.x * ADAM_THREADS;
-  for (int i = gid; i < total; i += stride) {
+  // (dead entries of a batch are computed on the live element their address was clamped to and not stored: without a branch
+  // per entry the compiler interleaves the entries' division chains)
+  auto update = [&](bool live, int i, float gi, float& pi, float& mi, float& vi) {
     int sgi = 0;
 #pragma unroll
     for (int k = 1; k < MAX_SEG; ++k)
       if (k < n_seg && i >= segs.off[k]) sgi = k;
-    const int cnt = count[sgi];
-    float lr = segs.lr[sgi];
-    if (decay) {
-      // mava/utils/training.py:36-42: frac = 1 - (count // (epochs*minibatches)) / num_updates
-      const float frac = 1.0f - (float)(cnt / steps_per_update) / (float)num_updates;
-      lr = lr * frac;
+    adam_element(gi, pi, mi, vi, grad_scale, s_clip[sgi], max_norm, b1, b2, s_bc1[sgi], s_bc2[sgi], s_lr[sgi], eps);
+    if (live) {
+      m[i] = mi;
+      v[i] = vi;
+      p[i] = pi;
     }
-    float gi = g[i] * grad_scale;
-    const float nrm = s_clip[sgi];
-    if (nrm >= 0.0f) gi = (gi / nrm) * max_norm;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    const float mhat = mi / s_bc1[sgi];
-    const float vhat = vi / s_bc2[sgi];
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = p[i] - lr * (mhat / (sqrtf(vhat) + eps));
+  };
+  if (pack_block) {
+    if constexpr (PACK > 0) {
+#pragma unroll
+      for (int u = 0; u < PACK_N; ++u) {
+        update(pb.live[u], pb.idx[u], pb.g[u], pb.p[u], pb.m[u], pb.v[u]);
+        const int j = (threadIdx.x / PACK_CHAINS) + (ADAM_THREADS / PACK_CHAINS) * u;
+        if (j < 8 * PACK) s_w[j][threadIdx.x & (PACK_CHAINS - 1)] = pb.live[u] ? pb.p[u] : 0.0f;
+      }
+      __syncthreads();
+      if (threadIdx.x < PACK_CHAINS)
+        h2::pack_w1_chain<PACK>([&](int j) { return s_w[j][threadIdx.x]; }, tail.pack_din, tail.w1_split, chain,
+                                h2::W_SCALE_CRITIC);
+    }
+  } else {
+    for (;;) {
+#pragma unroll
+      for (int u = 0; u < FLAT_N; ++u)
+        update(fb.live[u], fb.idx[u], fb.g[u], fb.p[u], fb.m[u], fb.v[u]);
+      flat_base += FLAT_N * flat_stride;  // (a second batch only when the grid was capped: > 256 K parameters)
+      if (flat_base >= n_flat) break;
+#pragma unroll
+      for (int u = 0; u < FLAT_N; ++u) {
+        const int i = flat_base + u * flat_stride;
+        fb.live[u] = i < n_flat;
+        fb.idx[u] = flat_index(min(i, n_flat - 1));
+      }
+      fb.load(g, p, m, v);
+    }
   }
 
   // ---- metrics (ff_mappo.py:255-265): loss_sums = [actor_loss, entropy, value_loss] summed
@@ -172,31 +340,16 @@ __global__ __launch_bounds__(ADAM_THREADS) void clip_adam_kernel(
     const float actor_loss = loss_sums[0] * grad_scale;
     const float entropy = loss_sums[1] * grad_scale;
     const float value_loss = loss_sums[2] * grad_scale;
-    metrics_out[0] = (actor_loss - ent_coef * entropy) + vf_coef * value_loss;  // total_loss
+    metrics_out[0] = __builtin_fmaf(vf_coef, value_loss, __builtin_fmaf(-ent_coef, entropy, actor_loss));  // total_loss
     metrics_out[1] = value_loss;
     metrics_out[2] = actor_loss;
     metrics_out[3] = entropy;
   }
 
-  // ---- last arriver: count increment (every block has read the counts by the time it takes its ticket) + W1 re-split
-  if (tail.ticket != nullptr) {
-    __threadfence();  // this thread's parameter stores are visible device-wide before the block's arrival
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned int t = __hip_atomic_fetch_add(tail.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = (t == gridDim.x - 1) ? 1 : 0;
-      if (s_last) {
-        __hip_atomic_store(tail.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-        for (int k = 0; k < n_seg; ++k) count[k] += 1;
-      }
-    }
-    __syncthreads();
-    if constexpr (PACK > 0) {
-      if (s_last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the other blocks' parameter stores, not this CU's cached lines
-        h2::pack_w1_body<PACK>(p + tail.pack_offset, tail.pack_din, tail.w1_split, threadIdx.x, h2::W_SCALE_CRITIC);
-      }
-    }
+  // ---- last arriver: count increment (every block had read the counts when it took its ticket)
+  if (tail.ticket != nullptr && threadIdx.x == 0 && ticket_no == gridDim.x - 1) {
+    __hip_atomic_store(tail.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+    for (int k = 0; k < n_seg; ++k) count[k] += 1;
   }
 }
 
@@ -419,9 +572,11 @@ extern "C" int mava_ppo_finish_f32(mava_ctx* ctx, const float* slab_a, long stri
     tail.pack_din = critic_din;
     tail.w1_split = static_cast<uint4*>(slot);
   }
-  int blocks = mava_cdiv(Pa + Pc, ADAM_THREADS * 4);
+  // flat blocks for everything but the W1 range of a packing launch, which PACK_BLOCKS further blocks update and split
+  int blocks = mava_cdiv(Pa + Pc - (pack ? (critic_din + 1) * MLP_H : 0), ADAM_THREADS * 4);
   if (blocks > 256) blocks = 256;
-#define FINISH_ADAM(PK)                                                                                                \
+  if (pack) blocks += PACK_BLOCKS;
+#define FINISH_ADAM(PK)                                                                                              \
   hipLaunchKernelGGL(clip_adam_kernel<PK>, dim3(blocks), dim3(ADAM_THREADS), 0, s, p, g, m, v, count, segs, 2, grad_scale, \
                      max_norm, decay, steps_per_update, num_updates, b1, b2, eps, g + Pa + Pc, vf_coef, ent_coef,      \
                      metrics_out, tail)

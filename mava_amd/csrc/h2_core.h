@@ -219,6 +219,25 @@ __device__ __forceinline__ void pack_w1_body(const float* P, int din, uint4* __r
     out[2 * gid + 1] = __builtin_bit_cast(uint4, f.lo);
   }
 }
+// One lane's share of pack_w1_body from values that are already on chip: `tid` is the lane of the 256-thread group whose
+// fragments are written, src(j) its j-th input in k order (j = 8 s + e <-> k = 16 s + 8 h + e); the same select, scale and
+// carry sequence, so the copy is bit for bit the one pack_w1_body writes.  The Adam launch splits the weights it has just
+// updated this way, without reading them back from memory (adam.hip).
+template <int STEPS, class Src>
+__device__ __forceinline__ void pack_w1_chain(Src src, int din, uint4* __restrict__ out, int tid, float scale) {
+  const int h = (tid & 63) >> 5;
+  float carry = 0.0f;
+#pragma unroll
+  for (int i = 0; i < STEPS; ++i) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (16 * i + 8 * h + e <= din) ? src(8 * i + e) * scale : 0.0f;
+    const Frag f = split8_carry(v, carry);
+    const int gid = i * 256 + tid;
+    out[2 * gid] = __builtin_bit_cast(uint4, f.hi);
+    out[2 * gid + 1] = __builtin_bit_cast(uint4, f.lo);
+  }
+}
 // The critic's W1 / W2 are split as 16 w.  A weight of magnitude ~0.1 has its low term (|w - hi| <= 2^-11 |w| ~ 4e-5) in
 // f16's SUBNORMAL range, whose spacing is an absolute 2^-24 = 6e-8: what hi + lo then fails to represent is ~2e-7 |w| - and it
 // is the same in every batch row, so with non-negative (post-ReLU) inputs it shifts the value coherently by ~1e-8, which
