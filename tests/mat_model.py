@@ -99,10 +99,16 @@ def forward(params, obs, action, mask, n_head: int):
     """Teacher-forced pass: (log_prob of `action` (B, A), entropy (B, A), value (B, A), logits)."""
     rep, value = encoder(params["encoder"], obs, n_head)
     logits = decoder(params["decoder"], rep, shifted_onehot(action, logits_dim(params)), n_head)
+    lp, entropy = log_prob_entropy(logits, action, mask)
+    return lp, entropy, value, logits
+
+
+def log_prob_entropy(logits, action, mask):
+    """logits (..., n), action (...) -> (log_prob of `action`, entropy) of the masked Categorical."""
     logp, _ = masked_log_softmax(logits, mask)
     p = logp.exp()
     entropy = -(torch.where(p > 0, p * logp, torch.zeros_like(p))).sum(-1)
-    return logp.gather(-1, action.long().unsqueeze(-1))[..., 0], entropy, value, logits
+    return logp.gather(-1, action.long().unsqueeze(-1))[..., 0], entropy
 
 
 def logits_dim(params) -> int:
@@ -133,6 +139,11 @@ def loss(params, obs, action, mask, old_log_prob, adv, old_value, target, n_head
          vf_coef: float):
     """(total, actor_loss, value_loss, entropy) over the agent rows of a minibatch of samples (leading axis B)."""
     lp, ent, value, _ = forward(params, obs, action, mask, n_head)
+    return loss_terms(lp, ent, value, old_log_prob, adv, old_value, target, clip_eps, ent_coef, vf_coef)
+
+
+def loss_terms(lp, ent, value, old_log_prob, adv, old_value, target, clip_eps: float, ent_coef: float, vf_coef: float):
+    """The loss on the network's outputs: log-probs, entropies and values of the agent rows, any common shape."""
     mean = adv.mean()
     std = torch.sqrt(torch.clamp((adv**2).mean() - mean**2, min=0.0))
     gae = (adv - mean) / (std + 1e-8)

@@ -48,8 +48,10 @@ def _maxabs_close(got, want, what, tol=1e-6):
 
 
 # ---- attention ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,H", [(32, 1), (64, 2), (128, 4), (128, 1)])
-@pytest.mark.parametrize("A", [1, 2, 3, 5, 16, 32])
+@pytest.mark.parametrize("D,H", [(32, 1), (64, 2), (96, 4), (128, 4), (128, 1)])  # head widths 32, 24 (no power of two) and 128
+# A = 7: groups of S = 4 samples, 28 rows that do not divide the tile, a partial last group; A = 20: S = 1 under a tile's 32 rows,
+# and the 400 scores of an item take two trips of the block
+@pytest.mark.parametrize("A", [1, 2, 3, 5, 7, 16, 20, 32])
 def test_attention_forward_and_backward(dev, A, D, H):
     check, L, ptr, sp = _lib()
     g = torch.Generator().manual_seed(A * 1000 + D + H)
