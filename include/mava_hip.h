@@ -50,13 +50,17 @@ enum {
                                       is instantiated, 1 = the four-wave kernels (ppo_train_h2.hip) only; bit 1: always run the x_lo
                                       products that inputs exact in f16 skip (same bits either way: tests); for A/B measurements */
   MAVA_CTX_W8_LAUNCHES = 6,        /* diagnostic counter: ... of which on the eight-wave kernel */
-  MAVA_CTX_W1_SPLIT_FRESH = 7      /* read: 1 while the handle's pre-split W1 copy (wide f16x2 critic, 96..287 inputs) holds the W1 that
+  MAVA_CTX_W1_SPLIT_FRESH = 7,     /* read: 1 while the handle's pre-split W1 copy (wide f16x2 critic, 96..287 inputs) holds the W1 that
                                       mava_ppo_finish_f32 wrote for the critic at p + Pa, critic_din inputs.  The next
                                       mava_ppo_critic_grad_f32 of the handle clears it, whichever kernel it runs on, and skips its own
                                       re-split only when its params pointer and din are that key's; mava_ctx_set(MATMUL_MODE) clears it
                                       too.  Contract left to the caller: whoever rewrites the CONTENTS of that same parameter buffer
                                       between the finish call and the next critic launch (a copy-in, another optimiser step) must
                                       write 0 here - the next launch then re-splits W1 itself */
+  MAVA_CTX_EXACT_TILES = 8         /* diagnostic counter on the device: 32-row tiles that the blocks of the handle's wide f16x2
+                                      gradient launches (96..287 inputs) ran in the exact-input tile loop - inputs exact in f16: hi plane
+                                      only, two MFMAs per product, the next x tile staged beside this one (ppo_train_h2.hip) -, summed
+                                      over launches.  Reading it waits for the device; 0 is the only value that can be written */
 };
 int mava_ctx_create(mava_ctx** out);
 int mava_ctx_destroy(mava_ctx* ctx); /* frees the handle's workspaces; NULL is a no-op */

@@ -161,6 +161,7 @@ class Ctx:
     their first argument (None = the library defaults: exact f32)."""
 
     MATMUL_MODE, CRITIC_AGGREGATION, GAE_VARIANT, POLICY_VARIANT, H2_LAUNCHES, TRAIN_VARIANT, W8_LAUNCHES, W1_SPLIT_FRESH = 0, 1, 2, 3, 4, 5, 6, 7
+    EXACT_TILES = 8  # wide f16x2 critic: tiles run in the exact-input loop (a device counter; reading it synchronises)
 
     def __init__(self, matmul_mode: str = "f32", critic_aggregation: bool = True):
         if matmul_mode not in ("f32", "f16x2"):

@@ -20,7 +20,7 @@ extern "C" const char* mava_last_error(void) { return g_err; }
 extern "C" int mava_abi_version(void) { return 3; }  // 3: round-3 signatures (mava_ctx handle instead of process-wide setters)
 
 // ---- context handle (ctx.h) -------------------------------------------------------------------------------------------
-enum { CTX_MATMUL_MODE = 0, CTX_CRITIC_AGGREGATION = 1, CTX_GAE_VARIANT = 2, CTX_POLICY_VARIANT = 3, CTX_H2_LAUNCHES = 4, CTX_TRAIN_VARIANT = 5, CTX_W8_LAUNCHES = 6, CTX_W1_SPLIT_FRESH = 7 };
+enum { CTX_MATMUL_MODE = 0, CTX_CRITIC_AGGREGATION = 1, CTX_GAE_VARIANT = 2, CTX_POLICY_VARIANT = 3, CTX_H2_LAUNCHES = 4, CTX_TRAIN_VARIANT = 5, CTX_W8_LAUNCHES = 6, CTX_W1_SPLIT_FRESH = 7, CTX_EXACT_TILES = 8 };
 
 extern "C" int mava_ctx_create(mava_ctx** out) {
   MAVA_ARG_CHECK(out != nullptr, 0, "mava_ctx_create: null output pointer");
@@ -38,6 +38,7 @@ extern "C" int mava_ctx_create(mava_ctx** out) {
     c->w1_key_params[i] = nullptr;
     c->w1_key_din[i] = c->w1_key_steps[i] = 0;
   }
+  c->exact_tiles = nullptr;
   *out = c;
   return MAVA_OK;
 }
@@ -46,6 +47,7 @@ extern "C" int mava_ctx_destroy(mava_ctx* c) {
   if (c == nullptr) return MAVA_OK;
   for (int i = 0; i < 2; ++i)
     if (c->w1_split[i] != nullptr) (void)hipFree(c->w1_split[i]);  // (synchronises with the launches that read it)
+  if (c->exact_tiles != nullptr) (void)hipFree(c->exact_tiles);
   delete c;
   return MAVA_OK;
 }
@@ -68,6 +70,13 @@ extern "C" int mava_ctx_set(mava_ctx* c, int key, long value) {
       MAVA_ARG_CHECK(value == 0, 1, "mava_ctx_set: MAVA_CTX_W1_SPLIT_FRESH can only be cleared (0) by the caller");
       c->w1_fresh[0] = c->w1_fresh[1] = 0;
       return MAVA_OK;
+    case CTX_EXACT_TILES:
+      MAVA_ARG_CHECK(value == 0, 1, "mava_ctx_set: MAVA_CTX_EXACT_TILES can only be reset (0) by the caller");
+      if (c->exact_tiles != nullptr) {  // (the launches that add to the word first)
+        MAVA_HIP_CHECK(hipDeviceSynchronize());
+        MAVA_HIP_CHECK(hipMemset(c->exact_tiles, 0, sizeof(unsigned long long)));
+      }
+      return MAVA_OK;
     default: mava_set_error("mava_ctx_set: unknown key %d", key); return MAVA_EARG(2);
   }
 }
@@ -83,6 +92,15 @@ extern "C" int mava_ctx_get(const mava_ctx* c, int key, long* value) {
     case CTX_TRAIN_VARIANT: *value = c->train_variant; return MAVA_OK;
     case CTX_W8_LAUNCHES: *value = c->w8_launches; return MAVA_OK;
     case CTX_W1_SPLIT_FRESH: *value = c->w1_fresh[1]; return MAVA_OK;
+    case CTX_EXACT_TILES: {  // a device word: waits for the launches that add to it
+      unsigned long long n = 0;
+      if (c->exact_tiles != nullptr) {
+        MAVA_HIP_CHECK(hipDeviceSynchronize());
+        MAVA_HIP_CHECK(hipMemcpy(&n, c->exact_tiles, sizeof(n), hipMemcpyDeviceToHost));
+      }
+      *value = (long)n;
+      return MAVA_OK;
+    }
     default: mava_set_error("mava_ctx_get: unknown key %d", key); return MAVA_EARG(2);
   }
 }

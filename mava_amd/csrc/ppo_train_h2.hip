@@ -30,6 +30,8 @@
 #include "ppo_train_task.h"
 #include "ctx.h"
 
+#include <type_traits>
+
 // Operand prefetch depth of the weight-gradient products (0 = pairs of reads followed by pairs of products).  A rolling
 // prefetch (operand of product i + depth read while product i runs) was measured at depth 3 (narrow kernels) and 2 / 3 (the
 // wide kernel's loader role): actor 5.12 vs 5.10 ms per update - nothing -, critic 2.31 / 2.43 vs 2.20 ms - the extra live
@@ -136,9 +138,10 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   float* const W3s = misc + 16;  // critic: the 128 head weights (read per tile: head on the VALU, dz2 = W3[f] * dy)
   const int xs_row = L.xs_row, xs_plane = L.xs_plane;
 
-  const int tid = threadIdx.x & 255;  // thread of its 4-wave group
-  const int lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
-  const int srow = tid >> 3, l8 = tid & 7;  // staging role: row srow of the tile, 8 threads per row
+  // (not const: the wide critic makes these roots opaque between its two tile loops, see below)
+  int tid = threadIdx.x & 255;  // thread of its 4-wave group
+  int lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
+  int srow = tid >> 3, l8 = tid & 7;  // staging role: row srow of the tile, 8 threads per row
   const int din = tk.din, no = tk.no;
   const long R = (!ACTOR && tk.agg > 1) ? (long)tk.Rb : (long)tk.Rb * tk.A;
   const float invR = 1.0f / (float)((long)tk.Rb * tk.A);
@@ -201,10 +204,17 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   // per step on 96 cycles of matrix work.  A base made opaque once per tile keeps the per-step addresses inside the loop:
   // two adds from a live register.
   const uint4* w1p_lane = w1p + 2 * (w * 64 + lane);  // + 2 * 256 * s
+  // The opaque base has lost its address space: read through it the fragments came by flat_load, which counts in lgkmcnt as
+  // well as in vmcnt - every `s_waitcnt lgkmcnt(0)` behind an LDS read of the P1 loop, and the one in front of barrier A, then
+  // waited for all ring fetches in flight (the next tile's among them): the ring was one step deep in effect.  Cast back to
+  // the global address space they are global_load again and only vmcnt knows them.
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(1))) u32x4* w1_gptr;
   auto w1_fetch = [&](int s) -> Frag {
+    const w1_gptr g = (w1_gptr)w1p_lane;
     Frag f;
-    f.hi = __builtin_bit_cast(half8, w1p_lane[512 * s]);
-    f.lo = __builtin_bit_cast(half8, w1p_lane[512 * s + 1]);
+    f.hi = __builtin_bit_cast(half8, g[512 * s]);
+    f.lo = __builtin_bit_cast(half8, g[512 * s + 1]);
     return f;
   };
   float w1_carry = 0.0f;
@@ -346,11 +356,14 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   u8* const xs_dummy = reinterpret_cast<u8*>(misc + 8);  // 16 bytes nobody reads
   // wide kernel: xflag[tile parity] != 0 when some staged value of that tile's x rows has a non-zero low f16 term.  Inputs
   // exact in f16 (flags, one-hot ids, small integers: the whole global state of RobotWarehouse and of the synthetic env) leave
-  // it 0; the loader group's dW1 product then skips x_lo . dz1 (exactly 0) and the reads of that plane - same bits.
+  // it 0: such tiles run in the exact-input tile loop below (hi plane only, two products instead of three - same bits).
   unsigned* const xflag = reinterpret_cast<unsigned*>(misc + 2);
   int tpar = 0;  // parity of the tile being processed
-  auto stage_commit = [&](int buf, const float (&xr)[NR], int flag_slot = 0) {
-    u8* base = lds + L.xs + buf * 2 * xs_plane + srow * xs_row;
+  // `dst`: row 0 of the hi plane written; HI_ONLY = false also writes the low plane (xs_plane behind it), FLAG ORs the low
+  // terms' bits into xflag[flag_slot]
+  auto stage_commit = [&](auto hi_only_tag, auto flag_tag, u8* dst, const float (&xr)[NR], int flag_slot) {
+    constexpr bool HI_ONLY = decltype(hi_only_tag)::value, FLAG = decltype(flag_tag)::value;
+    u8* base = dst + srow * xs_row;
     uint32_t lo_any = 0;
 #pragma unroll
     for (int i = 0; i < NPC; ++i) {
@@ -363,8 +376,8 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 #pragma unroll
         for (int e = 0; e < 4; ++e) { _Float16 x0, x1; split1(xr[4 * i + e], x0, x1); a[e] = x0; b[e] = x1; }
         *reinterpret_cast<half4*>(qa) = a;
-        *reinterpret_cast<half4*>(qb) = b;
-        if constexpr (WIDE) {
+        if constexpr (!HI_ONLY) *reinterpret_cast<half4*>(qb) = b;
+        if constexpr (FLAG) {
           const uint2 bb = __builtin_bit_cast(uint2, b);
           lo_any |= (bb.x | bb.y) & 0x7FFF7FFFu;
         }
@@ -374,20 +387,25 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 #pragma unroll
         for (int e = 0; e < 2; ++e) { _Float16 x0, x1; split1(xr[2 * i + e], x0, x1); a[e] = x0; b[e] = x1; }
         *reinterpret_cast<half2v*>(qa) = a;
-        *reinterpret_cast<half2v*>(qb) = b;
-        if constexpr (WIDE) lo_any |= __builtin_bit_cast(uint32_t, b) & 0x7FFF7FFFu;
+        if constexpr (!HI_ONLY) *reinterpret_cast<half2v*>(qb) = b;
+        if constexpr (FLAG) lo_any |= __builtin_bit_cast(uint32_t, b) & 0x7FFF7FFFu;
       } else {
         _Float16 x0, x1;
         split1(xr[i], x0, x1);
         *reinterpret_cast<_Float16*>(qa) = x0;
-        *reinterpret_cast<_Float16*>(qb) = x1;
-        if constexpr (WIDE) lo_any |= (uint32_t)__builtin_bit_cast(uint16_t, x1) & 0x7FFFu;
+        if constexpr (!HI_ONLY) *reinterpret_cast<_Float16*>(qb) = x1;
+        if constexpr (FLAG) lo_any |= (uint32_t)__builtin_bit_cast(uint16_t, x1) & 0x7FFFu;
       }
     }
-    if constexpr (WIDE) {
+    if constexpr (FLAG) {
       if (lo_any != 0) xflag[flag_slot] = 1u;  // (every writer stores the same value)
     }
   };
+  using std::false_type;
+  using std::true_type;
+  // the two-loop form is built for the wide CRITIC only: the wide actor roles already spill 200 - 590 bytes per lane with one loop
+  constexpr bool VERSIONED = WIDE && !ACTOR;
+  using versioned_tag = std::bool_constant<VERSIONED>;
 
   const long ntiles = (R + 31) / 32;
   long it = blockIdx.x;
@@ -413,7 +431,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       }
     }
     if (LOADER) {
-      stage_commit(0, xr);
+      stage_commit(false_type{}, versioned_tag{}, lds + L.xs, xr, 0);
       cursor_advance(cs);
     }
     if (CHAIN) {
@@ -436,13 +454,13 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   __syncthreads();
 
   // per-lane LDS byte offsets
-  const SwRow rowB = sw_row(r, h);                             // step s: features 16s + 8h .. + 7 of image row r
-  const SwTr trS = sw_tr(lane);                                // transposed reads of the swizzled images
+  SwRow rowB = sw_row(r, h);                                   // step s: features 16s + 8h .. + 7 of image row r
+  SwTr trS = sw_tr(lane);                                      // transposed reads of the swizzled images
   const int i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3, g1 = (lane >> 4) & 1;
   // transposed reads: block row (8h + tq) of a 16-row step, columns (16 g1 + 4 tp) .. + 3 of a 32-column tile
-  const int trX = (8 * h + tq) * xs_row + 2 * (16 * g1 + 4 * tp);
+  int trX = (8 * h + tq) * xs_row + 2 * (16 * g1 + 4 * tp);
   const int trD = (8 * h + tq) * DY_ROW + 2 * (16 * g1 + 4 * tp);
-  const SwRow w2row = sw_row(32 * w + r, h);                   // step s: W2[32w + r][16s + 8h .. + 7]
+  SwRow w2row = sw_row(32 * w + r, h);                         // step s: W2[32w + r][16s + 8h .. + 7]
   int buf = 0;
   // narrow inputs: this wave's layer-2 operand (its 32 columns of W2, all 8 steps: 64 registers of the ~110 the role
   // leaves free) stays in registers - P2 then reads only the h1 image, half the LDS bytes of the phase
@@ -457,11 +475,34 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   }
 
   STAMP_DECL
-  for (; it < ntiles; it += gridDim.x, buf ^= (WIDE ? 0 : 1), tpar ^= 1) {
+  // Wide critic: the tile loop exists in two versions (below): an exact-input loop for tiles whose x rows are exact in f16, and the
+  // general loop.  `exact`: the tile about to run may take the exact loop; n_exact: tiles this block ran there.
+  bool exact = false;
+  unsigned n_exact = 0;
+  // One tile.  EXACT (wide critic only): the x rows of this tile have zero low terms.  Then
+  //   * only hi planes exist: the x region (2 planes) holds the hi plane of tile i in plane `tpar` and that of tile i + 1 in
+  //     plane `tpar ^ 1`; layer 1 and dW1 drop their x_lo product - an MFMA on zeros, the other two keep mfma3's order, so
+  //     every sum has the same bits;
+  //   * the loader group commits tile i + 1 behind barrier B, in its idle time, instead of between barriers E and F with
+  //     the whole block waiting; barrier F is gone.
+  // Buffer hazards of the exact loop (tile i in plane p = tpar, tile i + 1 committed into plane p ^ 1 behind barrier B(i)):
+  //   * plane p ^ 1 was last read by dW1 of tile i - 1 (loader waves, behind D(i-1)): E(i-1), A0(i), A(i) and B(i) lie between
+  //     those reads and the commit.  Its first readers are the P1 of tile i + 1: B2(i) .. E(i) lie between.
+  //   * xflag[p ^ 1] is cleared at the top of tile i (last read behind E(i-2)), set by the commit behind B(i), read behind E(i).
+  //   * E(i) stays: the loader group's layer-1 partial sums of tile i + 1 go through the dz2 image region, which the chain
+  //     group's dW2 of tile i reads behind D(i); and P1(i+1) rewrites the h1 image that dW2 reads.
+  //   * the block's last tile (have_next == false) gathers and commits row 0 into plane p ^ 1, which nobody reads again; a
+  //     flag set by that row is not looked at: the loop ends on `it`.  A block with one tile is that case at once.
+  auto tile_body = [&](auto exact_tag) __attribute__((always_inline)) {
+    constexpr bool EXACT = decltype(exact_tag)::value;
+    static_assert(!EXACT || VERSIONED, "the exact-input loop belongs to the wide critic");
     STAMP(14);
     const bool valid = (it * 32 + r) < R;
     const long itn = it + gridDim.x;
     const bool have_next = itn < ntiles;
+    if constexpr (EXACT && LOADER) {
+      if (tid == 0) xflag[tpar ^ 1] = 0u;
+    }
     uint32_t xrow_next = LOADER ? stage_row(ps_next, as_next) : 0u;
     uint32_t fr_next[NP];
 #pragma unroll
@@ -471,7 +512,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 #pragma unroll
       for (int q = 0; q < NP; ++q) asm volatile("" : "+v"(fr_next[q]));
     }
-    const u8* const XSI = lds + L.xs + buf * 2 * xs_plane;
+    const u8* const XSI = lds + L.xs + (EXACT ? tpar : 2 * buf) * xs_plane;
 
     // ---------------------------------------------------------------- P1: z1 = W1^T x^T (+ b1 through the ones column)
     f32x16 acc;
@@ -488,12 +529,22 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 #pragma unroll
       for (int s = 0; s < NW1; ++s) W1f[s] = w1_fetch(S_LO + s);
     }
-    Frag xb = read_row_frag(XSI, xs_plane, r * xs_row + 16 * h + 32 * S_LO);
+    Frag xb;
+    xb.hi = *reinterpret_cast<const half8*>(XSI + r * xs_row + 16 * h + 32 * S_LO);
+    if constexpr (!EXACT) xb.lo = *reinterpret_cast<const half8*>(XSI + xs_plane + r * xs_row + 16 * h + 32 * S_LO);
 #pragma unroll
     for (int j = 0; j < RL; ++j) {  // this group's steps s = S_LO + j
       const Frag b = xb;
-      if (j + 1 < RL) xb = read_row_frag(XSI, xs_plane, r * xs_row + 16 * h + 32 * (S_LO + j + 1));
-      acc = mfma3(W1f[j % NW1], b, acc);
+      if (j + 1 < RL) {
+        xb.hi = *reinterpret_cast<const half8*>(XSI + r * xs_row + 16 * h + 32 * (S_LO + j + 1));
+        if constexpr (!EXACT) xb.lo = *reinterpret_cast<const half8*>(XSI + xs_plane + r * xs_row + 16 * h + 32 * (S_LO + j + 1));
+      }
+      if constexpr (EXACT) {  // mfma3 without its W1_hi . x_lo product
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1f[j % NW1].lo, b.hi, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1f[j % NW1].hi, b.hi, acc, 0, 0, 0);
+      } else {
+        acc = mfma3(W1f[j % NW1], b, acc);
+      }
       if (WIDE) {
         // refill the slot consumed one step ago with step j - 1 + W1_RING of this tile
         if (j >= 1 && j - 1 + W1_RING < RL) W1f[(j - 1) % NW1] = w1_fetch(S_LO + j - 1 + W1_RING);
@@ -546,7 +597,29 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       }
       asm volatile("" : "+v"(slot_c));
     }
-    if (have_next) {
+    if constexpr (WIDE && CHAIN) {
+      // The wide chain role: cursor arithmetic, then the next tile's row loads (their addresses are known since the loop
+      // top), and the index gather of the tile after it LAST.  With the gather in front, the multiply-add that forms a row
+      // address (v_mad_u64_u32 with a 64-bit addend whose high half is undefined) was given the register of the index in
+      // flight as that high half, and the wait-count pass put s_waitcnt vmcnt(0) in front of it: the role stood still for
+      // the gather's round trip to memory, 2.3 K cycles per tile in front of barrier A (phase stamps, "gather issue").
+      if (have_next) {
+        const bool more = itn + gridDim.x < ntiles;
+        Cursor c_old[NP];
+        if (more) {
+#pragma unroll
+          for (int q = 0; q < NP; ++q) { c_old[q] = cl[q]; cursor_advance(cl[q]); }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) load_row((long)fr_next[q], n_act[q], n_f0[q], n_f1[q], n_m[q]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {
+#pragma unroll
+          for (int q = 0; q < NP; ++q) cursor_gather(c_old[q], pl_next[q], al_next[q]);
+        }
+      }
+    } else if (have_next) {
       if (LOADER && !WIDE) stage_issue(xrow_next, xr);
       const bool more = itn + gridDim.x < ntiles;
       if (more) {
@@ -652,6 +725,13 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     STAMP(5);
     __syncthreads();  // B: partial logits (and the h2 image) complete
     STAMP(6);
+    if constexpr (EXACT && LOADER) {
+      // the next tile's hi plane into the other half of the x region, in this group's idle time (hazards: see tile_body).
+      // Behind barrier B, not A: the gathers were issued just in front of A and need their round trip to memory; committed
+      // there, the chain group waited 0.4 K cycles at B for this group (phase stamps); from here to barrier D this group
+      // has 3.5 K idle cycles
+      stage_commit(true_type{}, true_type{}, lds + L.xs + (tpar ^ 1) * xs_plane, xr, tpar ^ 1);
+    }
 
     // ---------------------------------------------------------------- P3: loss, d loss / d logits (x R), dW3, dz2
     f32x16 dz;
@@ -845,7 +925,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     if constexpr (!WIDE) {
       // narrow inputs: the next tile's x rows have arrived long ago - split + store them into the other buffer (read
       // from barrier D on)
-      if (have_next) stage_commit(buf ^ 1, xr);
+      if (have_next) stage_commit(false_type{}, false_type{}, lds + L.xs + (buf ^ 1) * 2 * xs_plane, xr, 0);
     }
     STAMP(10);
     if constexpr (!WIDE) do_gw2();
@@ -853,32 +933,21 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     __syncthreads();  // D: dz1 image (narrow inputs: and the next x tile) complete
     STAMP(12);
     if constexpr (WIDE && CHAIN) do_gw2();  // beside the loader group's dW1 product
-    bool x_lo = true;
-    if constexpr (WIDE && LOADER) {
-      x_lo = __builtin_amdgcn_readfirstlane((int)xflag[tpar]) != 0 || tk.force_xlo != 0;
-      // the next tile's flag: its last readers (the tile before this one) are long past, its writers (the commit between
-      // barriers E and F below) come after this
-      if (tid == 0) xflag[tpar ^ 1] = 0u;
-    }
     if constexpr (LOADER) {
       // gW1[k][n = 32w + r] += sum_rows x[row][k] dz1[row][n]   (row din of gW1 = db1 through the ones column)
       constexpr int NPR = 2 * KT1;                          // products
-      constexpr int D1 = WIDE ? MAVA_GW_DEPTH_WIDE : GW_DEPTH;  // operand prefetch depth (see do_gw2)
-      if (WIDE && D1 > 0 && !x_lo) {  // x exact in f16: hi plane only, two products per step
-        constexpr int DP = (D1 > 0 ? (D1 < NPR ? D1 : NPR) : 1);
-        const Frag b0 = sw_read_tr(DZ1I, SW_PLANE, trS, 0, w), b1 = sw_read_tr(DZ1I, SW_PLANE, trS, 1, w);
-        half8 a[DP];
+      constexpr int D1 = WIDE ? MAVA_GW_DEPTH_WIDE : GW_DEPTH;  // operand prefetch depth of the general loop (see do_gw2)
+      if constexpr (EXACT) {  // hi plane only: mfma3 without its x_lo . dz1_hi product
 #pragma unroll
-        for (int i = 0; i < DP; ++i) a[i] = read_tr8(XSI + trX + 16 * (i / KT1) * xs_row + 2 * (32 * (i % KT1)), xs_row);
+        for (int s = 0; s < 2; ++s) {
+          const Frag b = sw_read_tr(DZ1I, SW_PLANE, trS, s, w);
 #pragma unroll
-        for (int i = 0; i < NPR; ++i) {
-          const half8 cur = a[i % DP];
-          if (i + DP < NPR) a[i % DP] = read_tr8(XSI + trX + 16 * ((i + DP) / KT1) * xs_row + 2 * (32 * ((i + DP) % KT1)), xs_row);
-          const Frag& b = (i / KT1) ? b1 : b0;
-          f32x16 c = gW1[i % KT1];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur, b.lo, c, 0, 0, 0);
-          gW1[i % KT1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur, b.hi, c, 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
+          for (int t = 0; t < KT1; ++t) {
+            const half8 a = read_tr8(XSI + trX + 16 * s * xs_row + 2 * (32 * t), xs_row);
+            const f32x16 c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b.lo, gW1[t], 0, 0, 0);
+            gW1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b.hi, c, 0, 0, 0);
+            if (t & 1) __builtin_amdgcn_sched_barrier(0);
+          }
         }
       } else if constexpr (D1 > 0) {
         constexpr int DP = D1 < NPR ? D1 : NPR;
@@ -909,11 +978,18 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     }
     STAMP(13);
     if constexpr (WIDE) {
-      __syncthreads();  // E: every reader of the (single) x tile is done
-      if constexpr (LOADER) {
-        stage_commit(0, xr, tpar ^ 1);  // (without a next tile: row 0 into a buffer nobody reads again)
+      __syncthreads();  // E: every reader of this x tile, of the dz2 image and of the h1 image is done
+      if constexpr (EXACT) {
+        // the next tile was committed behind barrier B: may it run in this loop?
+        exact = __builtin_amdgcn_readfirstlane((int)xflag[tpar ^ 1]) == 0;
+        ++n_exact;
+      } else {
+        if constexpr (LOADER) {
+          // (without a next tile: row 0 into a buffer nobody reads again)
+          stage_commit(false_type{}, false_type{}, lds + L.xs, xr, 0);
+        }
+        __syncthreads();  // F: next x tile visible
       }
-      __syncthreads();  // F: next x tile visible
     }
     if constexpr (CHAIN) {
 #pragma unroll
@@ -921,7 +997,34 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     }
     // narrow inputs: no barrier here - the next tile's P1 writes the h1 image, whose last readers (gW2) sit before
     // barrier D, and reads the other x buffer, complete since D; every other image is rewritten only behind barriers A..C
+  };
+  if constexpr (VERSIONED) {
+    // The exact-input loop runs first; the general loop takes whatever is left and never hands back (real inputs are exact
+    // throughout or not at all).  The accumulators are loop-carried variables of two consecutive loops: no loop contains a
+    // branch that merges around them (a per-tile `if` around a two-product dW1 spilled 388 registers in the loader role).
+    exact = __builtin_amdgcn_readfirstlane((int)xflag[0]) == 0 && tk.force_xlo == 0;  // (tile 0: committed by the prologue)
+    if (exact && it < ntiles) {
+      // plane 1 becomes a hi plane: its ones column (first read by the P1 of this block's second tile, barriers A0 .. E away)
+      if (CHAIN && tid < 32) *reinterpret_cast<_Float16*>(lds + L.xs + xs_plane + tid * xs_row + 2 * din) = (_Float16)1.0f;
+    }
+    for (; it < ntiles && exact; it += gridDim.x, tpar ^= 1) tile_body(true_type{});
+    // The per-lane roots of every LDS address are made opaque between the two loops: the general loop's loop-invariant
+    // addresses are then formed behind the exact loop instead of being carried (spilled) across it - each loop sees the
+    // register budget of a single loop.
+    // (each role fences what its own loop body reads: a root kept alive across the exact loop only for this fence is a spill)
+    asm volatile("" : "+v"(tid), "+v"(lane), "+v"(w), "+v"(h), "+v"(r), "+v"(trS.b0), "+v"(trS.b1), "+v"(trS.q64));
+    if constexpr (LOADER) asm volatile("" : "+v"(srow), "+v"(l8), "+v"(trX));
+    if constexpr (CHAIN) asm volatile("" : "+v"(rowB.base), "+v"(rowB.hx), "+v"(w2row.base), "+v"(w2row.hx));
+    if (n_exact != 0 && it < ntiles) {
+      // the tile at `it` has low terms; its hi plane sits in plane `tpar`, and the loader group's registers still hold its rows:
+      // committed again in the general layout (hi plane 0, lo plane 1, ones column of the lo plane 0).  Every reader of both
+      // planes is behind barrier E of the last exact tile; the barrier here orders these stores before the general loop's P1.
+      if constexpr (LOADER) stage_commit(false_type{}, false_type{}, lds + L.xs, xr, 0);
+      if (CHAIN && tid < 32) *reinterpret_cast<_Float16*>(lds + L.xs + xs_plane + tid * xs_row + 2 * din) = (_Float16)0.0f;
+      __syncthreads();
+    }
   }
+  for (; it < ntiles; it += gridDim.x, buf ^= (WIDE ? 0 : 1)) tile_body(false_type{});
 #ifdef MAVA_STAMPS
   if (tk.stamps != nullptr && blockIdx.x == 0 && lane == 0) {
     for (int i = 0; i < 16; ++i) tk.stamps[((ROLE == 2 ? 4 : 0) + w) * 16 + i] = st_acc[i];
@@ -930,6 +1033,9 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 
   // ------------------------------------------------------------------ epilogue: one slab per block (x 1/R)
   __syncthreads();
+  if constexpr (VERSIONED && CHAIN) {  // proof that the exact-input loop ran: tiles of this block it took
+    if (tid == 0 && tk.exact_tiles != nullptr) atomicAdd(tk.exact_tiles, (unsigned long long)n_exact);
+  }
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
   const int oB2 = mlp_off_b2(din), oB3 = mlp_off_b3(din, no);
   const int Pn = mlp_param_count(din, no);
@@ -1045,9 +1151,18 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
     }
     fresh = 0;
     w1p = buf;
+    // the handle's exact-tile counter (ctx.h): one device word, allocated with the first wide launch
+    if (ctx->exact_tiles == nullptr) {
+      void* word = nullptr;
+      MAVA_HIP_CHECK(hipMalloc(&word, sizeof(unsigned long long)));
+      ctx->exact_tiles = static_cast<unsigned long long*>(word);
+      MAVA_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(unsigned long long), s));
+    }
   }
+  TrainTask tkl = tk;
+  tkl.exact_tiles = WIDE ? ctx->exact_tiles : nullptr;
   g_train_last_instance = train_instance_id(2, ACTOR, false, WIDE, NO, S1, XV);
-  hipLaunchKernelGGL((ppo_train_h2_kernel<NO, S1, ACTOR, WIDE, XV>), dim3(n_slab), dim3(WIDE ? 512 : 256), L.end, s, tk, L,
+  hipLaunchKernelGGL((ppo_train_h2_kernel<NO, S1, ACTOR, WIDE, XV>), dim3(n_slab), dim3(WIDE ? 512 : 256), L.end, s, tkl, L,
                      w1p);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;

@@ -30,6 +30,7 @@ struct TrainTask {
   long slab_stride;
   unsigned long long* stamps;  // diagnostic builds only (-DMAVA_STAMPS): per-phase cycle sums of block 0
   int force_xlo;           // f16x2 kernels: always run the x_lo products (MAVA_CTX_TRAIN_VARIANT bit 1; tests: same bits either way)
+  unsigned long long* exact_tiles;  // wide f16x2 kernels: device word every block adds its exact-loop tiles to (MAVA_CTX_EXACT_TILES), or null
 };
 
 // ppo_train_h2.hip: the same fused kernel on v_mfma_f32_32x32x16_f16 with every operand split into two f16 terms

@@ -1,5 +1,8 @@
 """Diagnostic: per-phase cycle shares of the fused PPO train kernels (needs a library built with
-MAVA_HIPCC_EXTRA="-DMAVA_STAMPS").  Prints, per wave of block 0, the cycles spent in each phase."""
+MAVA_HIPCC_EXTRA="-DMAVA_STAMPS").  Prints, per wave of block 0, the cycles spent in each phase.
+    python tools/train_stamps.py [f16x2] [w4] [exact]
+`exact`: observations exact in f16 (bits), as RobotWarehouse's are - the wide critic then runs its exact-input tile loop and
+the eight-wave actor its two-product layer 1; without it the inputs are Gaussian (general loop, three products)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -8,6 +11,7 @@ from mava_amd._lib import Ctx, lib
 
 dev = torch.device("cuda", 0)
 MODE = 1 if (len(sys.argv) > 1 and sys.argv[1] == "f16x2") else 0
+EXACT = "exact" in sys.argv[2:]
 TE, A, O, nA = 128 * 4096, 4, 66, 5
 Rb = TE // 2
 rng = np.random.default_rng(0)
@@ -23,7 +27,7 @@ names_w8 = ["P1 mfma", "P1 relu+image", "gather issue", "barrier A", "P2 mfma", 
             "barrier B2", "gW3+dz2+image", "gW2", "barrier C", "dh1+dz1 image", "gW1", "loop top", "-"]
 l = lib()
 ctx = Ctx("f16x2" if MODE == 1 else "f32")
-if len(sys.argv) > 2 and sys.argv[2] == "w4":
+if "w4" in sys.argv[2:]:
     ctx.set(ctx.TRAIN_VARIANT, 1)
 l.mava_debug_set_stamps.argtypes = [C.c_void_p]
 stamps = torch.zeros(128, dtype=torch.int64, device=dev)  # waves 0-3 (chain / only group), 4-7 (loader group of wide launches)
@@ -33,14 +37,14 @@ for which in ("critic", "actor"):
     if which == "critic":
         din = A * O
         params = torch.randn(ops.mlp_param_count(din, 1), device=dev) * 0.05
-        x = torch.randn(TE, din, device=dev)
+        x = (torch.rand(TE, din, device=dev) < 0.2).float() if EXACT else torch.randn(TE, din, device=dev)
         ov, tg = torch.randn(TE * A, device=dev), torch.randn(TE * A, device=dev)
         slab = torch.zeros(256, params.numel() + 2, device=dev)
         run = lambda: ops.ppo_critic_grad(params, x, A, ov, tg, perm, 0, Rb, A, 0.2, 0.5, slab, ctx=ctx)
     else:
         din = A + O
         params = torch.randn(ops.mlp_param_count(din, nA), device=dev) * 0.05
-        x = torch.randn(TE * A, din, device=dev)
+        x = (torch.rand(TE * A, din, device=dev) < 0.2).float() if EXACT else torch.randn(TE * A, din, device=dev)
         mask = (torch.rand(TE * A, nA, device=dev) > 0.2).to(torch.uint8); mask[:, 0] = 1
         act = torch.zeros(TE * A, dtype=torch.int32, device=dev)
         olp, adv = -torch.rand(TE * A, device=dev) - 1.0, torch.randn(TE * A, device=dev)
@@ -54,6 +58,8 @@ for which in ("critic", "actor"):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); run(); b.record(); torch.cuda.synchronize()
     s8 = stamps.cpu().numpy().reshape(8, 16)
+    if which == "critic" and MODE == 1:
+        print(f"   (exact-loop tiles of the three launches: {ctx.get(ctx.EXACT_TILES)} of {3 * -(-Rb // 32)})")
     if ctx.get(ctx.W8_LAUNCHES) > w8_before:  # eight equal waves: print waves 0-3 and wave 4 (the SIMD partner of wave 0)
         tot = s8.sum(1)
         ntile = -(-(Rb * A) // 32 // 256)
