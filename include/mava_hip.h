@@ -537,7 +537,8 @@ int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* c
  * block) gathered per batch row; W (K x N) row-major with row stride ldw; Y T32 (rows x N).  accumulate: start from
  * the existing Y (K-chunked products for inputs wider than 384).  With MAVA_CTX_MATMUL_MODE = 1 T32 inputs run on
  * split-f16 operands (rec_dense_h2.hip: 3 f16 MFMAs per product, f32 accumulate, operands must sit in f16 range -
- * see grad_scale below); row-major inputs always run the exact-f32 kernel.  y_ld (<= 0: N) is the feature count of the
+ * see grad_scale below); row-major inputs, N in 129..256 and K above 288 with a bias always run the exact-f32 kernel
+ * ("Support envelope of the dense and X^T Y products").  y_ld (<= 0: N) is the feature count of the
  * y / gate tiles: a call with a column block of W and y + 32 * n0 writes features [n0, n0 + N) of a wider matrix. */
 int mava_rec_dense_f32(const mava_ctx* ctx, const float* x, int x_rowmajor, const int32_t* idx, int Rm, int E, int A,
                        int x_share, int x_ld, int accumulate, const float* w, int ldw, const float* bias,

@@ -94,12 +94,13 @@ __global__ __launch_bounds__(256, 1) void rec_dense_kernel(DenseTask tk) {
       }
     }
   };
-  // raw gate loads of n-tile 0 for tile `it` (features past N clamp to the tile's first feature)
+  // raw gate loads of n-tile 0 for tile `it` (features past N clamp to feature 32 w, which exists: pf_gate has 32 w < N;
+  // the lane's own first feature 32 w + 4 h may not)
   auto load_gate = [&](int it, float (&g)[16]) {
     const int fb = 32 * w + 4 * h;
     const float* const go = tk.gate + ((long)it * tk.y_ld + fb) * 32 + j;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) g[r] = go[(fb + (r & 3) + 8 * (r >> 2) < N) ? DOFF(r) : 0];
+    for (int r = 0; r < 16; ++r) g[r] = go[(fb + (r & 3) + 8 * (r >> 2) < N) ? DOFF(r) : -4 * h * 32];
   };
   auto init_acc = [&](int it, f32x16 (&acc)[NTW]) {
 #pragma unroll
@@ -439,6 +440,8 @@ int launch_dense_rm(const DenseTask& tk, hipStream_t s) {
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL((rec_dense_kernel<NB, NTW, RM, FULLK>), dim3(blocks), dim3(256), lb, s, tk);
   MAVA_LAUNCH_CHECK();
+  g_rec_product_last_instance =
+      rec_product_instance_id(1, 1, RM ? REC_FORM_ROWMAJOR : (FULLK ? REC_FORM_FULLK : REC_FORM_T32), NB, NTW);
   return MAVA_OK;
 }
 
@@ -451,8 +454,9 @@ int launch_dense(const DenseTask& tk, hipStream_t s) {
   }
   if (tk.K == 16 * NB) return launch_dense_rm<NB, NTW, false, true>(tk, s);
   if (NTW == 1) return launch_dense_rm<NB, 1, false, false>(tk, s);  // any width: clamped operand addresses
-  mava_set_error("mava_rec_dense_f32: T32 input width K=%d is not instantiated for N=%d (T32 inputs: K <= 32, or K in "
-                 "{64,96,128,192,288,384} with N <= 128, or K = 128 / 192 with N <= 384 / 256)", tk.K, tk.N);
+  mava_set_error("mava_rec_dense_f32: T32 input width K=%d is not instantiated for N=%d (exact f32, T32 inputs: any K with "
+                 "N <= 128, K = 128 or 192 with N <= 256, K = 128 with N <= 384; the f16x2 arithmetic also takes any K <= 128 "
+                 "with N in 257..384)", tk.K, tk.N);
   return MAVA_EARG(9);
 }
 
@@ -469,10 +473,16 @@ int launch_xty(const XtyTask& tk, int n_slab, hipStream_t s) {
   }
   hipLaunchKernelGGL((rec_xty_kernel<KT, NTW>), dim3(n_slab), dim3(256), lb, s, tk);
   MAVA_LAUNCH_CHECK();
+  g_rec_product_last_instance = rec_product_instance_id(2, 1, tk.x_rowmajor ? REC_FORM_ROWMAJOR : REC_FORM_T32, KT, NTW);
   return MAVA_OK;
 }
 
 }  // namespace
+
+// Diagnostic (not part of include/mava_hip.h, like mava_debug_rollout_last_instance): which dense / X^T Y kernel instance the
+// last launch of this family used in this process (rec_task.h: rec_product_instance_id).
+int g_rec_product_last_instance = 0;
+extern "C" int mava_debug_rec_product_last_instance(void) { return g_rec_product_last_instance; }
 
 extern "C" int mava_rec_dense_f32(const mava_ctx* ctx, const float* x, int x_rowmajor, const int32_t* idx, int Rm, int E, int A,
                                   int x_share, int x_ld, int accumulate, const float* w, int ldw,

@@ -203,11 +203,11 @@ __global__ __launch_bounds__(256, 1) void rec_dense_h2_kernel(DenseTask tk) {
       }
     }
   };
-  auto load_gate = [&](int it, float (&g)[16]) {
+  auto load_gate = [&](int it, float (&g)[16]) {  // features past N clamp to feature 32 w (< N under pf_gate)
     const int fb = 32 * w + 4 * h;
     const float* const go = tk.gate + ((long)it * tk.y_ld + fb) * 32 + j;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) g[r] = go[(fb + (r & 3) + 8 * (r >> 2) < N) ? DOFF(r) : 0];
+    for (int r = 0; r < 16; ++r) g[r] = go[(fb + (r & 3) + 8 * (r >> 2) < N) ? DOFF(r) : -4 * h * 32];
   };
   const bool pf_gate = (NTW == 1) && tk.gate != nullptr && (32 * w < N);
 
@@ -461,6 +461,7 @@ int launch_dense_h2(const DenseTask& tk, hipStream_t s) {
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL((rec_dense_h2_kernel<NB, NTW, LEAN>), dim3(blocks), dim3(256), lb, s, tk);
   MAVA_LAUNCH_CHECK();
+  g_rec_product_last_instance = rec_product_instance_id(1, 2, LEAN ? REC_FORM_LEAN : REC_FORM_T32, NB, NTW);
   return MAVA_OK;
 }
 
@@ -476,6 +477,7 @@ int launch_xty_h2(const XtyTask& tk, int n_slab, hipStream_t s) {
   if (n_slab > tk.rows / 32) return 1;  // every block must own a tile (its prologue stages one)
   hipLaunchKernelGGL((rec_xty_h2_kernel<KT, NTW>), dim3(n_slab), dim3(256), lb, s, tk);
   MAVA_LAUNCH_CHECK();
+  g_rec_product_last_instance = rec_product_instance_id(2, 2, REC_FORM_T32, KT, NTW);
   return MAVA_OK;
 }
 

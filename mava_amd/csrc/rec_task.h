@@ -82,6 +82,18 @@ using mava_rec::ext_row;
 using mava_rec::XtyTask;
 using mava_rec::gather_row;
 
+// Diagnostic (rec_dense.hip: mava_debug_rec_product_last_instance): the kernel instance the last dense / X^T Y launch of
+// this process used, OP * 1000000 + FAMILY * 100000 + FORM * 10000 + P * 10 + NTW.  OP 1 = dense (P = NB), 2 = X^T Y (P = KT);
+// FAMILY 1 = exact f32 (rec_dense_kernel / rec_xty_kernel), 2 = f16x2 (rec_dense_h2_kernel / rec_xty_h2_kernel);
+// FORM 0 = T32 input (dense f32: the clamped-address form), 1 = FULLK, 2 = row-major gathered input, 3 = LEAN.
+// Written on the host in the launch_* templates; a refused launch leaves it unchanged, an f16x2 fall-through reports the
+// exact-f32 instance that ran.
+extern int g_rec_product_last_instance;
+enum { REC_FORM_T32 = 0, REC_FORM_FULLK = 1, REC_FORM_ROWMAJOR = 2, REC_FORM_LEAN = 3 };
+inline int rec_product_instance_id(int op, int family, int form, int p, int ntw) {
+  return op * 1000000 + family * 100000 + form * 10000 + p * 10 + ntw;
+}
+
 // f16x2 forms (rec_dense_h2.hip); T32 inputs only.  Return 1 when the shape is not instantiated (caller runs the f32 kernel).
 int mava_rec_dense_h2_launch(const DenseTask& tk, hipStream_t s);
 int mava_rec_xty_h2_launch(const XtyTask& tk, int n_slab, hipStream_t s);

@@ -132,11 +132,13 @@ def test_rec_dense_rowmajor_gather_and_xty(dev, rec_mode):
         check(lib().mava_rec_gather_t32_f32(ptr(src_d), ptr(idx_d), Rm, E, A, share, K, K, rows, kp, ptr(xin), stream_ptr()), "gather")
         got_x = _from_t32(xin.cpu().numpy(), rows, kp)
         assert np.array_equal(got_x[:, :K], xs.astype(np.float32)) and not got_x[:, K:].any(), "gathered T32 input"
-        if rec_mode == 1:  # (the exact-f32 kernel reads padded T32 inputs only when K is a multiple of 16)
-            check(lib().mava_rec_dense_f32(_cp(), ptr(xin), 0, None, 0, 0, 0, 1, kp, 0, ptr(w_d), N, ptr(b_d), None, ptr(y), 0, K, N, rows, 1,
-                                           stream_ptr()), "dense on the gathered input")
-            assert_close(_from_t32(y.cpu().numpy(), rows, N), np.maximum(xs @ w.astype(np.float64) + b, 0), 1e-5,
-                         "dense, gathered T32")
+        # both modes: x_ld = kp > K is read at run time (exact f32: the clamped-address form, whatever K)
+        y.fill_(float("nan"))
+        check(lib().mava_rec_dense_f32(_cp(), ptr(xin), 0, None, 0, 0, 0, 1, kp, 0, ptr(w_d), N, ptr(b_d), None, ptr(y), 0, K, N, rows, 1,
+                                       stream_ptr()), "dense on the gathered input")
+        assert_close(_from_t32(y.cpu().numpy(), rows, N), np.maximum(xs @ w.astype(np.float64) + b, 0), 1e-5,
+                     "dense, gathered T32")
+        assert not torch.isnan(y).any(), "dense, gathered T32: every output written"
         slab = torch.zeros((5, K * N + N), device=dev)
         check(lib().mava_rec_xty_f32(_cp(), ptr(xin), 0, None, 0, 0, 0, 1, kp, ptr(dy_d), 0, None, 0, 0, K, N, rows, 1, 1.0, ptr(slab), slab.shape[1], 5,
                                      stream_ptr()), "xty on the gathered input")
