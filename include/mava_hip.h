@@ -80,6 +80,10 @@ int mava_gae_f32(const mava_ctx* ctx, const float* reward, const float* value, c
  * out[0..n) = a bijection of [0, n) determined by (seed, counter): 16-round keyed Feistel network over [0, 2^ceil(log2 n))
  * with cycle walking (mava_amd/csrc/permutation.hip; bit-exact restatement oracle/permutation.py).  1 <= n < 2^31. */
 int mava_permutation_i32(long n, uint64_t seed, uint64_t counter, int32_t* out, mava_stream_t s);
+/* The n_perm (1..16) epoch permutations of an update in one launch: out[k * out_stride + i] = what
+ * mava_permutation_i32(n, seed, counter + k, .) writes at i, bit for bit.  out_stride >= n. */
+int mava_permutation_batched_i32(long n, uint64_t seed, uint64_t counter, int n_perm, int32_t* out, long out_stride,
+                                 mava_stream_t s);
 
 /* ---- optimiser: optax.chain(clip_by_global_norm, adam(eps=1e-5)) per network,
  *      mava/systems/ppo/ff_mappo.py:359-366 (definition) and :241-250 (application);
@@ -524,6 +528,23 @@ int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* c
                         int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
                         uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
                         uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda, mava_stream_t s);
+/* mava_rollout_ff_f32 that also writes what a caller otherwise copies or adds after it: last_reward / last_done (E, A) =
+ * reward[T-1] / done[T-1], and, when step_counter is not NULL, *step_counter += T (one thread, at the kernel's end: pass
+ * it for ONE replica of an update; the launch counts from t0 and never reads it). */
+int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                             int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                             uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                             int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                             uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                             uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                             float* last_reward, uint8_t* last_done, int32_t* step_counter, mava_stream_t s);
+/* The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of agents_view
+ * (T+1, E, A, obs_dim) f32, global_state (T+1, E, gs_dim) f32 (NULL with gs_dim 0: none), action_mask (T+1, E, A,
+ * n_actions) u8 and step_count (T+1, E, A) i32, in one launch.  Slots 1..T are not touched. */
+int mava_rollout_carry(int T, int E, int A, int obs_dim, long gs_dim, int n_actions, float* agents_view,
+                       float* global_state, uint8_t* action_mask, int32_t* step_count, mava_stream_t s);
 
 /* ---- recurrent systems (rec_ippo / rec_mappo): mava/networks.py:238-331 (ScannedRNN GRU with
  *      reset-on-done, RecurrentActor, RecurrentValueNet), mava/systems/ppo/rec_mappo.py:91-149,

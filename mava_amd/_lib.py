@@ -39,6 +39,7 @@ _SIGNATURES = {
     "mava_ctx_get": [vp, i32, vp],
     "mava_gae_f32": [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp],
     "mava_permutation_i32": [lng, u64, u64, vp, vp],
+    "mava_permutation_batched_i32": [lng, u64, u64, i32, vp, lng, vp],
     "mava_clip_adam": [vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(f32), i32, f32, f32, i32, i32, i32,
                        f32, f32, f32, vp, f32, f32, vp, vp],
     "mava_slab_reduce_f32": [vp, i32, lng, i32, i32, vp, vp],
@@ -88,6 +89,9 @@ _SIGNATURES = {
     "mava_sac_actor_grad_f32": [i32] * 4 + [f32] + [vp] * 9 + [i32, i32, i32, f32, f32] + [vp] * 3 + [i32, vp],
     "mava_sac_alpha_loss_f32": [i32, i32, vp, vp, f32, vp, vp, vp],
     "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18 + [vp, vp, f32, f32, vp],
+    "mava_rollout_ff_tail_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
+                                + [vp, vp, f32, f32, vp, vp, vp, vp],
+    "mava_rollout_carry": [i32, i32, i32, i32, lng, i32, vp, vp, vp, vp, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],
     "mava_rec_gather_t32_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],

@@ -94,6 +94,16 @@ __global__ __launch_bounds__(256) void adv_stats_kernel(const float* __restrict_
   partials += (long)blockIdx.y * 2 * gridDim.x;
   double s1 = 0.0, s2 = 0.0;
   const long stride = (long)gridDim.x * 256;
+  // A row of 2, 4 or 8 agents on a base aligned to the row is fetched with one 8-byte or one / two 16-byte loads (a
+  // permuted index puts every lane on its own cache line: A separate 4-byte loads touched that line A times); the
+  // values are added in the same order as the scalar loop, so the partials keep their bits.
+  const uintptr_t adv_addr = reinterpret_cast<uintptr_t>(adv);
+  const int vec = (A == 4 && (adv_addr & 15) == 0) ? 4 : (A == 8 && (adv_addr & 15) == 0) ? 8 : (A == 2 && (adv_addr & 7) == 0) ? 2 : 0;
+  auto add = [&](float f) {
+    const double v = (double)f;
+    s1 += v;
+    s2 += v * v;
+  };
   for (long b0 = (long)blockIdx.x * 256 + threadIdx.x; b0 < Rb; b0 += 4 * stride) {
     long p[4];
 #pragma unroll
@@ -102,14 +112,38 @@ __global__ __launch_bounds__(256) void adv_stats_kernel(const float* __restrict_
       const long bc = b < Rb ? b : b0;
       p[u] = idx ? (long)idx[bc] : idx_base + bc;
     }
+    if (vec == 4) {
+      float4 q[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (b0 + u * stride < Rb) {
-        const float* row = adv + p[u] * A;
-        for (int a = 0; a < A; ++a) {
-          const double v = (double)row[a];
-          s1 += v;
-          s2 += v * v;
+      for (int u = 0; u < 4; ++u) q[u] = *reinterpret_cast<const float4*>(adv + p[u] * 4);  // (p[u] is in range: see bc)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (b0 + u * stride < Rb) { add(q[u].x); add(q[u].y); add(q[u].z); add(q[u].w); }
+      }
+    } else if (vec == 8) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (b0 + u * stride < Rb) {
+          const float4 q0 = *reinterpret_cast<const float4*>(adv + p[u] * 8);
+          const float4 q1 = *reinterpret_cast<const float4*>(adv + p[u] * 8 + 4);
+          add(q0.x); add(q0.y); add(q0.z); add(q0.w);
+          add(q1.x); add(q1.y); add(q1.z); add(q1.w);
+        }
+      }
+    } else if (vec == 2) {
+      float2 q[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) q[u] = *reinterpret_cast<const float2*>(adv + p[u] * 2);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (b0 + u * stride < Rb) { add(q[u].x); add(q[u].y); }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (b0 + u * stride < Rb) {
+          const float* row = adv + p[u] * A;
+          for (int a = 0; a < A; ++a) add(row[a]);
         }
       }
     }

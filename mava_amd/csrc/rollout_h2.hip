@@ -72,17 +72,40 @@ struct RolloutArgs {
   float* info_return; int32_t* info_length; uint8_t* info_terminal;  // (T, E)
   float* adv; float* tgt;  // (T, E, A) or null: GAE of ff_mappo.py:112-139 in the kernel's tail
   float gamma, lam;
+  // mava_rollout_ff_tail_f32 (null otherwise): reward / done of the last step, (E, A), and the device step counter
+  float* last_reward; uint8_t* last_done; int32_t* step_counter;
 };
+
+// The kernel's arguments read again from the argument segment AT THE POINT OF USE.  The ~40 pointers and seeds of
+// RolloutArgs are loaded at the kernel's entry when they are used through the by-value parameter, and whatever the step
+// loop or the tail needs then stays live across the whole loop: twice the scalar registers a wave has, i.e. > 200 values
+// parked in lanes of vector registers and fetched back one v_readlane at a time, 240 of them per step on the critic waves
+// alone.  A phase that takes its pointers through this reference fetches them with a few wide scalar loads from the
+// (cached, read-only) argument segment instead; the empty asm keeps those loads from being hoisted back to the entry.
+// RolloutArgs is the kernel's first parameter: offset 0 of the segment.
+#define MAVA_AS4 __attribute__((address_space(4)))
+__device__ __forceinline__ const MAVA_AS4 RolloutArgs& args_here() {
+  const MAVA_AS4 RolloutArgs* p = (const MAVA_AS4 RolloutArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *p;
+}
+
+// x / d for x * d < 65536 with m = 65536 / d + 1: (x * m) >> 16 is exact there (x = q d + s: the excess x (d - 65536 % d) /
+// (65536 d) stays below 1 / d).  d is fixed for a launch; a division by a runtime value is ~35 instructions.
+__device__ __forceinline__ uint32_t div_small(uint32_t x, uint32_t m) { return __umul24(x, m) >> 16; }
 
 struct RolloutLds {  // byte offsets
   int xa, xa_row, xa_plane, xc, xc_row, xc_plane, h1, wl, ypa, ypc, act, mask, small, gum, xlf, end;
 };
-constexpr int W1_REG_STEPS = 12;  // layer-1 steps of the critic kept in registers; further steps live in LDS as fragments
+// layer-1 steps of the critic kept in registers; further steps live in LDS as fragments.  (11 measured the same as 12 once
+// the step loop was free of scratch, and fills the headline instance's LDS to 600 bytes below the CU's 160 KiB.)
+constexpr int W1_REG_STEPS = 12;
 
+// (constexpr: in the kernel every offset is an immediate of its LDS instruction, not a scalar register held over the step loop)
 template <int NO, int S1A, int S1C, bool SHARED>
-RolloutLds make_rollout_lds() {
+constexpr RolloutLds make_rollout_lds() {
   constexpr int KTA = (S1A + 1) / 2, KTC = (S1C + 1) / 2;
-  RolloutLds L;
+  RolloutLds L{};
   L.xa = 0;
   L.xa_row = 2 * 32 * KTA + 16;
   L.xa_plane = 32 * L.xa_row;
@@ -108,8 +131,9 @@ RolloutLds make_rollout_lds() {
 
 // ROLE 0: actor group (threads 0-255), ROLE 1: critic group (threads 256-511).  Both run the same barrier sequence.
 template <int NO, int S1A, int S1C, bool SHARED, int ROLE>
-__device__ __forceinline__ void rollout_body(const RolloutArgs& a, const RolloutLds& L, u8* lds) {
+__device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   constexpr bool ACT_ROLE = ROLE == 0;
+  constexpr RolloutLds L = make_rollout_lds<NO, S1A, S1C, SHARED>();
   const int t512 = threadIdx.x;          // thread of the workgroup (sample / env phases)
   const int tid = t512 & 255, lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
   const int A = a.A, O = a.O, no = a.no, W = A + O, E = a.E;
@@ -128,7 +152,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
   unsigned* const XLF = reinterpret_cast<unsigned*>(lds + L.xlf);
   float* const YPA = reinterpret_cast<float*>(lds + L.ypa);
   float* const YPC = reinterpret_cast<float*>(lds + L.ypc);
-  const int xa_row = L.xa_row, xa_plane = L.xa_plane, xc_row = L.xc_row, xc_plane = L.xc_plane;
+  constexpr int xa_row = L.xa_row, xa_plane = L.xa_plane, xc_row = L.xc_row, xc_plane = L.xc_plane;
 
   // ---------------------------------------------------------------- prologue
   for (int i = t512 * 16; i < L.end; i += 512 * 16) *reinterpret_cast<uint4*>(lds + i) = make_uint4(0, 0, 0, 0);
@@ -233,9 +257,10 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
   __syncthreads();
 
   // bookkeeping: thread 256 + i (first wave of the critic group) owns agent row i (env e0 + i / A, agent i % A)
-  const int bk_le = tid / A, bk_ag = tid - bk_le * A;
+  const int lgA = __builtin_ctz((unsigned)A);  // A divides 64: shifts and masks, no divisions by A in the step loop
+  const int bk_le = tid >> lgA, bk_ag = tid & (A - 1);
   const bool bk_on = !ACT_ROLE && tid < 64 && (e0 + bk_le) < E;
-  const long bk_k = (long)(e0 + bk_le) * A + bk_ag;  // (e, a) index
+  const long bk_k = (long)e0 * A + tid;  // (e, a) index: (e0 + bk_le) * A + bk_ag
   int sc_reg = bk_on ? a.step_count[bk_k] : 0;
   float rr_reg = 0.0f, er_reg = 0.0f;
   int rl_reg = 0, el_reg = 0;
@@ -339,6 +364,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
       // Philox4x32-10 call and two logarithms per lane were ~1.8 K of that phase's 5.5 K cycles).  One call per
       // (row, four outputs): thread (row = tid / 4, c = tid % 4) draws outputs 4 c .. 4 c + 3; same counters, same values.
       const int grow = tid >> 2, c = tid & 3;
+      const auto& a = args_here();  // (shadows the parameter: see args_here)
       if (c < NO / 4) {
         const uint32_t gid = a.row_offset + (uint32_t)(e0 * A + grow);
         const Philox4 rnd = philox4x32_10(gid, noise_step, (uint32_t)c, POLICY_STREAM, a.pseed_lo, a.pseed_hi);
@@ -444,12 +470,22 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
   // divisions.
   const int rows_ok = min(64, (E - e0) * A), envs_ok = min(EB, E - e0);  // valid rows / envs of this block
   const int AO = A * O;
+  const uint32_t no_m = 65536u / (uint32_t)no + 1u, nch_m = 65536u / nch + 1u;  // div_small: 64 no * no, 64 nch * nch < 65536
+  // write_out's pair / quad paths: 256 / (W / 2) and 256 / (A O / 4) with their div_small factors (256 * 136 < 65536)
+  const int tid_w = tid, wo_q = (W >> 1) > 0 ? (W >> 1) : 1, gs_q = (AO >> 2) > 0 ? (AO >> 2) : 1;
+  const int wo_dr = 256 / wo_q, gs_dr = 256 / gs_q;
+  const uint32_t wo_m = 65536u / (uint32_t)wo_q + 1u, gs_m = 65536u / (uint32_t)gs_q + 1u;
   auto write_out = [&](long slot, bool part_gs) {  // part_gs: the global state (actor group, after sampling); else the rest
+    const auto& a = args_here();  // (shadows the parameter: see args_here)
+    // The cursors' start values depend on the thread alone.  Computed from a thread id the compiler cannot see through,
+    // they are two instructions here (div_small) instead of registers held, and on the critic waves spilled, over the loop.
+    int tid = tid_w;
+    asm volatile("" : "+v"(tid));
     if (!part_gs) {
       float* dst = a.agents_view + (slot * EA + (long)e0 * A) * W;
       if ((W & 1) == 0) {  // pairs: 4-byte LDS reads, 8-byte stores (row bases are multiples of 8 bytes)
-        const int W2 = W >> 1, d_r = 256 / W2, d_f = 256 - d_r * W2;
-        int row = tid / W2, f = tid - row * W2;
+        const int W2 = W >> 1, d_r = wo_dr, d_f = 256 - d_r * W2;
+        int row = (int)div_small((uint32_t)tid, wo_m), f = tid - row * W2;
         for (int j = tid; j < 64 * W2; j += 256) {
           if (row < rows_ok) {
             const u8* xa = lds + L.xa + (row >> 5) * 2 * xa_plane + (row & 31) * xa_row;
@@ -475,8 +511,8 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
     if (part_gs && SHARED && a.global_state != nullptr) {
       float* dst = a.global_state + (slot * E + e0) * (long)AO;
       if ((AO & 3) == 0) {  // quads: 8-byte LDS reads, 16-byte stores
-        const int Q = AO >> 2, d_r = 256 / Q, d_f = 256 - d_r * Q;
-        int le = tid / Q, k = tid - le * Q;
+        const int Q = AO >> 2, d_r = gs_dr, d_f = 256 - d_r * Q;
+        int le = (int)div_small((uint32_t)tid, gs_m), k = tid - le * Q;
         for (int j = tid; j < EB * Q; j += 256) {
           if (le < envs_ok) {
             const half4 v = *reinterpret_cast<const half4*>(lds + L.xc + le * xc_row + 8 * k);
@@ -498,15 +534,18 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
     if (!part_gs) {
       uint8_t* dst = a.action_mask + (slot * EA + (long)e0 * A) * no;
       for (int j = tid; j < rows_ok * no; j += 256) {
-        const int row = j / no, o = j - row * no;
+        const int row = (int)div_small((uint32_t)j, no_m), o = j - row * no;
         dst[j] = MASK[row * 32 + o];
       }
     }
   };
 
-  for (int t = 0; t < a.T; ++t) {
-    const uint32_t step = a.t0 + (uint32_t)t;
+  const int T_steps = a.T;
+  const uint32_t t0 = a.t0;
+  for (int t = 0; t < T_steps; ++t) {
+    const uint32_t step = t0 + (uint32_t)t;
     forward(true, true, step);
+    const auto& a = args_here();  // (shadows the parameter for the sample phase: see args_here)
     // ---------------------------------------------------------------- S: sample, log-prob, value -> slot t
     // (the sample and observation-generation code runs on the actor group: the critic group's registers are full of
     // weights; it writes the values and does the per-agent bookkeeping meanwhile)
@@ -540,7 +579,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
           best = take ? bo : best;
         }
         const float lp = group_allreduce<NO>((o == best) ? logp : 0.0f, add_op);
-        const int e = e0 + row / A;
+        const int e = e0 + (row >> lgA);
         if (o == 0) {
           ACT[row] = best;
           if (e < E) {
@@ -551,8 +590,8 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
         }
       }
     } else {
-      if (tid < 64 && (e0 + tid / A) < E) {
-        a.value[(long)t * EA + (long)e0 * A + tid] = value_of(SHARED ? tid / A : tid);
+      if (tid < 64 && (e0 + (tid >> lgA)) < E) {
+        a.value[(long)t * EA + (long)e0 * A + tid] = value_of(SHARED ? (tid >> lgA) : tid);
       }
       if (t > 0) write_out((long)t, false);  // slot t = what the env phase of step t - 1 produced (slot 0 came from memory)
     }
@@ -562,12 +601,13 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
     RSTAMP(5);
     // ---------------------------------------------------------------- E: env.step -> slot t + 1 (HBM f32 + LDS images)
     {
+      const auto& a = args_here();  // (the env phase's own fetch)
       const uint32_t tn = step + 1;
       const long slot = (long)(t + 1);
       const uint32_t n_view = (uint32_t)(64 * nch);  // (row, chunk) items of the block
       for (uint32_t i = ACT_ROLE ? (uint32_t)tid : n_view; i < n_view; i += 256) {
-        const uint32_t row = i / nch, c = i - row * nch;
-        const uint32_t le = row / A, ag = row - le * A, e = e0 + le;
+        const uint32_t row = div_small(i, nch_m), c = i - row * nch;
+        const uint32_t le = row >> lgA, ag = row - (le << lgA), e = e0 + le;
         if ((int)e >= E) continue;
         const uint32_t ent = (a.env_offset + e) * A + ag;
         const Philox4 rv = philox4x32_10(ent, tn, c, ENV_STREAM, a.eseed_lo, a.eseed_hi);
@@ -617,7 +657,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
       // wave of the critic group, idle in this phase - on the actor group's lanes with c == 0 every one of its waves ran it
       if (!ACT_ROLE && tid >= 64 && tid < 128) {
         const uint32_t row = (uint32_t)(tid - 64);
-        const uint32_t le = row / A, ag = row - le * A, e = e0 + le;
+        const uint32_t le = row >> lgA, ag = row - (le << lgA), e = e0 + le;
         if ((int)e < E) {
           const uint32_t ent = (a.env_offset + e) * A + ag;
           u8* xa = lds + L.xa + (row >> 5) * 2 * xa_plane + (row & 31) * xa_row;
@@ -677,58 +717,95 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Rollout
     for (int i = 0; i < 8; ++i) g_rollout_stamps[(ACT_ROLE ? 0 : 8) + i] = rs_acc[i];
 #endif
   // ------------------------------------------------------------------ bootstrap value (ff_mappo.py:109-110)
-  write_out((long)a.T, ACT_ROLE);  // the last observation
+  write_out((long)T_steps, ACT_ROLE);  // the last observation
   forward(!ACT_ROLE, false, 0u);
+  {
+  const auto& a = args_here();  // (the tail's pointers are fetched here, not carried through the loop)
+  float lv = 0.0f;
   if (bk_on) {
-    const float lv = value_of(SHARED ? tid / A : tid);
+    lv = value_of(SHARED ? (tid >> lgA) : tid);
     a.last_val[bk_k] = lv;
-    if (a.adv != nullptr) {
-      // GAE (ff_mappo.py:117-136) for this thread's (env, agent) column, reading back the reward / value / done it
-      // wrote itself during the rollout: delta = r + gamma V' (1 - d) - V; gae = delta + gamma lambda (1 - d) gae.
-      // Eight steps' loads go out together, then the sequential f32 recurrence; no separate pass over the trajectory.
-      float g = 0.0f, nv = lv;
-      const float gl = a.gamma * a.lam;
-      for (int tb = a.T; tb > 0; tb -= 8) {
-        float rw[8], vv[8];
-        uint8_t dd[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int t = tb - 1 - i;
-          const long k = (long)(t >= 0 ? t : 0) * EA + bk_k;
-          rw[i] = a.reward[k]; vv[i] = a.value[k]; dd[i] = a.done[k];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int t = tb - 1 - i;
-          if (t >= 0) {
-            const float nd = dd[i] ? 0.0f : 1.0f;
-            const float delta = rw[i] + a.gamma * nv * nd - vv[i];
-            g = delta + gl * nd * g;
-            const long k = (long)t * EA + bk_k;
-            a.adv[k] = g;
-            a.tgt[k] = g + vv[i];
-            nv = vv[i];
-          }
-        }
-      }
-    }
-  }
-  if (bk_on) {
     a.step_count[bk_k] = sc_reg;
     if (bk_ag == 0) {
       a.run_return[e0 + bk_le] = rr_reg; a.run_length[e0 + bk_le] = rl_reg;
       a.ep_return[e0 + bk_le] = er_reg; a.ep_length[e0 + bk_le] = el_reg;
     }
+    if (a.last_reward != nullptr) {  // reward / done of the last step: what this thread stored at t = T - 1
+      const long k = (long)(a.T - 1) * EA + bk_k;
+      a.last_reward[bk_k] = a.reward[k];
+      a.last_done[bk_k] = a.done[k];
+    }
+  }
+  if (a.adv != nullptr) {
+    // GAE (ff_mappo.py:117-136): delta = r + gamma V' (1 - d) - V; gae = delta + gamma lambda (1 - d) gae, for the block's
+    // 64 (env, agent) columns.  The images and the W1 fragments below L.ypa are dead after the bootstrap pass (value_of
+    // reads the head partials behind them): ALL 512 threads bring the block's reward / value / done columns into that LDS
+    // with every load in flight, the 64 column threads run the sequential f32 recurrence from LDS and leave adv / tgt in
+    // place of reward / value, and all threads store them, consecutive lanes on consecutive addresses.  (One wave loading
+    // eight steps at a time made T / 8 dependent round trips to memory while seven waves had finished.)  A rollout
+    // longer than the LDS holds goes in chunks of TC steps, the last chunk first, g and V' carried in registers.
+    const int T = a.T;
+    const int TC = min(T, (L.ypa / (64 * 9)) & ~7);
+    float* const RW = reinterpret_cast<float*>(lds);  // [TC][64] reward, then adv
+    float* const VV = RW + TC * 64;                   // [TC][64] value, then tgt
+    u8* const DD = reinterpret_cast<u8*>(VV + TC * 64);
+    const long col0 = (long)e0 * A;
+    const float gl = a.gamma * a.lam;
+    float g = 0.0f, nv = lv;
+    for (int tb = T; tb > 0; tb -= TC) {
+      const int t_lo = max(tb - TC, 0), n = (tb - t_lo) * 64;
+      __syncthreads();  // the previous chunk's stores have read the LDS
+      for (int i0 = t512; i0 < n; i0 += 512 * 8) {
+        float rw[8], vv[8];
+        uint8_t dd[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {  // (an entry past the chunk or the valid columns re-reads a valid one)
+          const int j = min(i0 + 512 * i, n - 1);
+          const long k = (long)(t_lo + (j >> 6)) * EA + col0 + min(j & 63, rows_ok - 1);
+          rw[i] = a.reward[k]; vv[i] = a.value[k]; dd[i] = a.done[k];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int j = i0 + 512 * i;
+          if (j < n) { RW[j] = rw[i]; VV[j] = vv[i]; DD[j] = dd[i]; }
+        }
+      }
+      __syncthreads();
+      if (bk_on) {
+#pragma unroll 8
+        for (int t = tb - 1; t >= t_lo; --t) {
+          const int j = (t - t_lo) * 64 + tid;
+          const float rw = RW[j], vv = VV[j];
+          const float nd = DD[j] ? 0.0f : 1.0f;
+          const float delta = rw + a.gamma * nv * nd - vv;
+          g = delta + gl * nd * g;
+          RW[j] = g;
+          VV[j] = g + vv;
+          nv = vv;
+        }
+      }
+      __syncthreads();
+      for (int j = t512; j < n; j += 512) {
+        if ((j & 63) < rows_ok) {
+          const long k = (long)(t_lo + (j >> 6)) * EA + col0 + (j & 63);
+          a.adv[k] = RW[j];
+          a.tgt[k] = VV[j];
+        }
+      }
+    }
+  }
+  // (one thread of the launch: no block reads the counter, every block takes t0 from the arguments)
+  if (!ACT_ROLE && blockIdx.x == 0 && tid == 0 && a.step_counter != nullptr) *a.step_counter += a.T;
   }
 }
 
 template <int NO, int S1A, int S1C, bool SHARED>
-__global__ __launch_bounds__(512, 2) void rollout_h2_kernel(RolloutArgs a, RolloutLds L) {
+__global__ __launch_bounds__(512, 2) void rollout_h2_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) u8 lds[];
   if (threadIdx.x < 256) {
-    rollout_body<NO, S1A, S1C, SHARED, 0>(a, L, lds);
+    rollout_body<NO, S1A, S1C, SHARED, 0>(a, lds);
   } else {
-    rollout_body<NO, S1A, S1C, SHARED, 1>(a, L, lds);
+    rollout_body<NO, S1A, S1C, SHARED, 1>(a, lds);
   }
 }
 
@@ -737,7 +814,7 @@ int g_rollout_last_instance = 0;  // diagnostic: which template instance the las
 template <int NO, int S1A, int S1C, bool SHARED>
 int launch_rollout(const RolloutArgs& a, hipStream_t s) {
   g_rollout_last_instance = NO * 100000 + S1A * 1000 + S1C * 10 + (SHARED ? 1 : 0);
-  const RolloutLds L = make_rollout_lds<NO, S1A, S1C, SHARED>();
+  constexpr RolloutLds L = make_rollout_lds<NO, S1A, S1C, SHARED>();
   MAVA_ARG_CHECK(L.end <= 163840, 8, "mava_rollout_ff_f32: %d bytes of LDS exceed the 160 KiB of a CU", L.end);
   // (more than half a CU's LDS whatever the layout needs - the benchmarked layouts take ~150 KB anyway: two rollouts launched
   // side by side, the replicas of update_batch_size > 1, are never placed on one CU while others idle)
@@ -749,7 +826,7 @@ int launch_rollout(const RolloutArgs& a, hipStream_t s) {
     attr_set = true;
   }
   const int EB = 64 / a.A;
-  hipLaunchKernelGGL((rollout_h2_kernel<NO, S1A, S1C, SHARED>), dim3(mava_cdiv(a.E, EB)), dim3(512), lds_bytes, s, a, L);
+  hipLaunchKernelGGL((rollout_h2_kernel<NO, S1A, S1C, SHARED>), dim3(mava_cdiv(a.E, EB)), dim3(512), lds_bytes, s, a);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }
@@ -768,15 +845,15 @@ extern "C" int mava_debug_get_rollout_stamps(unsigned long long* out16) {
 // test can assert WHICH instantiation it checked (tests/test_gpu_learner.py).
 extern "C" int mava_debug_rollout_last_instance(void) { return g_rollout_last_instance; }
 
-extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                                   hipStream_t s) {
+static int rollout_ff_impl(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                           int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                           uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                           int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                           int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                           int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                           uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                           uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                           float* last_reward, uint8_t* last_done, int32_t* step_counter, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 1 && A >= 1 && O >= 2 && T >= 1 && n_actions >= 1 && time_limit >= 1, 0,
                  "mava_rollout_ff_f32: bad shape E=%d A=%d O=%d T=%d nA=%d", E, A, O, T, n_actions);
   MAVA_ARG_CHECK(actor_params && critic_params && step_count && run_return && run_length && ep_return && ep_length &&
@@ -799,6 +876,7 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
   a.info_terminal = info_terminal;
   MAVA_ARG_CHECK((adv == nullptr) == (tgt == nullptr), 1, "mava_rollout_ff_f32: adv and tgt go together");
   a.adv = adv; a.tgt = tgt; a.gamma = gamma; a.lam = gae_lambda;
+  a.last_reward = last_reward; a.last_done = last_done; a.step_counter = step_counter;
   if (critic_shared) {
     if (s1a == 5 && s1c == 17 && A >= 4) return launch_rollout<8, 5, 17, true>(a, s);  // RWARE tiny / small-4ag (O 66, A 4)
 #ifndef MAVA_FAST_BUILD
@@ -813,4 +891,91 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
   if (s1a <= 2) return launch_rollout<8, 2, 2, false>(a, s);
 #endif
   return 1;
+}
+
+extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                   hipStream_t s) {
+  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
+                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
+                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
+                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, nullptr, nullptr,
+                         nullptr, s);
+}
+
+// mava_rollout_ff_f32 that also leaves what the caller copied or added after it: last_reward / last_done (E, A) = reward /
+// done of step T - 1, and *step_counter += T when step_counter is not null (one replica of an update passes it; the
+// kernel itself counts from t0).
+extern "C" int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions, const float* critic_params,
+                                        int critic_shared, int E, int A, int O, int T, int time_limit,
+                                        uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
+                                        uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
+                                        int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                                        float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
+                                        int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
+                                        float* last_val, float* info_return, int32_t* info_length, uint8_t* info_terminal,
+                                        float* adv, float* tgt, float gamma, float gae_lambda, float* last_reward,
+                                        uint8_t* last_done, int32_t* step_counter, hipStream_t s) {
+  MAVA_ARG_CHECK(last_reward && last_done, 1, "mava_rollout_ff_tail_f32: null pointer argument");
+  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
+                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
+                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
+                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
+                         last_done, step_counter, s);
+}
+
+// The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of the four observation
+// arrays of a (T + 1, ...) trajectory in ONE launch (blockIdx.y = array).  Copies go in 16-byte pieces where the array's
+// base and its slot size allow, else in 4-byte or single-byte pieces.
+namespace {
+struct CarryArgs {
+  uint8_t* base[4];
+  long slot_bytes[4];
+  int T;
+};
+template <typename V>
+__device__ __forceinline__ void carry_copy(uint8_t* dst, const uint8_t* src, long bytes) {
+  const long nv = bytes / (long)sizeof(V), stride = (long)gridDim.x * blockDim.x;
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long i = i0; i < nv; i += stride) reinterpret_cast<V*>(dst)[i] = reinterpret_cast<const V*>(src)[i];
+  for (long i = nv * (long)sizeof(V) + i0; i < bytes; i += stride) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void rollout_carry_kernel(CarryArgs c) {
+  uint8_t* const dst = c.base[blockIdx.y];
+  const long bytes = c.slot_bytes[blockIdx.y];
+  if (dst == nullptr || bytes <= 0) return;
+  const uint8_t* const src = dst + (long)c.T * bytes;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src);
+  if ((al & 15) == 0) carry_copy<uint4>(dst, src, bytes);
+  else if ((al & 3) == 0) carry_copy<uint32_t>(dst, src, bytes);
+  else carry_copy<uint8_t>(dst, src, bytes);
+}
+}  // namespace
+
+// E, A, obs_dim, gs_dim, n_actions: agents_view (T + 1, E, A, obs_dim) f32, global_state (T + 1, E, gs_dim) f32 or null,
+// action_mask (T + 1, E, A, n_actions) u8, step_count (T + 1, E, A) i32
+extern "C" int mava_rollout_carry(int T, int E, int A, int obs_dim, long gs_dim, int n_actions, float* agents_view,
+                                  float* global_state, uint8_t* action_mask, int32_t* step_count, hipStream_t s) {
+  MAVA_ARG_CHECK(T >= 1 && E >= 1 && A >= 1 && obs_dim >= 1 && gs_dim >= 0 && n_actions >= 1, 0,
+                 "mava_rollout_carry: bad shape T=%d E=%d A=%d obs_dim=%d gs_dim=%ld nA=%d", T, E, A, obs_dim, gs_dim, n_actions);
+  MAVA_ARG_CHECK(agents_view && action_mask && step_count && (gs_dim == 0 || global_state), 1,
+                 "mava_rollout_carry: null pointer argument");
+  CarryArgs c = {};
+  c.T = T;
+  c.base[0] = reinterpret_cast<uint8_t*>(agents_view); c.slot_bytes[0] = (long)E * A * obs_dim * 4;
+  c.base[1] = gs_dim ? reinterpret_cast<uint8_t*>(global_state) : nullptr; c.slot_bytes[1] = (long)E * gs_dim * 4;
+  c.base[2] = action_mask; c.slot_bytes[2] = (long)E * A * n_actions;
+  c.base[3] = reinterpret_cast<uint8_t*>(step_count); c.slot_bytes[3] = (long)E * A * 4;
+  long most = 0;
+  for (int i = 0; i < 4; ++i) most = c.slot_bytes[i] > most ? c.slot_bytes[i] : most;
+  const long blocks = mava_cdiv(most, 256L * 16 * 4);  // four 16-byte pieces per thread of the largest array
+  hipLaunchKernelGGL(rollout_carry_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks), 4), dim3(256), 0, s, c);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
 }

@@ -374,17 +374,15 @@ class FFLearner:
                 action=rep.action, value=rep.value, reward=rep.reward, log_prob=rep.log_prob, done=rep.done,
                 last_val=rep.last_val, info_return=rep.info_return[n], info_length=rep.info_length[n],
                 info_terminal=rep.info_terminal[n], adv=rep.adv, tgt=rep.tgt, gamma=float(s.gamma),
-                gae_lambda=float(s.gae_lambda))
+                gae_lambda=float(s.gae_lambda), last_reward=rep.last_reward, last_done=rep.last_done,
+                step_counter=self.step_dev if u == 0 else None)  # (the launch leaves all three: nothing follows it)
               if not ok:
                 assert u == 0
                 self.fused_rollout = False
                 return False
-              rep.last_reward.copy_(rep.reward[self.T - 1])
-              rep.last_done.copy_(rep.done[self.T - 1])
         if side:
             for st in self._roll_streams:
                 main.wait_stream(st)
-        self.step_dev.add_(self.T)
         return True
 
     def _rollout_body(self) -> None:
@@ -604,15 +602,16 @@ class FFLearner:
     def _permutations(self) -> List[torch.Tensor]:
         """ff_mappo.py:272-273: one permutation of the T*E rows per epoch, identical on every replica and rank (the
         reference hands the same PRNG key to all of them, :417-426): mava_permutation_i32 keyed by (seed, a running
-        epoch counter) - one 5 us launch each, where torch.randperm's sort passes were ~1 ms of device time per update
-        at T*E = 524 288.  Written into persistent buffers (read by the kernels of this update only)."""
+        epoch counter) - one launch for the K epochs (up to 16 per launch), where torch.randperm's sort passes were
+        ~1 ms of device time per update at T*E = 524 288.  Written into persistent buffers (read by the kernels of this
+        update only)."""
         if not hasattr(self, "_perm_bufs"):
             self._perm_all = torch.empty((self.K, self.T * self.E), dtype=torch.int32, device=self.device)
             self._perm_bufs = [self._perm_all[k] for k in range(self.K)]
             self._stats_all = torch.empty((self.U, self.K * self.M, self.stats.shape[0], 2), dtype=torch.float64, device=self.device)
-        for buf in self._perm_bufs:
-            ops.permutation(self.T * self.E, self.seed, self.perm_count, out=buf)
-            self.perm_count += 1
+        for k0 in range(0, self.K, 16):  # row k: counter perm_count + k
+            ops.permutation_batched(self.T * self.E, self.seed, self.perm_count + k0, self._perm_all[k0 : k0 + 16])
+        self.perm_count += self.K
         return self._perm_bufs
 
     def update(self, n: int, permutations: Optional[List[torch.Tensor]] = None) -> None:
@@ -636,10 +635,7 @@ class FFLearner:
                 self._minibatch(n, k, mb, perm)
         # the bootstrap observation becomes the first observation of the next rollout
         for rep in self.reps:
-            rep.agents_view[0].copy_(rep.agents_view[self.T])
-            rep.global_state[0].copy_(rep.global_state[self.T])
-            rep.action_mask[0].copy_(rep.action_mask[self.T])
-            rep.step_count[0].copy_(rep.step_count[self.T])
+            ops.rollout_carry(rep.agents_view, rep.global_state, rep.action_mask, rep.step_count)
 
     def learn(self, learner_state: LearnerState) -> ExperimentOutput:
         """LearnerFn (mava/types.py:154): num_updates_per_eval updates, asynchronous on the current

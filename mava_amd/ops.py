@@ -41,6 +41,39 @@ def permutation(n: int, seed: int, counter: int, out: Optional[torch.Tensor] = N
     return out
 
 
+def permutation_batched(n: int, seed: int, counter: int, out: torch.Tensor) -> torch.Tensor:
+    """out[k] = permutation(n, seed, counter + k) for every row k of the (K, n) int32 tensor out, in one launch
+    (mava_permutation_batched_i32)."""
+    _req(out, torch.int32, "out")
+    if out.dim() != 2 or out.shape[1] != n or out.stride(1) != 1 or out.stride(0) < n:
+        raise ValueError(f"out: expected a (K, {n}) tensor with contiguous rows, got {tuple(out.shape)}")
+    check(lib().mava_permutation_batched_i32(n, seed & (2**64 - 1), counter & (2**64 - 1), out.shape[0], ptr(out),
+                                             out.stride(0), stream_ptr()), "mava_permutation_batched_i32")
+    return out
+
+
+def rollout_carry(agents_view: torch.Tensor, global_state: Optional[torch.Tensor], action_mask: torch.Tensor,
+                  step_count: torch.Tensor) -> None:
+    """Slot T -> slot 0 of the observation arrays of a (T + 1, E, ...) trajectory in one launch (mava_rollout_carry)."""
+    T1, E, A, W = agents_view.shape
+    _req(agents_view, torch.float32, "agents_view")
+    _req(action_mask, torch.uint8, "action_mask")
+    if tuple(action_mask.shape[:3]) != (T1, E, A) or action_mask.dim() != 4:
+        raise ValueError(f"action_mask: expected ({T1}, {E}, {A}, n_actions), got {tuple(action_mask.shape)}")
+    _req(step_count, torch.int32, "step_count", (T1, E, A))
+    gs_dim = 0
+    if global_state is not None and global_state.numel() > 0:
+        _req(global_state, torch.float32, "global_state")
+        if global_state.shape[0] != T1 or global_state.shape[1] != E:
+            raise ValueError(f"global_state: expected ({T1}, {E}, ...), got {tuple(global_state.shape)}")
+        gs_dim = global_state.numel() // (T1 * E)
+    if T1 < 2:
+        raise ValueError("a trajectory has at least two slots")
+    check(lib().mava_rollout_carry(T1 - 1, E, A, W, gs_dim, action_mask.shape[3], ptr(agents_view),
+                                   ptr(global_state) if gs_dim else None, ptr(action_mask), ptr(step_count), stream_ptr()),
+          "mava_rollout_carry")
+
+
 def gae(reward, value, done, last_val, gamma: float, gae_lambda: float, last_done=None, out=None, ctx: Optional[Ctx] = None):
     """(advantages, targets) for time-major (T, ...) inputs; see mava_gae_f32."""
     T = reward.shape[0]
@@ -463,9 +496,11 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
                time_limit: int, policy_seed: int, env_seed: int, t0: int, row_offset: int, env_offset: int,
                reward_mode: int, env_state, agents_view, global_state, action_mask, obs_step_count, action, value,
                reward, log_prob, done, last_val, info_return, info_length, info_terminal, adv=None, tgt=None,
-               gamma: float = 0.99, gae_lambda: float = 0.95) -> bool:
+               gamma: float = 0.99, gae_lambda: float = 0.95, last_reward=None, last_done=None, step_counter=None) -> bool:
     """The whole rollout of one replica in one launch (mava_rollout_ff_f32).  Returns False when the library does not
-    instantiate the shape - the caller then steps policy_step / env.step_into per time step."""
+    instantiate the shape - the caller then steps policy_step / env.step_into per time step.
+    last_reward / last_done (E, A): also written by the launch (= reward[T-1], done[T-1]); step_counter (1,) int32:
+    advanced by T at the launch's end (mava_rollout_ff_tail_f32)."""
     W = A + O
     _req(actor_params, torch.float32, "actor_params")
     _req(critic_params, torch.float32, "critic_params")
@@ -493,15 +528,25 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
     for name, t, dt in (("run_return", env_state.run_return, torch.float32), ("run_length", env_state.run_length, torch.int32),
                         ("ep_return", env_state.ep_return, torch.float32), ("ep_length", env_state.ep_length, torch.int32)):
         _req(t, dt, name, (E,))
-    rc = lib().mava_rollout_ff_f32(
+    args = (
         ptr(actor_params), n_actions, ptr(critic_params), int(critic_shared), E, A, O, T, time_limit,
         policy_seed & 0xFFFFFFFFFFFFFFFF, env_seed & 0xFFFFFFFFFFFFFFFF, t0 & 0xFFFFFFFF, row_offset & 0xFFFFFFFF,
         env_offset & 0xFFFFFFFF, reward_mode, ptr(env_state.step_count), ptr(env_state.run_return),
         ptr(env_state.run_length), ptr(env_state.ep_return), ptr(env_state.ep_length), ptr(agents_view),
         ptr(global_state) if critic_shared else None, ptr(action_mask), ptr(obs_step_count), ptr(action), ptr(value),
         ptr(reward), ptr(log_prob), ptr(done), ptr(last_val), ptr(info_return), ptr(info_length), ptr(info_terminal),
-        ptr(adv), ptr(tgt), gamma, gae_lambda, stream_ptr())
+        ptr(adv), ptr(tgt), gamma, gae_lambda)
+    if last_reward is None and last_done is None and step_counter is None:
+        name = "mava_rollout_ff_f32"
+        rc = lib().mava_rollout_ff_f32(*args, stream_ptr())
+    else:
+        name = "mava_rollout_ff_tail_f32"
+        _req(last_reward, torch.float32, "last_reward", (E, A))
+        _req(last_done, torch.uint8, "last_done", (E, A))
+        if step_counter is not None:
+            _req(step_counter, torch.int32, "step_counter", (1,))
+        rc = lib().mava_rollout_ff_tail_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), stream_ptr())
     if rc == 1:
         return False
-    check(rc, "mava_rollout_ff_f32")
+    check(rc, name)
     return True
