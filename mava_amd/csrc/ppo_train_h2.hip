@@ -43,6 +43,18 @@
 #ifndef MAVA_GW_DEPTH_WIDE
 #define MAVA_GW_DEPTH_WIDE 0
 #endif
+// Wide critic, exact-input loop: layer 1 of tile i + 1 on the loader group, under the chain group's dz2 and P4 phases of tile i
+// (see tile_body).  In halves of the layer's S1 K-steps: 0 = none (layer 1 at the top of the tile, split between the groups),
+// 1 = P1_EARLY = S1 / 2 (the loader group's own range early, the chain group's in place), 2 = P1_EARLY = S1 (the chain group
+// runs no layer-1 product).  Only these three keep the bits: z1 is (partial over [0, S1 / 2)) + (partial over [S1 / 2, S1)), each
+// from zero in step order, and a range cut anywhere else would change the order of an f32 sum.
+#ifndef MAVA_P1_EARLY_HALVES
+#define MAVA_P1_EARLY_HALVES 2
+#endif
+// register ring of the early pass, in K-steps (the loader group's staging registers are dead behind its commit)
+#ifndef MAVA_P1_EARLY_RING
+#define MAVA_P1_EARLY_RING 3
+#endif
 
 namespace {
 
@@ -66,7 +78,7 @@ constexpr int STATS_BLOCKS = 128;  // == ppo_train.hip (mava_adv_stats_blocks)
 #endif
 
 struct H2Layout {  // byte offsets into the dynamic LDS array (all multiples of 16)
-  int h1, dz2, dz1, w2, xs, xs_plane, xs_row, dy, yp, agg, small, end;
+  int h1, dz2, dz1, w2, xs, xs_plane, xs_row, dy, yp, agg, small, relu, end;
 };
 
 // WIDE (input width > 95): the layer-1 weights stream from a pre-split global copy through a register ring and the
@@ -88,7 +100,8 @@ H2Layout make_h2_layout(bool actor) {
   L.agg = L.dy + (actor ? 2 * DY_PLANE : 0);
   L.small = L.agg + 8 * 33 * 4;  // f32: b2[128] | b3[32] | misc[16] | W3[128] (critic)
   L.small = (L.small + 15) & ~15;
-  L.end = L.small + (128 + 32 + 16 + 128) * 4;
+  L.relu = L.small + (128 + 32 + 16 + 128) * 4;  // WIDE: layer 1's ReLU bits, one word per lane of a group (early layer 1)
+  L.end = L.relu + (WIDE ? 256 * 4 : 0);
   return L;
 }
 constexpr int W2_PLANE = 128 * SW_ROW;  // (the images of this kernel are the swizzled ones of h2_core.h; regions keep IMG_BYTES)
@@ -136,6 +149,13 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   float* const B3s = B2s + 128;
   float* const misc = B3s + 32;
   float* const W3s = misc + 16;  // critic: the 128 head weights (read per tile: head on the VALU, dz2 = W3[f] * dy)
+  uint32_t* const RELU1 = reinterpret_cast<uint32_t*>(lds + L.relu);  // WIDE: [256 lanes of a group], see P1_EARLY
+  // the two-loop form is built for the wide CRITIC only: the wide actor roles already spill 200 - 590 bytes per lane with one loop
+  constexpr bool VERSIONED = WIDE && !ACTOR;
+  // exact-input loop: K-steps of the NEXT tile's layer 1 that the loader group runs behind barrier B2 (MAVA_P1_EARLY_HALVES)
+  constexpr int P1_EARLY = VERSIONED ? MAVA_P1_EARLY_HALVES * (S1 / 2) : 0;
+  static_assert(MAVA_P1_EARLY_HALVES >= 0 && MAVA_P1_EARLY_HALVES <= 2, "P1_EARLY is 0, S1 / 2 or S1");
+  constexpr bool EARLY = P1_EARLY > 0, EARLY_ALL = EARLY && P1_EARLY == S1;
   const int xs_row = L.xs_row, xs_plane = L.xs_plane;
 
   // (not const: the wide critic makes these roots opaque between its two tile loops, see below)
@@ -219,7 +239,9 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   };
   float w1_carry = 0.0f;
 #pragma unroll
-  for (int s = 0; s < (CHAIN ? NW1 : 0); ++s) {  // (the loader group of WIDE launches fills its ring at the start of each P1)
+  // (the loader group of WIDE launches fills its ring at the start of each P1; P1_EARLY == S1: the chain group's ring is filled
+  // in front of the general loop, the exact loop does not use it)
+  for (int s = 0; s < ((CHAIN && !EARLY_ALL) ? NW1 : 0); ++s) {
     if (WIDE) {
       W1f[s] = w1_fetch(S_LO + s);
     } else {
@@ -403,8 +425,6 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   };
   using std::false_type;
   using std::true_type;
-  // the two-loop form is built for the wide CRITIC only: the wide actor roles already spill 200 - 590 bytes per lane with one loop
-  constexpr bool VERSIONED = WIDE && !ACTOR;
   using versioned_tag = std::bool_constant<VERSIONED>;
 
   const long ntiles = (R + 31) / 32;
@@ -493,9 +513,75 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   //     group's dW2 of tile i reads behind D(i); and P1(i+1) rewrites the h1 image that dW2 reads.
   //   * the block's last tile (have_next == false) gathers and commits row 0 into plane p ^ 1, which nobody reads again; a
   //     flag set by that row is not looked at: the loop ends on `it`.  A block with one tile is that case at once.
+  // Early layer 1 (P1_EARLY > 0, exact loop only): behind B2(i) the loader group, which would wait at C(i) and D(i), runs
+  // P1_EARLY K-steps of tile i + 1's layer 1 - steps [S1 - P1_EARLY, S1) - into eC (steps below S1 / 2: the chain group's range
+  // of the split) and eL (the loader group's range), each from zero in step order, W1_lo . x_hi before W1_hi . x_hi: the two
+  // partial sums of the split, bit for bit.  It keeps them over its dW1(i) and hands over at the top of tile i + 1, behind E(i):
+  // with P1_EARLY == S1 it forms z1 = eC + eL (chain partial + loader partial, as the chain group adds them), scales, applies the
+  // ReLU and writes the split h1 image and the ReLU bits of each lane (RELU1[tid]: P4 of the chain lane with the same wave and
+  // lane masks with them - bits taken from the image would lose an activation that rounds to zero in both f16 terms); the chain
+  // group then runs no layer-1 product, fetches no W1 and there is no barrier A0.  With P1_EARLY == S1 / 2 it writes eL through
+  // the exchange and the chain group's own range stays in place.  The first exact tile's sums are produced in front of the loop.
+  // The loader group's tile with an early pass: hand-over, gathers of tile i + 1 | A | commit into plane p ^ 1, W1 ring prefetch
+  // | B | steps [0, GB) | B2 | steps [GB, GC) | C | the rest | D | dW1 | E.  (Gathers at the top and the commit behind A, not B:
+  // this group has nothing else to do in front of B any more; measured with the commit behind B and the pass behind B2: 199 - 201
+  // against 191 - 193 us per launch.)
+  // Hazards of the early pass:
+  //   * it reads plane p ^ 1 behind B(i); the commit into that plane, behind A(i), is ordered before it by B(i) and behind the
+  //     plane's last readers (dW1 of tile i - 1) by E(i-1).  xflag[p ^ 1] is cleared at the top of tile i, in front of A(i).
+  //     The W1 ring is prefetched behind the commit, into the staging registers that are dead there: tile i + 1's rows are
+  //     NOT kept in registers up to E(i) any more - the one switch to the general loop gathers them again (xrow_keep);
+  //   * dW2(i) reads the h1 image and the dz2 region (the exchange) up to E(i): the hand-over writes behind E(i), in front of
+  //     A0(i+1) / A(i+1); RELU1 is read behind A(i+1) and rewritten behind E(i+1);
+  //   * the pass is UNCONDITIONAL.  When tile i + 1 has low terms (xflag[p ^ 1], looked at behind E(i) as before) or does not
+  //     exist (have_next == false: the dummy commit of row 0), the pass still runs on whatever hi plane the commit left - valid
+  //     LDS contents and W1 addresses - and its sums are dropped: the loop ends at its bottom as it always did and the general
+  //     loop runs that tile's layer 1 itself.  One wasted pass per block and launch, in waiting time of the loader group.  Skipping
+  //     it was built as a loop exit between B2 and C, with the second half of the tile repeated behind the loop: that form
+  //     spilled 360 (P1_EARLY == S1) / 444 (S1 / 2) registers, in both roles (a per-tile branch is what spilled 388 before).
+  //     The sums of the block's first tile are produced in front of the loop, unconditionally for the same reason;
+  //   * a block with one tile: sums in front of the loop, hand-over, a dropped pass on the dummy commit, end.
+  constexpr int ER = MAVA_P1_EARLY_RING, SB = S1 - P1_EARLY;
+  // steps [0, GB) of the pass run between B and B2 (the chain group's loss phase, 0.5 K cycles), [GB, GC) between B2 and C
+  // (dz2, 1.5 K), the rest between C and D (P4, 1.9 K)
+  constexpr int GB = P1_EARLY / 9, GC = GB + (P1_EARLY * 7) / 18;
+  f32x16 eC, eL;
+  Frag W1e[(EARLY && LOADER) ? ER : 1];
+  auto early_fill = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int g = 0; g < ER && g < P1_EARLY; ++g) W1e[g] = w1_fetch(SB + g);
+  };
+  auto early_steps = [&](auto g0_tag, auto g1_tag, const u8* xsi) __attribute__((always_inline)) {
+    constexpr int G0 = decltype(g0_tag)::value, G1 = decltype(g1_tag)::value;
+    if constexpr (G0 < G1) {
+      half8 xh = *reinterpret_cast<const half8*>(xsi + r * xs_row + 16 * h + 32 * (SB + G0));
+#pragma unroll
+      for (int g = G0; g < G1; ++g) {
+        const half8 b = xh;
+        if (g + 1 < G1) xh = *reinterpret_cast<const half8*>(xsi + r * xs_row + 16 * h + 32 * (SB + g + 1));
+        if (g == 0 || SB + g == S1 / 2) {  // first step of a range: its sum starts from zero
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            if (SB + g < S1 / 2) eC[q] = 0.0f; else eL[q] = 0.0f;
+          }
+        }
+        if (SB + g < S1 / 2) {
+          eC = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1e[g % ER].lo, b, eC, 0, 0, 0);
+          eC = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1e[g % ER].hi, b, eC, 0, 0, 0);
+        } else {
+          eL = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1e[g % ER].lo, b, eL, 0, 0, 0);
+          eL = __builtin_amdgcn_mfma_f32_32x32x16_f16(W1e[g % ER].hi, b, eL, 0, 0, 0);
+        }
+        if (g >= 1 && g - 1 + ER < P1_EARLY) W1e[(g - 1) % ER] = w1_fetch(SB + g - 1 + ER);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+  uint32_t xrow_keep = 0;  // loader group: the row this lane gathered for the next tile
   auto tile_body = [&](auto exact_tag) __attribute__((always_inline)) {
     constexpr bool EXACT = decltype(exact_tag)::value;
     static_assert(!EXACT || VERSIONED, "the exact-input loop belongs to the wide critic");
+    constexpr bool XE = EXACT && EARLY;  // this tile's layer 1 (or the loader group's part of it) arrives in eC / eL
     STAMP(14);
     const bool valid = (it * 32 + r) < R;
     const long itn = it + gridDim.x;
@@ -513,12 +599,14 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       for (int q = 0; q < NP; ++q) asm volatile("" : "+v"(fr_next[q]));
     }
     const u8* const XSI = lds + L.xs + (EXACT ? tpar : 2 * buf) * xs_plane;
+    if constexpr (XE && LOADER) xrow_keep = xrow_next;
 
     // ---------------------------------------------------------------- P1: z1 = W1^T x^T (+ b1 through the ones column)
     f32x16 acc;
     uint32_t relu1 = 0;
     if constexpr (WIDE) asm volatile("" : "+v"(w1p_lane));  // (see w1_fetch: its addresses stay loop-variant)
-    if constexpr (CHAIN || WIDE) {
+    // (with an early pass the loader group's range is in eL already, and with P1_EARLY == S1 the chain group's in eC)
+    if constexpr ((CHAIN || WIDE) && !(XE && (LOADER || EARLY_ALL))) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
     // operand reads run ONE step ahead of their MFMAs (explicit double buffer + scheduling fence: without it the
@@ -552,10 +640,30 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       __builtin_amdgcn_sched_barrier(0);
     }
     }
-    if constexpr (WIDE) {
+    if constexpr (XE && EARLY_ALL && LOADER) {
+      // hand-over of the whole layer: what the chain group does below with its own sum and the exchanged one
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        acc[q] = fmaxf((eC[q] + eL[q]) * WU, 0.0f);
+        relu1 |= (acc[q] > 0.0f) ? (1u << q) : 0u;
+      }
+      // the next tile's gathers as early as the registers allow (the two sums are dead here): their round trip runs under the
+      // image stores, and the commit follows behind barrier A
+      __builtin_amdgcn_sched_barrier(0);
+      stage_issue(have_next ? xrow_next : 0u, xr);
+      __builtin_amdgcn_sched_barrier(0);
+      half4 ph[4], pl[4];
+      sw_write_image(H1I, r, w, h, acc, ph, pl);
+      RELU1[tid] = relu1;
+    }
+    if constexpr (WIDE && !(XE && EARLY_ALL)) {
       // the loader group's partial sums of its input range -> the chain group (the dz2 image region is idle here)
       float4* const xch = reinterpret_cast<float4*>(DZ2I) + (w * 4) * 64 + lane;
       if constexpr (LOADER) {
+        if constexpr (XE) {
+          acc = eL;
+          stage_issue(have_next ? xrow_next : 0u, xr);  // (as early as possible: committed behind barrier A)
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) xch[g * 64] = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
       }
@@ -568,7 +676,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
         }
       }
     }
-    if constexpr (CHAIN) {
+    if constexpr (CHAIN && !(XE && EARLY_ALL)) {
     STAMP(0);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -582,7 +690,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     }  // CHAIN
     STAMP(1);
     // next tile's gathers: issued after P1 (their latency hides under P2..P4)
-    if constexpr (WIDE && LOADER) {
+    if constexpr (WIDE && LOADER && !XE) {
       // unconditional (row 0 when there is no next tile): the staging registers are then dead from the commit to here,
       // and P1's ring and accumulator live in them
       stage_issue(have_next ? xrow_next : 0u, xr);
@@ -643,7 +751,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
         for (int q = 0; q < NP; ++q) load_row((long)fr_next[q], n_act[q], n_f0[q], n_f1[q], n_m[q]);
       }
     }
-    if constexpr (WIDE && CHAIN) {
+    if constexpr (WIDE && CHAIN && !(XE && EARLY_ALL)) {
       // the chain group's ring for the NEXT tile (steps 0 .. W1_RING - 1: a whole tile of latency to hide under).  Issued
       // here, behind the gather block: a spilled cursor value reloaded there comes with s_waitcnt vmcnt(0), which waited
       // for these fetches when they were issued at the end of the P1 loop (3.0 K cycles per tile)
@@ -655,6 +763,14 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     STAMP(2);
     __syncthreads();  // A: h1 image complete
     STAMP(3);
+    if constexpr (XE && LOADER) {
+      // the next tile's hi plane, behind barrier A here: this group has no layer-1 work in front of A any more, the gathers
+      // were issued at the top of the tile, and the early pass can start behind B.  Then its W1 ring, into the staging
+      // registers that are dead from here
+      stage_commit(true_type{}, true_type{}, lds + L.xs + (tpar ^ 1) * xs_plane, xr, tpar ^ 1);
+      early_fill();
+    }
+    if constexpr (XE && EARLY_ALL && CHAIN) relu1 = RELU1[tid];  // (P4 masks dh1 with them)
 
     // ---------------------------------------------------------------- P2: z2 = b2 + W2^T h1^T ; head partial logits
     f32x16 h2;
@@ -725,7 +841,8 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     STAMP(5);
     __syncthreads();  // B: partial logits (and the h2 image) complete
     STAMP(6);
-    if constexpr (EXACT && LOADER) {
+    if constexpr (XE && LOADER) early_steps(std::integral_constant<int, 0>{}, std::integral_constant<int, GB>{}, lds + L.xs + (tpar ^ 1) * xs_plane);
+    if constexpr (EXACT && LOADER && !XE) {
       // the next tile's hi plane into the other half of the x region, in this group's idle time (hazards: see tile_body).
       // Behind barrier B, not A: the gathers were issued just in front of A and need their round trip to memory; committed
       // there, the chain group waited 0.4 K cycles at B for this group (phase stamps); from here to barrier D this group
@@ -813,6 +930,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     STAMP(7);
     __syncthreads();  // B2: dy of all 32 rows visible; every reader of the partial logits is done
     STAMP(15);
+    if constexpr (XE && LOADER) early_steps(std::integral_constant<int, GB>{}, std::integral_constant<int, GC>{}, lds + L.xs + (tpar ^ 1) * xs_plane);
     if constexpr (CHAIN) {
     if (ACTOR) {
       // gW3^T[o][f = 32w + r] += sum_rows dy[row][o] h2[row][f]   (outputs >= NO of the dy image are zero)
@@ -927,6 +1045,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // from barrier D on)
       if (have_next) stage_commit(false_type{}, false_type{}, lds + L.xs + (buf ^ 1) * 2 * xs_plane, xr, 0);
     }
+    if constexpr (XE && LOADER) early_steps(std::integral_constant<int, GC>{}, std::integral_constant<int, P1_EARLY>{}, lds + L.xs + (tpar ^ 1) * xs_plane);
     STAMP(10);
     if constexpr (!WIDE) do_gw2();
     STAMP(11);
@@ -1007,6 +1126,11 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // plane 1 becomes a hi plane: its ones column (first read by the P1 of this block's second tile, barriers A0 .. E away)
       if (CHAIN && tid < 32) *reinterpret_cast<_Float16*>(lds + L.xs + xs_plane + tid * xs_row + 2 * din) = (_Float16)1.0f;
     }
+    if constexpr (EARLY && LOADER) {
+      // the first tile's layer-1 sums (its hi plane is in plane 0 since the prologue; unconditional: see tile_body)
+      early_fill();
+      early_steps(std::integral_constant<int, 0>{}, std::integral_constant<int, P1_EARLY>{}, lds + L.xs);
+    }
     for (; it < ntiles && exact; it += gridDim.x, tpar ^= 1) tile_body(true_type{});
     // The per-lane roots of every LDS address are made opaque between the two loops: the general loop's loop-invariant
     // addresses are then formed behind the exact loop instead of being carried (spilled) across it - each loop sees the
@@ -1019,9 +1143,21 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // the tile at `it` has low terms; its hi plane sits in plane `tpar`, and the loader group's registers still hold its rows:
       // committed again in the general layout (hi plane 0, lo plane 1, ones column of the lo plane 0).  Every reader of both
       // planes is behind barrier E of the last exact tile; the barrier here orders these stores before the general loop's P1.
-      if constexpr (LOADER) stage_commit(false_type{}, false_type{}, lds + L.xs, xr, 0);
+      // (with an early pass those registers were given to its ring and sums: the rows are gathered again, once per block)
+      if constexpr (LOADER) {
+        if constexpr (EARLY) {
+          // (opaque: recognised as the row of the last exact tile's gather, its nine addresses were kept from there to here)
+          asm volatile("" : "+v"(xrow_keep));
+          stage_issue(xrow_keep, xr);
+        }
+        stage_commit(false_type{}, false_type{}, lds + L.xs, xr, 0);
+      }
       if (CHAIN && tid < 32) *reinterpret_cast<_Float16*>(lds + L.xs + xs_plane + tid * xs_row + 2 * din) = (_Float16)0.0f;
       __syncthreads();
+    }
+    if constexpr (EARLY_ALL && CHAIN) {  // the chain group's W1 ring: the general loop expects its first steps in flight
+#pragma unroll
+      for (int s = 0; s < NW1; ++s) W1f[s] = w1_fetch(S_LO + s);
     }
   }
   for (; it < ntiles; it += gridDim.x, buf ^= (WIDE ? 0 : 1)) tile_body(false_type{});
