@@ -57,10 +57,13 @@ enum {
                                       too.  Contract left to the caller: whoever rewrites the CONTENTS of that same parameter buffer
                                       between the finish call and the next critic launch (a copy-in, another optimiser step) must
                                       write 0 here - the next launch then re-splits W1 itself */
-  MAVA_CTX_EXACT_TILES = 8         /* diagnostic counter on the device: 32-row tiles that the blocks of the handle's wide f16x2
+  MAVA_CTX_EXACT_TILES = 8,        /* diagnostic counter on the device: 32-row tiles that the blocks of the handle's wide f16x2
                                       gradient launches (96..287 inputs) ran in the exact-input tile loop - inputs exact in f16: hi plane
                                       only, two MFMAs per product, the next x tile staged beside this one (ppo_train_h2.hip) -, summed
                                       over launches.  Reading it waits for the device; 0 is the only value that can be written */
+  MAVA_CTX_X16_LAUNCHES = 9        /* diagnostic counter on the device: wide f16x2 critic launches of the handle that staged their input
+                                      from the caller's f16 copy (mava_ppo_critic_grad_x16_f32 with a valid copy).  Reading it waits for
+                                      the device; 0 is the only value that can be written */
 };
 int mava_ctx_create(mava_ctx** out);
 int mava_ctx_destroy(mava_ctx* ctx); /* frees the handle's workspaces; NULL is a no-op */
@@ -217,6 +220,23 @@ int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const 
                              const float* old_value, const float* targets, const int32_t* idx,
                              long idx_base, int Rb, int A, float clip_eps, float vf_coef,
                              float* slab, long slab_stride, int n_slab, mava_stream_t s);
+
+/* mava_ppo_critic_grad_f32 with an f16 copy of critic_input: input16 (rows of critic_input, din) IEEE binary16, contiguous,
+ * 16-byte aligned, and input16_valid, one 32-bit device word written by whoever wrote the copy (mava_rollout_ff_x16_f32):
+ * 1 = input16 holds, for every element, the f16 high term f16(critic_input) that the kernel would form itself, and the low term
+ * f16(critic_input - high) is zero everywhere (an input whose remainder underflows f16, such as 1 + 2^-30, counts as exact there
+ * too: the f32 path drops the same remainder).  The wide f16x2 critic kernel (96..287 inputs) then reads the word on the
+ * device, once per block, and with 1 stages its input from the copy - half the bytes, no conversion, every tile in the
+ * exact-input loop (MAVA_CTX_X16_LAUNCHES counts such launches); the gradient has the same bits either way.  The copy is
+ * NOT read, and the call is mava_ppo_critic_grad_f32, when the word is not 1, when either pointer is NULL, din % 8 != 0,
+ * critic_input is not 16-byte aligned, MAVA_CTX_TRAIN_VARIANT bit 1 is set, or another kernel takes the launch.  The host
+ * never reads the word.  New entry points rather than handle keys: the rollout takes no handle, and a learner with several
+ * replicas has one copy per replica. */
+int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
+                                 const float* old_value, const float* targets, const int32_t* idx,
+                                 long idx_base, int Rb, int A, float clip_eps, float vf_coef,
+                                 float* slab, long slab_stride, int n_slab, const uint16_t* input16,
+                                 const uint32_t* input16_valid, mava_stream_t s);
 
 /* Both gradient kernels read MAVA_CTX_MATMUL_MODE, the critic also MAVA_CTX_CRITIC_AGGREGATION, from their handle. */
 
@@ -540,6 +560,25 @@ int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions, const flo
                              uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
                              uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
                              float* last_reward, uint8_t* last_done, int32_t* step_counter, mava_stream_t s);
+/* mava_rollout_ff_tail_f32 that also writes an f16 copy of the shared global state, for mava_ppo_critic_grad_x16_f32:
+ * state16 (T+1, E, A*O) IEEE binary16, contiguous, 16-byte aligned - every slot, slot 0 included, is written by the launch
+ * with the halves the kernel's LDS image holds (global_state is their conversion to f32) - and state16_valid, one 32-bit
+ * device word that must hold 0 or 1 on entry (allocate it zeroed) and is left 1 when every value the launch loaded from slot 0
+ * of global_state had a zero low f16 term f16(x - f16(x)), else 0; with 1, state16[t] is the f16 high term of global_state[t] that
+ * the critic kernel would form itself, for every t < T (slots 1 .. T-1 are float(state16[t]) == global_state[t] bit for bit always; slot 0
+ * is the caller's, and a value there whose remainder underflows f16 counts as exact, as it does in the f32 staging path).  (Between
+ * entry and the end of the launch the word counts blocks; the last block stores the result.)  Needs critic_shared and
+ * A*O % 8 == 0.  Both NULL (and last_reward / last_done NULL or not, as in the two calls above): exactly those calls. */
+int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                            int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                            uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                            int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                            int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                            int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                            uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                            uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                            float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                            uint32_t* state16_valid, mava_stream_t s);
 /* The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of agents_view
  * (T+1, E, A, obs_dim) f32, global_state (T+1, E, gs_dim) f32 (NULL with gs_dim 0: none), action_mask (T+1, E, A,
  * n_actions) u8 and step_count (T+1, E, A) i32, in one launch.  Slots 1..T are not touched. */

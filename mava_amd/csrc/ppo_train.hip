@@ -1094,11 +1094,10 @@ extern "C" int mava_ppo_actor_grad_continuous_f32(const float* params, int din, 
   return dispatch_kt<16, true, true>(tk, n_slab, s);
 }
 
-extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input,
-                                        int x_share, const float* old_value, const float* targets,
-                                        const int32_t* idx, long idx_base, int Rb, int A,
-                                        float clip_eps, float vf_coef, float* slab, long slab_stride,
-                                        int n_slab, hipStream_t s) {
+static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
+                            const float* old_value, const float* targets, const int32_t* idx, long idx_base, int Rb, int A,
+                            float clip_eps, float vf_coef, float* slab, long slab_stride, int n_slab, const uint16_t* input16,
+                            const uint32_t* input16_valid, hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && x_share >= 1, 0, "mava_ppo_critic_grad_f32: din=%d x_share=%d", din, x_share);
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1 && n_slab >= 1 && n_slab <= 1024 && (long)Rb * A < (1L << 31), 1,
                  "mava_ppo_critic_grad_f32: Rb=%d A=%d n_slab=%d", Rb, A, n_slab);
@@ -1116,9 +1115,33 @@ extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int 
   tk.old_value = old_value; tk.targets = targets; tk.clip_eps = clip_eps; tk.vf_coef = vf_coef;
   tk.slab = slab; tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
+  // (the f16 copy of the input: only the wide f16x2 kernel reads it, see ppo_train_task.h)
+  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid;
   int rc = 1;
   if (mava_ctx_matmul_mode(ctx) == 1) rc = mava_train_h2_launch(ctx, tk, n_slab, false, s);
   if (ctx != nullptr) ctx->w1_fresh[1] = 0;  // one-shot whichever kernel takes the launch (the exact-f32 one does not read the copy)
   if (rc <= 0) return rc;
   return dispatch_kt<1, false>(tk, n_slab, s);
+}
+
+extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input,
+                                        int x_share, const float* old_value, const float* targets,
+                                        const int32_t* idx, long idx_base, int Rb, int A,
+                                        float clip_eps, float vf_coef, float* slab, long slab_stride,
+                                        int n_slab, hipStream_t s) {
+  return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
+                          slab, slab_stride, n_slab, nullptr, nullptr, s);
+}
+
+// ... with an f16 copy of critic_input and its validity word on the device (include/mava_hip.h)
+extern "C" int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input,
+                                            int x_share, const float* old_value, const float* targets,
+                                            const int32_t* idx, long idx_base, int Rb, int A,
+                                            float clip_eps, float vf_coef, float* slab, long slab_stride,
+                                            int n_slab, const uint16_t* input16, const uint32_t* input16_valid,
+                                            hipStream_t s) {
+  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr), 3,
+                 "mava_ppo_critic_grad_x16_f32: input16 and input16_valid go together");
+  return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
+                          slab, slab_stride, n_slab, input16, input16_valid, s);
 }

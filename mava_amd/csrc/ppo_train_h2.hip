@@ -118,10 +118,13 @@ __global__ __launch_bounds__(256) void pack_w1_kernel(const float* __restrict__ 
 // sets (two waves per SIMD, 256 registers each): ROLE 1, the CHAIN group (waves 0-3: layers, loss, backward chain, dW2,
 // small gradients; W1 through a register ring), and ROLE 2, the LOADER group (waves 4-7: gathers and splits the x tiles,
 // owns the 9 x 16 accumulator registers of dW1).  Every role executes the same barrier sequence.
-template <int NO, int S1, bool ACTOR, bool WIDE, int XV, int ROLE>
+// X16 (wide critic only): the x tiles come from the task's f16 copy of x (TrainTask::x16) - 16-byte loads and 16-byte LDS
+// stores of the halves as they are, no split, no flag: every tile of the launch runs in the exact-input loop.
+template <int NO, int S1, bool ACTOR, bool WIDE, int XV, int ROLE, bool X16 = false>
 __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, const uint4* __restrict__ w1p, u8* lds) {
   static_assert(!WIDE || S1 % W1_RING == 0, "WIDE: S1 must be a multiple of the W1 ring depth");
   static_assert((ROLE == 0) == !WIDE, "roles 1 / 2 belong to WIDE launches");
+  static_assert(!X16 || (WIDE && !ACTOR), "the f16 copy of x is read by the wide critic only");
   constexpr bool CHAIN = ROLE != 2, LOADER = ROLE != 1;
 #if defined(MAVA_NO_W2_RESIDENT) || defined(MAVA_W2_RESIDENT_P4)
   constexpr bool W2_RESIDENT = false;
@@ -376,6 +379,29 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     }
   };
   u8* const xs_dummy = reinterpret_cast<u8*>(misc + 8);  // 16 bytes nobody reads
+  // X16: thread l8 of a row takes the 8-half pieces l8, l8 + 8, ... of the f16 row (din % 8 == 0, 16-byte aligned rows); same
+  // rule for a piece past the row end
+  constexpr int NPC16 = (32 * KT1 / 8 + 7) / 8;
+  const int nv16 = din / 8;
+  // (pieces are native 4 x 32-bit vectors read through a global-address-space pointer, like w1_fetch's: an array of them is
+  // promoted to registers, and the loads are global_load, counted in vmcnt alone)
+  auto stage_issue16 = [&](uint32_t xrow_idx, u32x4 (&xq)[NPC16]) {
+    const w1_gptr xrow = (w1_gptr)(tk.x16 + (long)xrow_idx * din);
+#pragma unroll
+    for (int i = 0; i < NPC16; ++i) {
+      const int c = l8 + 8 * i;
+      xq[i] = xrow[(c < nv16) ? c : 0];
+    }
+  };
+  // `dst`: row 0 of the hi plane written (the only plane of the exact-input loop)
+  auto stage_commit16 = [&](u8* dst, const u32x4 (&xq)[NPC16]) {
+    u8* base = dst + srow * xs_row;
+#pragma unroll
+    for (int i = 0; i < NPC16; ++i) {
+      const int c = l8 + 8 * i;
+      *reinterpret_cast<u32x4*>((c < nv16) ? (base + 16 * c) : xs_dummy) = xq[i];
+    }
+  };
   // wide kernel: xflag[tile parity] != 0 when some staged value of that tile's x rows has a non-zero low f16 term.  Inputs
   // exact in f16 (flags, one-hot ids, small integers: the whole global state of RobotWarehouse and of the synthetic env) leave
   // it 0: such tiles run in the exact-input tile loop below (hi plane only, two products instead of three - same bits).
@@ -429,7 +455,15 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 
   const long ntiles = (R + 31) / 32;
   long it = blockIdx.x;
-  float xr[NR];
+  float xr[X16 ? 1 : NR];
+  u32x4 xq[X16 ? NPC16 : 1];
+  // the two staging forms behind one pair of names: gathers of a row, and the commit of a hi plane of the exact-input loop
+  auto issue = [&](uint32_t xrow_idx) __attribute__((always_inline)) {
+    if constexpr (X16) stage_issue16(xrow_idx, xq); else stage_issue(xrow_idx, xr);
+  };
+  auto commit_hi = [&](u8* dst, int flag_slot) __attribute__((always_inline)) {
+    if constexpr (X16) stage_commit16(dst, xq); else stage_commit(true_type{}, true_type{}, dst, xr, flag_slot);
+  };
   int r_act[NP] = {}, n_act[NP] = {};
   float r_f0[NP] = {}, r_f1[NP] = {}, n_f0[NP] = {}, n_f1[NP] = {};
   uint32_t r_m[NP] = {}, n_m[NP] = {};
@@ -441,7 +475,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   if (it < ntiles) {
     if (LOADER) {
       cursor_gather(cs, ps_next, as_next);
-      stage_issue(stage_row(ps_next, as_next), xr);
+      issue(stage_row(ps_next, as_next));
     }
     if (CHAIN) {
 #pragma unroll
@@ -451,7 +485,8 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       }
     }
     if (LOADER) {
-      stage_commit(false_type{}, versioned_tag{}, lds + L.xs, xr, 0);
+      if constexpr (X16) stage_commit16(lds + L.xs, xq);  // (plane 1 stays zero: it becomes the next tile's hi plane)
+      else stage_commit(false_type{}, versioned_tag{}, lds + L.xs, xr, 0);
       cursor_advance(cs);
     }
     if (CHAIN) {
@@ -586,7 +621,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     const bool valid = (it * 32 + r) < R;
     const long itn = it + gridDim.x;
     const bool have_next = itn < ntiles;
-    if constexpr (EXACT && LOADER) {
+    if constexpr (EXACT && LOADER && !X16) {
       if (tid == 0) xflag[tpar ^ 1] = 0u;
     }
     uint32_t xrow_next = LOADER ? stage_row(ps_next, as_next) : 0u;
@@ -650,7 +685,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // the next tile's gathers as early as the registers allow (the two sums are dead here): their round trip runs under the
       // image stores, and the commit follows behind barrier A
       __builtin_amdgcn_sched_barrier(0);
-      stage_issue(have_next ? xrow_next : 0u, xr);
+      issue(have_next ? xrow_next : 0u);
       __builtin_amdgcn_sched_barrier(0);
       half4 ph[4], pl[4];
       sw_write_image(H1I, r, w, h, acc, ph, pl);
@@ -662,7 +697,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       if constexpr (LOADER) {
         if constexpr (XE) {
           acc = eL;
-          stage_issue(have_next ? xrow_next : 0u, xr);  // (as early as possible: committed behind barrier A)
+          issue(have_next ? xrow_next : 0u);  // (as early as possible: committed behind barrier A)
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) xch[g * 64] = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
@@ -693,7 +728,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     if constexpr (WIDE && LOADER && !XE) {
       // unconditional (row 0 when there is no next tile): the staging registers are then dead from the commit to here,
       // and P1's ring and accumulator live in them
-      stage_issue(have_next ? xrow_next : 0u, xr);
+      issue(have_next ? xrow_next : 0u);
     }
     if constexpr (WIDE && CHAIN) {
       // everything the gather block reads is pinned into registers here, before its first load: reloads of spilled values
@@ -728,7 +763,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
         }
       }
     } else if (have_next) {
-      if (LOADER && !WIDE) stage_issue(xrow_next, xr);
+      if (LOADER && !WIDE) issue(xrow_next);
       const bool more = itn + gridDim.x < ntiles;
       if (more) {
         if (LOADER) {
@@ -767,7 +802,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // the next tile's hi plane, behind barrier A here: this group has no layer-1 work in front of A any more, the gathers
       // were issued at the top of the tile, and the early pass can start behind B.  Then its W1 ring, into the staging
       // registers that are dead from here
-      stage_commit(true_type{}, true_type{}, lds + L.xs + (tpar ^ 1) * xs_plane, xr, tpar ^ 1);
+      commit_hi(lds + L.xs + (tpar ^ 1) * xs_plane, tpar ^ 1);
       early_fill();
     }
     if constexpr (XE && EARLY_ALL && CHAIN) relu1 = RELU1[tid];  // (P4 masks dh1 with them)
@@ -847,7 +882,7 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       // Behind barrier B, not A: the gathers were issued just in front of A and need their round trip to memory; committed
       // there, the chain group waited 0.4 K cycles at B for this group (phase stamps); from here to barrier D this group
       // has 3.5 K idle cycles
-      stage_commit(true_type{}, true_type{}, lds + L.xs + (tpar ^ 1) * xs_plane, xr, tpar ^ 1);
+      commit_hi(lds + L.xs + (tpar ^ 1) * xs_plane, tpar ^ 1);
     }
 
     // ---------------------------------------------------------------- P3: loss, d loss / d logits (x R), dW3, dz2
@@ -1043,7 +1078,9 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     if constexpr (!WIDE) {
       // narrow inputs: the next tile's x rows have arrived long ago - split + store them into the other buffer (read
       // from barrier D on)
-      if (have_next) stage_commit(false_type{}, false_type{}, lds + L.xs + (buf ^ 1) * 2 * xs_plane, xr, 0);
+      if constexpr (!X16) {
+        if (have_next) stage_commit(false_type{}, false_type{}, lds + L.xs + (buf ^ 1) * 2 * xs_plane, xr, 0);
+      }
     }
     if constexpr (XE && LOADER) early_steps(std::integral_constant<int, GC>{}, std::integral_constant<int, P1_EARLY>{}, lds + L.xs + (tpar ^ 1) * xs_plane);
     STAMP(10);
@@ -1099,11 +1136,11 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     if constexpr (WIDE) {
       __syncthreads();  // E: every reader of this x tile, of the dz2 image and of the h1 image is done
       if constexpr (EXACT) {
-        // the next tile was committed behind barrier B: may it run in this loop?
-        exact = __builtin_amdgcn_readfirstlane((int)xflag[tpar ^ 1]) == 0;
+        // the next tile was committed behind barrier B: may it run in this loop?  (X16: every tile does)
+        if constexpr (!X16) exact = __builtin_amdgcn_readfirstlane((int)xflag[tpar ^ 1]) == 0;
         ++n_exact;
       } else {
-        if constexpr (LOADER) {
+        if constexpr (LOADER && !X16) {
           // (without a next tile: row 0 into a buffer nobody reads again)
           stage_commit(false_type{}, false_type{}, lds + L.xs, xr, 0);
         }
@@ -1121,7 +1158,8 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
     // The exact-input loop runs first; the general loop takes whatever is left and never hands back (real inputs are exact
     // throughout or not at all).  The accumulators are loop-carried variables of two consecutive loops: no loop contains a
     // branch that merges around them (a per-tile `if` around a two-product dW1 spilled 388 registers in the loader role).
-    exact = __builtin_amdgcn_readfirstlane((int)xflag[0]) == 0 && tk.force_xlo == 0;  // (tile 0: committed by the prologue)
+    // (tile 0: committed by the prologue; X16: the copy holds nothing but exact values)
+    exact = X16 || (__builtin_amdgcn_readfirstlane((int)xflag[0]) == 0 && tk.force_xlo == 0);
     if (exact && it < ntiles) {
       // plane 1 becomes a hi plane: its ones column (first read by the P1 of this block's second tile, barriers A0 .. E away)
       if (CHAIN && tid < 32) *reinterpret_cast<_Float16*>(lds + L.xs + xs_plane + tid * xs_row + 2 * din) = (_Float16)1.0f;
@@ -1131,6 +1169,9 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
       early_fill();
       early_steps(std::integral_constant<int, 0>{}, std::integral_constant<int, P1_EARLY>{}, lds + L.xs);
     }
+    if constexpr (X16) {
+      for (; it < ntiles; it += gridDim.x, tpar ^= 1) tile_body(true_type{});
+    } else {
     for (; it < ntiles && exact; it += gridDim.x, tpar ^= 1) tile_body(true_type{});
     // The per-lane roots of every LDS address are made opaque between the two loops: the general loop's loop-invariant
     // addresses are then formed behind the exact loop instead of being carried (spilled) across it - each loop sees the
@@ -1159,8 +1200,11 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
 #pragma unroll
       for (int s = 0; s < NW1; ++s) W1f[s] = w1_fetch(S_LO + s);
     }
+    }  // !X16
   }
-  for (; it < ntiles; it += gridDim.x, buf ^= (WIDE ? 0 : 1)) tile_body(false_type{});
+  if constexpr (!X16) {
+    for (; it < ntiles; it += gridDim.x, buf ^= (WIDE ? 0 : 1)) tile_body(false_type{});
+  }
 #ifdef MAVA_STAMPS
   if (tk.stamps != nullptr && blockIdx.x == 0 && lane == 0) {
     for (int i = 0; i < 16; ++i) tk.stamps[((ROLE == 2 ? 4 : 0) + w) * 16 + i] = st_acc[i];
@@ -1171,6 +1215,9 @@ __device__ __forceinline__ void h2_body(const TrainTask& tk, const H2Layout& L, 
   __syncthreads();
   if constexpr (VERSIONED && CHAIN) {  // proof that the exact-input loop ran: tiles of this block it took
     if (tid == 0 && tk.exact_tiles != nullptr) atomicAdd(tk.exact_tiles, (unsigned long long)n_exact);
+    if constexpr (X16) {  // ... and that this launch read the f16 copy
+      if (tid == 0 && blockIdx.x == 0 && tk.x16_launches != nullptr) atomicAdd(tk.x16_launches, 1ull);
+    }
   }
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
   const int oB2 = mlp_off_b2(din), oB3 = mlp_off_b3(din, no);
@@ -1249,7 +1296,23 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 2 : 1) void ppo_train_h2_k
                                                                                      const uint4* __restrict__ w1p) {
   extern __shared__ __attribute__((aligned(16))) u8 lds[];
   if constexpr (WIDE) {
-    if (threadIdx.x < 256) {
+    // The wide critic on 16-byte aligned rows carries both staging forms: the launch passes x16_valid only when everything the
+    // host can see allows the f16 copy (launch_h2), and the word itself - written by the kernel that wrote the copy - is read
+    // here, once per block, with a wave-uniform load.  The two forms are separate bodies: neither holds the other's registers.
+    constexpr bool X16_CAPABLE = !ACTOR && XV == 4;
+    bool x16 = false;
+    if constexpr (X16_CAPABLE) {
+      if (tk.x16_valid != nullptr) x16 = __builtin_amdgcn_readfirstlane((int)*tk.x16_valid) == 1;
+    }
+    if (X16_CAPABLE && x16) {
+      if constexpr (X16_CAPABLE) {
+        if (threadIdx.x < 256) {
+          h2_body<NO, S1, ACTOR, WIDE, XV, 1, true>(tk, L, w1p, lds);
+        } else {
+          h2_body<NO, S1, ACTOR, WIDE, XV, 2, true>(tk, L, w1p, lds);
+        }
+      }
+    } else if (threadIdx.x < 256) {
       h2_body<NO, S1, ACTOR, WIDE, XV, 1>(tk, L, w1p, lds);
     } else {
       h2_body<NO, S1, ACTOR, WIDE, XV, 2>(tk, L, w1p, lds);
@@ -1287,16 +1350,22 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
     }
     fresh = 0;
     w1p = buf;
-    // the handle's exact-tile counter (ctx.h): one device word, allocated with the first wide launch
+    // the handle's device counters (ctx.h): exact tiles, launches on the f16 copy of x; allocated with the first wide launch
     if (ctx->exact_tiles == nullptr) {
       void* word = nullptr;
-      MAVA_HIP_CHECK(hipMalloc(&word, sizeof(unsigned long long)));
+      MAVA_HIP_CHECK(hipMalloc(&word, 2 * sizeof(unsigned long long)));
       ctx->exact_tiles = static_cast<unsigned long long*>(word);
-      MAVA_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(unsigned long long), s));
+      MAVA_HIP_CHECK(hipMemsetAsync(word, 0, 2 * sizeof(unsigned long long), s));
     }
   }
   TrainTask tkl = tk;
   tkl.exact_tiles = WIDE ? ctx->exact_tiles : nullptr;
+  // the f16 copy of x: handed to the kernel only where it has the second staging form and the copy fits it (16-byte pieces of
+  // 16-byte aligned rows, no forced x_lo products); whether the copy is VALID is the kernel's own look at the device word
+  const bool x16_ok = WIDE && !ACTOR && XV == 4 && tk.x16 != nullptr && tk.x16_valid != nullptr && tk.din % 8 == 0 &&
+                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0;
+  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; }
+  tkl.x16_launches = x16_ok ? ctx->exact_tiles + 1 : nullptr;  // (the second word of the handle's counter allocation)
   g_train_last_instance = train_instance_id(2, ACTOR, false, WIDE, NO, S1, XV);
   hipLaunchKernelGGL((ppo_train_h2_kernel<NO, S1, ACTOR, WIDE, XV>), dim3(n_slab), dim3(WIDE ? 512 : 256), L.end, s, tkl, L,
                      w1p);

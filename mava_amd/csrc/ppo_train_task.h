@@ -31,6 +31,12 @@ struct TrainTask {
   unsigned long long* stamps;  // diagnostic builds only (-DMAVA_STAMPS): per-phase cycle sums of block 0
   int force_xlo;           // f16x2 kernels: always run the x_lo products (MAVA_CTX_TRAIN_VARIANT bit 1; tests: same bits either way)
   unsigned long long* exact_tiles;  // wide f16x2 kernels: device word every block adds its exact-loop tiles to (MAVA_CTX_EXACT_TILES), or null
+  // Wide f16x2 critic: an f16 copy of x (rows_x, din), 16-byte aligned rows (din % 8 == 0), and the device word that says
+  // whether it may be read: 1 = x16 is the f16 high term of x and the low term is zero everywhere.  Both null: no copy.  The launch stages x from the copy - 16-byte
+  // loads, no conversion, every tile in the exact-input loop - when the word reads 1 (ppo_train_h2.hip), and from x otherwise.
+  const _Float16* x16;
+  const uint32_t* x16_valid;
+  unsigned long long* x16_launches;  // device word block 0 of a launch that read the copy adds 1 to (MAVA_CTX_X16_LAUNCHES), or null
 };
 
 // ppo_train_h2.hip: the same fused kernel on v_mfma_f32_32x32x16_f16 with every operand split into two f16 terms

@@ -74,6 +74,9 @@ struct RolloutArgs {
   float gamma, lam;
   // mava_rollout_ff_tail_f32 (null otherwise): reward / done of the last step, (E, A), and the device step counter
   float* last_reward; uint8_t* last_done; int32_t* step_counter;
+  // mava_rollout_ff_x16_f32 (null otherwise): the f16 copy of global_state, (T+1, E, A*O) with A*O % 8 == 0, and its validity
+  // word (see the prologue).  Last members: the offsets of everything above stay what they were.
+  _Float16* state16; uint32_t* state16_valid;
 };
 
 // The kernel's arguments read again from the argument segment AT THE POINT OF USE.  The ~40 pointers and seeds of
@@ -218,7 +221,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   // x images of slot 0 (written by the previous rollout or the reset), ones (bias) columns, masks of slot 0
   {
     const long slot0_av = 0;
-    uint32_t lo_any = 0;
+    uint32_t lo_any = 0, lo_gs = 0;
     for (int i = t512; i < 64 * W; i += 512) {
       const int row = i / W, c = i - row * W;
       const int e = e0 + row / A;
@@ -244,8 +247,10 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
         u8* p = lds + L.xc + le * xc_row + 2 * c;
         *reinterpret_cast<_Float16*>(p) = x0;
         *reinterpret_cast<_Float16*>(p + xc_plane) = x1;
-        lo_any |= (uint32_t)__builtin_bit_cast(uint16_t, x1) & 0x7FFFu;
+        lo_gs |= (uint32_t)__builtin_bit_cast(uint16_t, x1) & 0x7FFFu;
       }
+      lo_any |= lo_gs;
+      if (lo_gs != 0) XLF[1] = 1u;  // (the global state alone: what the f16 copy's validity word reports)
       if (t512 < XC_ROWS) *reinterpret_cast<_Float16*>(lds + L.xc + t512 * xc_row + 2 * din_c) = (_Float16)1.0f;
     }
     for (int i = t512; i < 64 * no; i += 512) {
@@ -273,6 +278,17 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   // observations loaded above are exact too, the low plane is zero for the whole rollout, and layer 1 runs two MFMAs per
   // product instead of three without reading that plane (the skipped product is exactly 0: same bits).
   const bool x_lo = __builtin_amdgcn_readfirstlane((int)*XLF) != 0;
+  // The f16 copy's validity word, one per launch: 1 when no block loaded a global-state value with a low term - then the f32
+  // record of slot 0 is the conversion of the halves in the image, like every later slot's.  The word holds 0 or 1 on entry.
+  // One thread per block counts itself in bits 1 .. 30, a block with a low term sets bit 31 first; the block that finds every
+  // other one counted stores the result.  (Nobody reads the word before the launch ends.)
+  if (SHARED && ACT_ROLE && tid == 0 && a.state16_valid != nullptr) {
+    uint32_t seen = 0;
+    if (XLF[1] != 0) seen = atomicOr(a.state16_valid, 0x80000000u);
+    asm volatile("" : "+v"(seen) : : "memory");  // (the count below is issued behind the returned value)
+    const uint32_t old = atomicAdd(a.state16_valid, 2u);
+    if (((old >> 1) & 0x3FFFFFFFu) == gridDim.x - 1u) *a.state16_valid = (old & 0x80000000u) ? 0u : 1u;
+  }
   const int rowB = r * IMG_ROW + 16 * h;  // + 32 s: features 16s + 8h .. + 7 of image row r
   const long EA = (long)E * A;
   const uint32_t nch = (O - 2 + 15) / 16 > 0 ? (O - 2 + 15) / 16 : 1;  // bit chunks per raw view
@@ -475,6 +491,44 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   const int tid_w = tid, wo_q = (W >> 1) > 0 ? (W >> 1) : 1, gs_q = (AO >> 2) > 0 ? (AO >> 2) : 1;
   const int wo_dr = 256 / wo_q, gs_dr = 256 / gs_q;
   const uint32_t wo_m = 65536u / (uint32_t)wo_q + 1u, gs_m = 65536u / (uint32_t)gs_q + 1u;
+  // The global state of slot `slot` from the shared critic's image (actor group): its f32 record (f32_too; slot 0 came from
+  // memory and is left alone) and, with mava_rollout_ff_x16_f32, the halves themselves into state16.  The copy rides on the
+  // quad loop's cursors: the lane of an even quad k also moves the 16 bytes of quads k and k + 1 (A O % 8 == 0, the launcher's
+  // check: a row is a whole number of such pairs and pair j / 2 of the block is piece j / 2 of the record) - one 16-byte LDS
+  // read and one 16-byte store, consecutive even lanes on consecutive pieces; no cursor or factor of its own.
+  auto write_gs = [&](long slot, bool f32_too) {
+    const auto& a = args_here();  // (shadows the parameter: see args_here)
+    int tid = tid_w;
+    asm volatile("" : "+v"(tid));
+    if (SHARED && a.global_state != nullptr) {
+      float* dst = a.global_state + (slot * E + e0) * (long)AO;
+      if ((AO & 3) == 0) {  // quads: 8-byte LDS reads, 16-byte stores
+        const bool h16 = a.state16 != nullptr;
+        uint4* const dst16 = h16 ? reinterpret_cast<uint4*>(a.state16 + (slot * E + e0) * (long)AO) : nullptr;
+        const int Q = AO >> 2, d_r = gs_dr, d_f = 256 - d_r * Q;
+        int le = (int)div_small((uint32_t)tid, gs_m), k = tid - le * Q;
+        for (int j = tid; j < EB * Q; j += 256) {
+          if (le < envs_ok) {
+            if (f32_too) {
+              const half4 v = *reinterpret_cast<const half4*>(lds + L.xc + le * xc_row + 8 * k);
+              reinterpret_cast<float4*>(dst)[j] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+            }
+            if (h16 && (k & 1) == 0) dst16[j >> 1] = *reinterpret_cast<const uint4*>(lds + L.xc + le * xc_row + 8 * k);
+          }
+          le += d_r; k += d_f;
+          if (k >= Q) { k -= Q; ++le; }
+        }
+      } else if (f32_too) {
+        const int d_r = 256 / AO, d_f = 256 - d_r * AO;
+        int le = tid / AO, k = tid - le * AO;
+        for (int j = tid; j < EB * AO; j += 256) {
+          if (le < envs_ok) dst[j] = (float)*reinterpret_cast<const _Float16*>(lds + L.xc + le * xc_row + 2 * k);
+          le += d_r; k += d_f;
+          if (k >= AO) { k -= AO; ++le; }
+        }
+      }
+    }
+  };
   auto write_out = [&](long slot, bool part_gs) {  // part_gs: the global state (actor group, after sampling); else the rest
     const auto& a = args_here();  // (shadows the parameter: see args_here)
     // The cursors' start values depend on the thread alone.  Computed from a thread id the compiler cannot see through,
@@ -508,29 +562,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
         }
       }
     }
-    if (part_gs && SHARED && a.global_state != nullptr) {
-      float* dst = a.global_state + (slot * E + e0) * (long)AO;
-      if ((AO & 3) == 0) {  // quads: 8-byte LDS reads, 16-byte stores
-        const int Q = AO >> 2, d_r = gs_dr, d_f = 256 - d_r * Q;
-        int le = (int)div_small((uint32_t)tid, gs_m), k = tid - le * Q;
-        for (int j = tid; j < EB * Q; j += 256) {
-          if (le < envs_ok) {
-            const half4 v = *reinterpret_cast<const half4*>(lds + L.xc + le * xc_row + 8 * k);
-            reinterpret_cast<float4*>(dst)[j] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-          }
-          le += d_r; k += d_f;
-          if (k >= Q) { k -= Q; ++le; }
-        }
-      } else {
-        const int d_r = 256 / AO, d_f = 256 - d_r * AO;
-        int le = tid / AO, k = tid - le * AO;
-        for (int j = tid; j < EB * AO; j += 256) {
-          if (le < envs_ok) dst[j] = (float)*reinterpret_cast<const _Float16*>(lds + L.xc + le * xc_row + 2 * k);
-          le += d_r; k += d_f;
-          if (k >= AO) { k -= AO; ++le; }
-        }
-      }
-    }
+    if (part_gs) write_gs(slot, true);
     if (!part_gs) {
       uint8_t* dst = a.action_mask + (slot * EA + (long)e0 * A) * no;
       for (int j = tid; j < rows_ok * no; j += 256) {
@@ -542,6 +574,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
 
   const int T_steps = a.T;
   const uint32_t t0 = a.t0;
+  if (SHARED && ACT_ROLE && a.state16 != nullptr) write_gs(0L, false);  // slot 0 of the f16 copy: the image the prologue filled from memory
   for (int t = 0; t < T_steps; ++t) {
     const uint32_t step = t0 + (uint32_t)t;
     forward(true, true, step);
@@ -853,7 +886,8 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
                            int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
                            uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
                            uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                           float* last_reward, uint8_t* last_done, int32_t* step_counter, hipStream_t s) {
+                           float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                           uint32_t* state16_valid, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 1 && A >= 1 && O >= 2 && T >= 1 && n_actions >= 1 && time_limit >= 1, 0,
                  "mava_rollout_ff_f32: bad shape E=%d A=%d O=%d T=%d nA=%d", E, A, O, T, n_actions);
   MAVA_ARG_CHECK(actor_params && critic_params && step_count && run_return && run_length && ep_return && ep_length &&
@@ -877,6 +911,10 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
   MAVA_ARG_CHECK((adv == nullptr) == (tgt == nullptr), 1, "mava_rollout_ff_f32: adv and tgt go together");
   a.adv = adv; a.tgt = tgt; a.gamma = gamma; a.lam = gae_lambda;
   a.last_reward = last_reward; a.last_done = last_done; a.step_counter = step_counter;
+  MAVA_ARG_CHECK((state16 == nullptr) == (state16_valid == nullptr), 1, "mava_rollout_ff_x16_f32: state16 and state16_valid go together");
+  MAVA_ARG_CHECK(state16 == nullptr || (critic_shared && (A * O) % 8 == 0 && (uintptr_t)state16 % 16 == 0), 2,
+                 "mava_rollout_ff_x16_f32: state16 needs the shared critic, A*O %% 8 == 0 (A*O=%d) and 16-byte alignment", A * O);
+  a.state16 = reinterpret_cast<_Float16*>(state16); a.state16_valid = state16_valid;
   if (critic_shared) {
     if (s1a == 5 && s1c == 17 && A >= 4) return launch_rollout<8, 5, 17, true>(a, s);  // RWARE tiny / small-4ag (O 66, A 4)
 #ifndef MAVA_FAST_BUILD
@@ -906,7 +944,7 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
                          t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
                          agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
                          last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, nullptr, nullptr,
-                         nullptr, s);
+                         nullptr, nullptr, nullptr, s);
 }
 
 // mava_rollout_ff_f32 that also leaves what the caller copied or added after it: last_reward / last_done (E, A) = reward /
@@ -927,7 +965,29 @@ extern "C" int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions
                          t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
                          agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
                          last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, s);
+                         last_done, step_counter, nullptr, nullptr, s);
+}
+
+// ... that also writes the f16 copy of the shared global state and its validity word (include/mava_hip.h).  last_reward /
+// last_done may be null here (then step_counter is too).
+extern "C" int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions, const float* critic_params,
+                                       int critic_shared, int E, int A, int O, int T, int time_limit,
+                                       uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
+                                       uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
+                                       int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                                       float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
+                                       int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
+                                       float* last_val, float* info_return, int32_t* info_length, uint8_t* info_terminal,
+                                       float* adv, float* tgt, float gamma, float gae_lambda, float* last_reward,
+                                       uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                       uint32_t* state16_valid, hipStream_t s) {
+  MAVA_ARG_CHECK((last_reward == nullptr) == (last_done == nullptr) && (last_reward != nullptr || step_counter == nullptr), 1,
+                 "mava_rollout_ff_x16_f32: last_reward, last_done (and step_counter) go together");
+  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
+                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
+                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
+                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
+                         last_done, step_counter, state16, state16_valid, s);
 }
 
 // The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of the four observation

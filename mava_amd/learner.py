@@ -205,6 +205,15 @@ class FFLearner:
                               and bool(getattr(env0, "supports_fused_rollout", False))
                               and int(getattr(env0, "synth_state_dim", 0)) == 0
                               and (not centralised_critic or (env0.gs_tiles == 1 and env0.global_state_shared)))
+        # The fused rollout's LDS image of the shared global state is f16 and its f32 record is that image converted; the wide critic
+        # gradient kernel converts it back on every launch.  With a shared critic on a multiple of 8 inputs the rollout also keeps
+        # the halves themselves (rollout_h2.hip state16: (T + 1) * E * Oc * 2 bytes per replica) and a validity word on the device,
+        # and every critic gradient launch of the update is handed both (ppo_train_h2.hip: 16-byte loads, no conversion; same
+        # bits).  The word is never read on the host.  MAVA_X16=0 turns the copy off (A/B runs, tests).
+        self.x16 = (self.fused_rollout and centralised_critic and self.Oc % 8 == 0 and os.environ.get("MAVA_X16", "1") != "0")
+        for rep in self.reps:
+            rep.state16 = torch.zeros((self.T + 1, self.E, 1, self.Oc), dtype=torch.float16, device=d) if self.x16 else None
+            rep.state16_valid = torch.zeros((1,), dtype=torch.int32, device=d) if self.x16 else None
         self._learn_calls = 0  # guards.check_f16_range: the previous call's metrics are checked from the second call on
         # One rank: nothing sits between the gradient kernels and Adam, so both slab sums, clip + Adam, the count increment and
         # the wide critic's W1 re-split run as TWO launches (ops.ppo_finish) instead of six.  With several replicas every
@@ -375,10 +384,13 @@ class FFLearner:
                 last_val=rep.last_val, info_return=rep.info_return[n], info_length=rep.info_length[n],
                 info_terminal=rep.info_terminal[n], adv=rep.adv, tgt=rep.tgt, gamma=float(s.gamma),
                 gae_lambda=float(s.gae_lambda), last_reward=rep.last_reward, last_done=rep.last_done,
-                step_counter=self.step_dev if u == 0 else None)  # (the launch leaves all three: nothing follows it)
+                step_counter=self.step_dev if u == 0 else None,  # (the launch leaves all three: nothing follows it)
+                state16=rep.state16, state16_valid=rep.state16_valid)
               if not ok:
                 assert u == 0
-                self.fused_rollout = False
+                self.fused_rollout = self.x16 = False
+                for r in self.reps:  # (nobody writes the copy: the critic launches must not be handed it)
+                    r.state16 = r.state16_valid = None
                 return False
         if side:
             for st in self._roll_streams:
@@ -479,7 +491,9 @@ class FFLearner:
             cx = rep.global_state[:T].view(-1, self.Oc) if self.centralised else av
             self._timed("critic_grad", ops.ppo_critic_grad, pc, cx, self.critic_share, rep.value.view(TEA), rep.tgt.view(TEA),
                         idx, base, self.Rb, A, float(s.clip_eps), float(s.vf_coef),
-                        self.slab_c[u * ns : (u + 1) * ns] if per_rep else self.slab_c, ctx=self.ctx)
+                        self.slab_c[u * ns : (u + 1) * ns] if per_rep else self.slab_c, ctx=self.ctx,
+                        input16=rep.state16[:T].view(-1, self.Oc) if self.x16 else None,
+                        input16_valid=rep.state16_valid if self.x16 else None)
             if not self.fused_tail:
                 ops.slab_reduce2(self.slab_c, self.Pc, self.g[self.Pa : self.P], 1, self.g[self.P + 2 : self.P + 3], accumulate=u > 0)
         if self.fused_tail:

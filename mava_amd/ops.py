@@ -447,11 +447,20 @@ def ppo_actor_grad(params, agents_view, action_mask, action, old_log_prob, advan
 
 
 def ppo_critic_grad(params, critic_input, x_share: int, old_value, targets, idx, idx_base: int, Rb: int, A: int,
-                    clip_eps: float, vf_coef: float, slab: torch.Tensor, ctx: Optional[Ctx] = None) -> None:
+                    clip_eps: float, vf_coef: float, slab: torch.Tensor, ctx: Optional[Ctx] = None,
+                    input16: Optional[torch.Tensor] = None, input16_valid: Optional[torch.Tensor] = None) -> None:
     """Fills slab (n_slab, stride) with partial [critic gradient | value_loss, 0] sums.  `ctx` selects the arithmetic and
-    the aggregation of shared input rows (None: exact f32, aggregation on)."""
+    the aggregation of shared input rows (None: exact f32, aggregation on).
+    input16 / input16_valid: an f16 copy of critic_input and the (1,) int32 device word that says whether it equals
+    critic_input (written by rollout_ff): the wide f16x2 critic kernel stages its input from the copy when the word reads 1
+    (mava_ppo_critic_grad_x16_f32); same bits either way, and no host read of the word."""
     _req(critic_input, torch.float32, "critic_input")
     din = critic_input.shape[1]
+    if (input16 is None) != (input16_valid is None):
+        raise ValueError("input16 and input16_valid go together")
+    if input16 is not None:
+        _req(input16, torch.float16, "input16", tuple(critic_input.shape))
+        _req(input16_valid, torch.int32, "input16_valid", (1,))
     _req(params, torch.float32, "params")
     P = mlp_param_count(din, 1)
     if params.numel() != P:
@@ -469,12 +478,12 @@ def ppo_critic_grad(params, critic_input, x_share: int, old_value, targets, idx,
     _req(slab, torch.float32, "slab")
     if slab.dim() != 2 or slab.shape[1] < P + 2:
         raise ValueError("slab must be (n_slab, >= P+2)")
-    check(
-        lib().mava_ppo_critic_grad_f32(ctx_ptr(ctx), ptr(params), din, ptr(critic_input), x_share, ptr(old_value), ptr(targets),
-                                       ptr(idx), idx_base, Rb, A, clip_eps, vf_coef, ptr(slab), slab.shape[1],
-                                       slab.shape[0], stream_ptr()),
-        "mava_ppo_critic_grad_f32",
-    )
+    args = (ctx_ptr(ctx), ptr(params), din, ptr(critic_input), x_share, ptr(old_value), ptr(targets), ptr(idx), idx_base, Rb, A,
+            clip_eps, vf_coef, ptr(slab), slab.shape[1], slab.shape[0])
+    if input16 is not None:
+        check(lib().mava_ppo_critic_grad_x16_f32(*args, ptr(input16), ptr(input16_valid), stream_ptr()), "mava_ppo_critic_grad_x16_f32")
+        return
+    check(lib().mava_ppo_critic_grad_f32(*args, stream_ptr()), "mava_ppo_critic_grad_f32")
 
 
 def slab_reduce2(slab: torch.Tensor, n_main: int, out_main: torch.Tensor, n_tail: int, out_tail: torch.Tensor,
@@ -496,11 +505,14 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
                time_limit: int, policy_seed: int, env_seed: int, t0: int, row_offset: int, env_offset: int,
                reward_mode: int, env_state, agents_view, global_state, action_mask, obs_step_count, action, value,
                reward, log_prob, done, last_val, info_return, info_length, info_terminal, adv=None, tgt=None,
-               gamma: float = 0.99, gae_lambda: float = 0.95, last_reward=None, last_done=None, step_counter=None) -> bool:
+               gamma: float = 0.99, gae_lambda: float = 0.95, last_reward=None, last_done=None, step_counter=None,
+               state16=None, state16_valid=None) -> bool:
     """The whole rollout of one replica in one launch (mava_rollout_ff_f32).  Returns False when the library does not
     instantiate the shape - the caller then steps policy_step / env.step_into per time step.
     last_reward / last_done (E, A): also written by the launch (= reward[T-1], done[T-1]); step_counter (1,) int32:
-    advanced by T at the launch's end (mava_rollout_ff_tail_f32)."""
+    advanced by T at the launch's end (mava_rollout_ff_tail_f32).
+    state16 (T + 1, E, 1, A * O) float16 / state16_valid (1,) int32 holding 0 or 1: the launch also writes the f16 copy of
+    global_state and whether it equals it (mava_rollout_ff_x16_f32); shared critic with A * O % 8 == 0 only."""
     W = A + O
     _req(actor_params, torch.float32, "actor_params")
     _req(critic_params, torch.float32, "critic_params")
@@ -536,7 +548,22 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
         ptr(global_state) if critic_shared else None, ptr(action_mask), ptr(obs_step_count), ptr(action), ptr(value),
         ptr(reward), ptr(log_prob), ptr(done), ptr(last_val), ptr(info_return), ptr(info_length), ptr(info_terminal),
         ptr(adv), ptr(tgt), gamma, gae_lambda)
-    if last_reward is None and last_done is None and step_counter is None:
+    if (state16 is None) != (state16_valid is None):
+        raise ValueError("state16 and state16_valid go together")
+    if state16 is not None:
+        if not critic_shared or (A * O) % 8:
+            raise ValueError("state16 needs the shared critic and A * O % 8 == 0")
+        _req(state16, torch.float16, "state16", (T + 1, E, 1, A * O))
+        _req(state16_valid, torch.int32, "state16_valid", (1,))
+        name = "mava_rollout_ff_x16_f32"
+        if last_reward is not None:
+            _req(last_reward, torch.float32, "last_reward", (E, A))
+            _req(last_done, torch.uint8, "last_done", (E, A))
+        if step_counter is not None:
+            _req(step_counter, torch.int32, "step_counter", (1,))
+        rc = lib().mava_rollout_ff_x16_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16),
+                                           ptr(state16_valid), stream_ptr())
+    elif last_reward is None and last_done is None and step_counter is None:
         name = "mava_rollout_ff_f32"
         rc = lib().mava_rollout_ff_f32(*args, stream_ptr())
     else:

@@ -1,8 +1,10 @@
 """Diagnostic: per-phase cycle shares of the fused PPO train kernels (needs a library built with
 MAVA_HIPCC_EXTRA="-DMAVA_STAMPS").  Prints, per wave of block 0, the cycles spent in each phase.
-    python tools/train_stamps.py [f16x2] [w4] [exact]
+    python tools/train_stamps.py [f16x2] [w4] [exact] [x16]
 `exact`: observations exact in f16 (bits), as RobotWarehouse's are - the wide critic then runs its exact-input tile loop and
-the eight-wave actor its two-product layer 1; without it the inputs are Gaussian (general loop, three products)."""
+the eight-wave actor its two-product layer 1; without it the inputs are Gaussian (general loop, three products).
+`x16` (with `exact`): the critic launch is handed an f16 copy of its input and a validity word of 1, as the learner does after a
+fused rollout - the wide critic then stages its x tiles from the copy."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,6 +14,7 @@ from mava_amd._lib import Ctx, lib
 dev = torch.device("cuda", 0)
 MODE = 1 if (len(sys.argv) > 1 and sys.argv[1] == "f16x2") else 0
 EXACT = "exact" in sys.argv[2:]
+X16 = "x16" in sys.argv[2:]
 TE, A, O, nA = 128 * 4096, 4, 66, 5
 Rb = TE // 2
 rng = np.random.default_rng(0)
@@ -40,7 +43,10 @@ for which in ("critic", "actor"):
         x = (torch.rand(TE, din, device=dev) < 0.2).float() if EXACT else torch.randn(TE, din, device=dev)
         ov, tg = torch.randn(TE * A, device=dev), torch.randn(TE * A, device=dev)
         slab = torch.zeros(256, params.numel() + 2, device=dev)
-        run = lambda: ops.ppo_critic_grad(params, x, A, ov, tg, perm, 0, Rb, A, 0.2, 0.5, slab, ctx=ctx)
+        x16 = x.half() if (X16 and EXACT) else None
+        x16_valid = torch.ones(1, dtype=torch.int32, device=dev) if x16 is not None else None
+        run = lambda: ops.ppo_critic_grad(params, x, A, ov, tg, perm, 0, Rb, A, 0.2, 0.5, slab, ctx=ctx, input16=x16,
+                                          input16_valid=x16_valid)
     else:
         din = A + O
         params = torch.randn(ops.mlp_param_count(din, nA), device=dev) * 0.05
@@ -59,7 +65,8 @@ for which in ("critic", "actor"):
     a.record(); run(); b.record(); torch.cuda.synchronize()
     s8 = stamps.cpu().numpy().reshape(8, 16)
     if which == "critic" and MODE == 1:
-        print(f"   (exact-loop tiles of the three launches: {ctx.get(ctx.EXACT_TILES)} of {3 * -(-Rb // 32)})")
+        print(f"   (exact-loop tiles of the three launches: {ctx.get(ctx.EXACT_TILES)} of {3 * -(-Rb // 32)}; "
+              f"launches on the f16 copy: {ctx.get(ctx.X16_LAUNCHES)})")
     if ctx.get(ctx.W8_LAUNCHES) > w8_before:  # eight equal waves: print waves 0-3 and wave 4 (the SIMD partner of wave 0)
         tot = s8.sum(1)
         ntile = -(-(Rb * A) // 32 // 256)
