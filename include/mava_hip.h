@@ -61,9 +61,12 @@ enum {
                                       gradient launches (96..287 inputs) ran in the exact-input tile loop - inputs exact in f16: hi plane
                                       only, two MFMAs per product, the next x tile staged beside this one (ppo_train_h2.hip) -, summed
                                       over launches.  Reading it waits for the device; 0 is the only value that can be written */
-  MAVA_CTX_X16_LAUNCHES = 9        /* diagnostic counter on the device: wide f16x2 critic launches of the handle that staged their input
+  MAVA_CTX_X16_LAUNCHES = 9,       /* diagnostic counter on the device: wide f16x2 critic launches of the handle that staged their input
                                       from the caller's f16 copy (mava_ppo_critic_grad_x16_f32 with a valid copy).  Reading it waits for
                                       the device; 0 is the only value that can be written */
+  MAVA_CTX_X16_W8_LAUNCHES = 10    /* the same for the eight-wave f16x2 kernel (discrete actor <= 16 actions, value network on <= 127
+                                      inputs): launches of mava_ppo_actor_grad_x16_f32 / mava_ppo_critic_grad_x16_f32 that staged their
+                                      input from the f16 record */
 };
 int mava_ctx_create(mava_ctx** out);
 int mava_ctx_destroy(mava_ctx* ctx); /* frees the handle's workspaces; NULL is a no-op */
@@ -236,7 +239,21 @@ int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, int din, co
                                  const float* old_value, const float* targets, const int32_t* idx,
                                  long idx_base, int Rb, int A, float clip_eps, float vf_coef,
                                  float* slab, long slab_stride, int n_slab, const uint16_t* input16,
-                                 const uint32_t* input16_valid, mava_stream_t s);
+                                 const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
+/* input16_ld: halves between rows of input16; 0 = din (all the wide kernel takes).  The eight-wave kernel (din <= 127, x_share == 1,
+ * no aggregation) reads a record with input16_ld % 8 == 0 and input16_ld >= din on a 16-byte aligned base; where input16_ld > din
+ * the row is laid out like mava_rollout_ff_records16_f32's view16 (din values, 1.0, zeros to a multiple of 8).  Such launches are
+ * counted by MAVA_CTX_X16_W8_LAUNCHES.  Odd din, a misaligned base or row, MAVA_CTX_TRAIN_VARIANT bit 1, a word that is not 1:
+ * the record is not read. */
+
+/* mava_ppo_actor_grad_f32 with an f16 record of agents_view under the same contract: input16 (rows of agents_view, input16_ld)
+ * IEEE binary16 as above, input16_valid its device word.  The eight-wave kernel reads the word once per block and with 1 stages
+ * its input with 16-byte loads and LDS stores of the halves - no conversion; the gradient has the same bits either way. */
+int mava_ppo_actor_grad_x16_f32(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
+                                const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
+                                const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base, int Rb,
+                                int A, float clip_eps, float ent_coef, float* slab, long slab_stride, int n_slab,
+                                const uint16_t* input16, const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
 
 /* Both gradient kernels read MAVA_CTX_MATMUL_MODE, the critic also MAVA_CTX_CRITIC_AGGREGATION, from their handle. */
 
@@ -579,6 +596,22 @@ int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions, const floa
                             uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
                             float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
                             uint32_t* state16_valid, mava_stream_t s);
+/* ... and / or an f16 record of agents_view, for mava_ppo_actor_grad_x16_f32 (and mava_ppo_critic_grad_x16_f32 under a
+ * decentralised critic): view16 (T+1, E, A, RP) IEEE binary16 with RP = 8 * ceil((A + O + 1) / 8), contiguous, 16-byte aligned - every
+ * slot's row is the row of the kernel's LDS image: halves [0, A+O) the observation (agents_view is their conversion to f32), half
+ * A+O 1.0, the rest 0 - and view16_valid, a device word under state16_valid's protocol (0 or 1 on entry; left 1 when every
+ * slot-0 value of agents_view had a zero low f16 term, else 0).  Every instance takes it, shared critic or not; each of the two
+ * pairs may be NULL on its own. */
+int mava_rollout_ff_records16_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                                  int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                                  uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                                  int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                  int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                  int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                                  uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                                  uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                  float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                  uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, mava_stream_t s);
 /* The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of agents_view
  * (T+1, E, A, obs_dim) f32, global_state (T+1, E, gs_dim) f32 (NULL with gs_dim 0: none), action_mask (T+1, E, A,
  * n_actions) u8 and step_count (T+1, E, A) i32, in one launch.  Slots 1..T are not touched. */

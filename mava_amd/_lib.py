@@ -61,7 +61,9 @@ _SIGNATURES = {
     "mava_ppo_actor_grad_f32": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32,
                                 vp],
     "mava_ppo_critic_grad_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp],
-    "mava_ppo_critic_grad_x16_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp, vp, vp],
+    "mava_ppo_critic_grad_x16_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp, vp, i32, vp],
+    "mava_ppo_actor_grad_x16_f32": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32,
+                                    vp, vp, i32, vp],
     "mava_synth_rware_step": [i32, i32, i32, i32, i32, i32, i32, u64, u32, vp, u32, i32] + [vp] * 14 + [vp, i32, vp],
     "mava_lbf_step": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
     "mava_lbf_step_real_next": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 24 + [vp],
@@ -94,6 +96,8 @@ _SIGNATURES = {
                                 + [vp, vp, f32, f32, vp, vp, vp, vp],
     "mava_rollout_ff_x16_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
                                + [vp, vp, f32, f32, vp, vp, vp, vp, vp, vp],
+    "mava_rollout_ff_records16_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
+                                     + [vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp],
     "mava_rollout_carry": [i32, i32, i32, i32, lng, i32, vp, vp, vp, vp, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],
@@ -170,6 +174,7 @@ class Ctx:
     MATMUL_MODE, CRITIC_AGGREGATION, GAE_VARIANT, POLICY_VARIANT, H2_LAUNCHES, TRAIN_VARIANT, W8_LAUNCHES, W1_SPLIT_FRESH = 0, 1, 2, 3, 4, 5, 6, 7
     EXACT_TILES = 8  # wide f16x2 critic: tiles run in the exact-input loop (a device counter; reading it synchronises)
     X16_LAUNCHES = 9  # wide f16x2 critic: launches that staged x from the f16 copy (a device counter; reading it synchronises)
+    X16_W8_LAUNCHES = 10  # eight-wave f16x2 kernel: launches that staged x from an f16 record (likewise)
 
     def __init__(self, matmul_mode: str = "f32", critic_aggregation: bool = True):
         if matmul_mode not in ("f32", "f16x2"):

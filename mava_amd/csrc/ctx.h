@@ -22,9 +22,10 @@ struct mava_ctx {
   int w1_key_din[2];              // instantiation's, 12 or 18); a wide launch skips its own pack only when all three match.  What the
   int w1_key_steps[2];            // key cannot see: a caller who rewrites the CONTENTS of the same buffer between the finish launch and
                                   // the next gradient launch must clear the flag
-  unsigned long long* exact_tiles;  // two device words (allocated by the first wide f16x2 launch, null before).  [0]: 32-row tiles
+  unsigned long long* exact_tiles;  // three device words (allocated by the first launch that may add to one, null before).  [0]: 32-row tiles
                                     // that the wide kernels' blocks ran in their exact-input tile loop (ppo_train_h2.hip), summed over
-                                    // launches; [1]: wide critic launches that staged x from the caller's f16 copy (TrainTask::x16)
+                                    // launches; [1]: wide critic launches that staged x from the caller's f16 copy (TrainTask::x16);
+                                    // [2]: eight-wave launches (ppo_train_w8.hip) that did
 };
 
 static inline int mava_ctx_matmul_mode(const mava_ctx* c) { return c ? c->matmul_mode : 0; }

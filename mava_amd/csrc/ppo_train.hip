@@ -1031,13 +1031,11 @@ extern "C" int mava_adv_stats_batched_f64(const float* adv, const int32_t* idx, 
   return MAVA_OK;
 }
 
-extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int din, int n_actions,
-                                       const float* agents_view, const uint8_t* action_mask,
-                                       const int32_t* action, const float* old_log_prob,
-                                       const float* advantages, const double* adv_stats,
-                                       const int32_t* idx, long idx_base, int Rb, int A,
-                                       float clip_eps, float ent_coef, float* slab, long slab_stride,
-                                       int n_slab, hipStream_t s) {
+static int actor_grad_impl(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
+                           const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
+                           const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base, int Rb, int A,
+                           float clip_eps, float ent_coef, float* slab, long slab_stride, int n_slab, const uint16_t* input16,
+                           const uint32_t* input16_valid, int input16_ld, hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && n_actions >= 1 && n_actions <= 32, 0,
                  "mava_ppo_actor_grad_f32: din=%d n_actions=%d unsupported", din, n_actions);
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1 && n_slab >= 1 && n_slab <= 1024 && (long)Rb * A < (1L << 31), 1,
@@ -1053,6 +1051,8 @@ extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int d
   tk.stats = adv_stats; tk.clip_eps = clip_eps; tk.ent_coef = ent_coef; tk.slab = slab;
   tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
+  // (the f16 record of the input: only the eight-wave f16x2 kernel reads it, see ppo_train_task.h)
+  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
   if (mava_ctx_matmul_mode(ctx) == 1) {
     const int rc = mava_train_h2_launch(ctx, tk, n_slab, true, s);
     if (rc <= 0) return rc;  // launched (0) or failed (< 0); 1: shape not instantiated there
@@ -1060,6 +1060,32 @@ extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int d
   if (n_actions <= 8) return dispatch_kt<8, true>(tk, n_slab, s);
   if (n_actions <= 16) return dispatch_kt<16, true>(tk, n_slab, s);
   return dispatch_kt<32, true>(tk, n_slab, s);
+}
+
+extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int din, int n_actions,
+                                       const float* agents_view, const uint8_t* action_mask,
+                                       const int32_t* action, const float* old_log_prob,
+                                       const float* advantages, const double* adv_stats,
+                                       const int32_t* idx, long idx_base, int Rb, int A,
+                                       float clip_eps, float ent_coef, float* slab, long slab_stride,
+                                       int n_slab, hipStream_t s) {
+  return actor_grad_impl(ctx, params, din, n_actions, agents_view, action_mask, action, old_log_prob, advantages, adv_stats, idx,
+                         idx_base, Rb, A, clip_eps, ent_coef, slab, slab_stride, n_slab, nullptr, nullptr, 0, s);
+}
+
+// ... with an f16 record of agents_view, its row length in halves and its validity word on the device (include/mava_hip.h)
+extern "C" int mava_ppo_actor_grad_x16_f32(mava_ctx* ctx, const float* params, int din, int n_actions,
+                                           const float* agents_view, const uint8_t* action_mask,
+                                           const int32_t* action, const float* old_log_prob,
+                                           const float* advantages, const double* adv_stats,
+                                           const int32_t* idx, long idx_base, int Rb, int A,
+                                           float clip_eps, float ent_coef, float* slab, long slab_stride,
+                                           int n_slab, const uint16_t* input16, const uint32_t* input16_valid,
+                                           int input16_ld, hipStream_t s) {
+  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
+                 "mava_ppo_actor_grad_x16_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
+  return actor_grad_impl(ctx, params, din, n_actions, agents_view, action_mask, action, old_log_prob, advantages, adv_stats, idx,
+                         idx_base, Rb, A, clip_eps, ent_coef, slab, slab_stride, n_slab, input16, input16_valid, input16_ld, s);
 }
 
 // Continuous action head (networks.py:127-169): params = [MLP(din -> 128 -> 128 -> action_dim) | log_std(action_dim)],
@@ -1097,7 +1123,7 @@ extern "C" int mava_ppo_actor_grad_continuous_f32(const float* params, int din, 
 static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
                             const float* old_value, const float* targets, const int32_t* idx, long idx_base, int Rb, int A,
                             float clip_eps, float vf_coef, float* slab, long slab_stride, int n_slab, const uint16_t* input16,
-                            const uint32_t* input16_valid, hipStream_t s) {
+                            const uint32_t* input16_valid, int input16_ld, hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && x_share >= 1, 0, "mava_ppo_critic_grad_f32: din=%d x_share=%d", din, x_share);
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1 && n_slab >= 1 && n_slab <= 1024 && (long)Rb * A < (1L << 31), 1,
                  "mava_ppo_critic_grad_f32: Rb=%d A=%d n_slab=%d", Rb, A, n_slab);
@@ -1115,8 +1141,8 @@ static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const f
   tk.old_value = old_value; tk.targets = targets; tk.clip_eps = clip_eps; tk.vf_coef = vf_coef;
   tk.slab = slab; tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
-  // (the f16 copy of the input: only the wide f16x2 kernel reads it, see ppo_train_task.h)
-  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid;
+  // (the f16 copy of the input: only the wide and the eight-wave f16x2 kernels read it, see ppo_train_task.h)
+  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
   int rc = 1;
   if (mava_ctx_matmul_mode(ctx) == 1) rc = mava_train_h2_launch(ctx, tk, n_slab, false, s);
   if (ctx != nullptr) ctx->w1_fresh[1] = 0;  // one-shot whichever kernel takes the launch (the exact-f32 one does not read the copy)
@@ -1130,7 +1156,7 @@ extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int 
                                         float clip_eps, float vf_coef, float* slab, long slab_stride,
                                         int n_slab, hipStream_t s) {
   return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
-                          slab, slab_stride, n_slab, nullptr, nullptr, s);
+                          slab, slab_stride, n_slab, nullptr, nullptr, 0, s);
 }
 
 // ... with an f16 copy of critic_input and its validity word on the device (include/mava_hip.h)
@@ -1139,9 +1165,9 @@ extern "C" int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, 
                                             const int32_t* idx, long idx_base, int Rb, int A,
                                             float clip_eps, float vf_coef, float* slab, long slab_stride,
                                             int n_slab, const uint16_t* input16, const uint32_t* input16_valid,
-                                            hipStream_t s) {
-  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr), 3,
-                 "mava_ppo_critic_grad_x16_f32: input16 and input16_valid go together");
+                                            int input16_ld, hipStream_t s) {
+  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
+                 "mava_ppo_critic_grad_x16_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
   return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
-                          slab, slab_stride, n_slab, input16, input16_valid, s);
+                          slab, slab_stride, n_slab, input16, input16_valid, input16_ld, s);
 }

@@ -1325,6 +1325,18 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 2 : 1) void ppo_train_h2_k
 // WIDE launches: one pre-split copy of W1 per network kind in the caller's context handle (ctx.h), allocated on first
 // use and freed by mava_ctx_destroy (18 steps x 256 lanes x 32 bytes = 147 KB); filled by pack_w1_kernel on the launch
 // stream ahead of every launch - launches that share a handle must therefore be on one stream.
+// the handle's device counters (ctx.h): exact tiles, wide critic launches and eight-wave launches on an f16 record of x;
+// allocated with the first launch that may add to one of them
+int ctx_counters(mava_ctx* ctx, hipStream_t s) {
+  if (ctx->exact_tiles == nullptr) {
+    void* word = nullptr;
+    MAVA_HIP_CHECK(hipMalloc(&word, 3 * sizeof(unsigned long long)));
+    ctx->exact_tiles = static_cast<unsigned long long*>(word);
+    MAVA_HIP_CHECK(hipMemsetAsync(word, 0, 3 * sizeof(unsigned long long), s));
+  }
+  return MAVA_OK;
+}
+
 template <int NO, int S1, bool ACTOR, bool WIDE, int XV>
 int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
   const H2Layout L = make_h2_layout<NO, S1, WIDE>(ACTOR);
@@ -1350,20 +1362,15 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
     }
     fresh = 0;
     w1p = buf;
-    // the handle's device counters (ctx.h): exact tiles, launches on the f16 copy of x; allocated with the first wide launch
-    if (ctx->exact_tiles == nullptr) {
-      void* word = nullptr;
-      MAVA_HIP_CHECK(hipMalloc(&word, 2 * sizeof(unsigned long long)));
-      ctx->exact_tiles = static_cast<unsigned long long*>(word);
-      MAVA_HIP_CHECK(hipMemsetAsync(word, 0, 2 * sizeof(unsigned long long), s));
-    }
+    const int rc = ctx_counters(ctx, s);
+    if (rc != MAVA_OK) return rc;
   }
   TrainTask tkl = tk;
   tkl.exact_tiles = WIDE ? ctx->exact_tiles : nullptr;
   // the f16 copy of x: handed to the kernel only where it has the second staging form and the copy fits it (16-byte pieces of
   // 16-byte aligned rows, no forced x_lo products); whether the copy is VALID is the kernel's own look at the device word
   const bool x16_ok = WIDE && !ACTOR && XV == 4 && tk.x16 != nullptr && tk.x16_valid != nullptr && tk.din % 8 == 0 &&
-                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0;
+                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && (tk.x16_ld == 0 || tk.x16_ld == tk.din);
   if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; }
   tkl.x16_launches = x16_ok ? ctx->exact_tiles + 1 : nullptr;  // (the second word of the handle's counter allocation)
   g_train_last_instance = train_instance_id(2, ACTOR, false, WIDE, NO, S1, XV);
@@ -1426,6 +1433,11 @@ int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk_in, int n_slab, bool
   TrainTask tk = tk_in;
   tk.force_xlo = (ctx->train_variant & 2) != 0;
   if ((ctx->train_variant & 1) == 0) {  // the eight-wave kernel: the discrete actor and the value network on narrow inputs
+    if (tk.x16 != nullptr && tk.x16_valid != nullptr) {  // (its launches on the f16 record are counted in the third word)
+      const int rcc = ctx_counters(ctx, s);
+      if (rcc != MAVA_OK) return rcc;
+      tk.x16_launches = ctx->exact_tiles + 2;
+    }
     const int rc8 = mava_train_w8_launch(tk, n_slab, actor, s);
     if (rc8 <= 0) {
       if (rc8 == 0) { ++ctx->h2_launches; ++ctx->w8_launches; }

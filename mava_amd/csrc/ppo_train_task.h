@@ -37,6 +37,10 @@ struct TrainTask {
   const _Float16* x16;
   const uint32_t* x16_valid;
   unsigned long long* x16_launches;  // device word block 0 of a launch that read the copy adds 1 to (MAVA_CTX_X16_LAUNCHES), or null
+  // The eight-wave kernel (ppo_train_w8.hip) reads the same three through its second staging body, from a record whose rows are
+  // x16_ld halves apart (0: din) and, where x16_ld > din, laid out like the kernel's x image row: din values, 1.0 (the ones
+  // column), zeros up to a multiple of 8 halves.  Its x16_launches is the word behind MAVA_CTX_X16_W8_LAUNCHES.
+  int x16_ld;
 };
 
 // ppo_train_h2.hip: the same fused kernel on v_mfma_f32_32x32x16_f16 with every operand split into two f16 terms

@@ -128,9 +128,13 @@ inline W8Layout make_w8_layout() {
 // (phase stamps).  ROLE 0 (16 action lanes: every thread is a loss lane) does both.  All roles run the same barrier sequence
 // and the same matrix work on their own 16 features.  (A static priority raise for waves 4-7, the younger half that loses
 // issue arbitration against its SIMD partners - s_setprio 1 - was measured: 65.5 M env-steps/s either way.)
-template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE>
+// X16 (staging roles): the x tiles come from the task's f16 record of x (TrainTask::x16, rows x16_ld halves apart, laid out
+// like an x image row) - 16-byte loads and 16-byte LDS stores of the halves as they are into the hi plane: no split, no low
+// plane, no flag; every tile takes the two-product paths of P1 and dW1 (the loss role reads a flag that stays 0).
+template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE, bool X16 = false>
 __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, u8* lds) {
   constexpr bool DO_LOSS = ROLE != 2, DO_STAGE = ROLE != 1;
+  static_assert(!X16 || (DO_STAGE && XV == 2), "the f16 record is read by a staging role of an XV = 2 instance");
   // ACTOR = false: the value network on narrow inputs (ff_ippo's critic, ff_mappo.py:183-213): one output, the clipped value
   // loss on lane 0 of a row's NO loss lanes; its weights are split as WS * w and the layer accumulators unscaled by WU
   // (h2_core.h W_SCALE_CRITIC: the low terms of the weights leave f16's subnormal range)
@@ -295,6 +299,31 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   };
   u8* const xs_dummy = reinterpret_cast<u8*>(misc + 8);
   const int xsw = 16 * w8_sw(srow);
+  // X16: thread l16 of a row takes the 16-byte chunks l16, l16 + TPR, ... of the record's row; same rule for a chunk past the
+  // row's last one.  (Pieces are native 4 x 32-bit vectors read through a global-address-space pointer: an array of them stays
+  // in registers and the loads are global_load.)
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(1))) u32x4* x16_gptr;
+  constexpr int NPC16 = (4 * S1 + TPR - 1) / TPR;  // chunks per thread: an image row holds 4 S1 of them
+  // chunks staged per row: up to and including the one with the ones column when the record carries it (x16_ld > din)
+  const int rp16 = 8 * ((din + 8) >> 3);
+  const int nv16 = (tk.x16_ld < rp16 ? tk.x16_ld : rp16) >> 3;
+  auto stage_issue16 = [&](uint32_t fr, u32x4 (&xq)[NPC16]) {
+    const x16_gptr xrow = (x16_gptr)(tk.x16 + (long)fr * tk.x16_ld);
+#pragma unroll
+    for (int k = 0; k < NPC16; ++k) {
+      const int c = l16 + TPR * k;
+      xq[k] = xrow[(c < nv16) ? c : 0];
+    }
+  };
+  auto stage_commit16 = [&](int buf, const u32x4 (&xq)[NPC16]) {
+    u8* base = lds + L.xs + buf * WIMG + WROW * srow;
+#pragma unroll
+    for (int k = 0; k < NPC16; ++k) {
+      const int c = l16 + TPR * k;
+      *reinterpret_cast<u32x4*>((c < nv16) ? (base + ((16 * c) ^ xsw)) : xs_dummy) = xq[k];
+    }
+  };
   auto stage_commit = [&](int buf, const float (&xr)[NR]) {
     u8* base = lds + L.xs + buf * WIMG + WROW * srow;
     uint32_t lo_any = 0;
@@ -341,7 +370,15 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
 
   const long ntiles = (R + 31) / 32;
   long it = blockIdx.x;
-  float xr[NR];
+  float xr[X16 ? 1 : NR];
+  u32x4 xq[X16 ? NPC16 : 1];
+  // the two staging forms behind one pair of names
+  auto issue = [&](uint32_t fr) __attribute__((always_inline)) {
+    if constexpr (X16) stage_issue16(fr, xq); else stage_issue(fr, xr);
+  };
+  auto commit = [&](int b) __attribute__((always_inline)) {
+    if constexpr (X16) stage_commit16(b, xq); else stage_commit(b, xr);
+  };
   int r_act = 0, n_act = 0;
   float r_f0 = 0.0f, r_f1 = 0.0f, n_f0 = 0.0f, n_f1 = 0.0f;
   uint32_t r_m = 1u, n_m = 1u;
@@ -351,14 +388,14 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   if (it < ntiles) {
     if constexpr (DO_STAGE) {
       cursor_gather(cs, ps_next, as_next);
-      stage_issue(stage_row(ps_next, as_next), xr);
+      issue(stage_row(ps_next, as_next));
     }
     if constexpr (DO_LOSS) {
       cursor_gather(cl, pl_next, al_next);
       load_row((uint32_t)pl_next * Au + al_next, r_act, r_f0, r_f1, r_m);
     }
     if constexpr (DO_STAGE) {
-      stage_commit(0, xr);
+      commit(0);
       cursor_advance(cs);
     }
     if constexpr (DO_LOSS) cursor_advance(cl);
@@ -460,7 +497,7 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     WSTAMP(1);
     // next tile's gathers: their latency hides under P2 .. P3
     if (have_next) {
-      if constexpr (DO_STAGE) stage_issue(xrow_next, xr);
+      if constexpr (DO_STAGE) issue(xrow_next);
       if constexpr (DO_LOSS) load_row(lrow_next, n_act, n_f0, n_f1, n_m);
       if (itn + gridDim.x < ntiles) {
         if constexpr (DO_STAGE) { cursor_gather(cs, ps_next, as_next); cursor_advance(cs); }
@@ -472,7 +509,7 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     WSTAMP(3);
     // the other x buffer's flag: its last readers (the previous tile's dW1) are behind this barrier, its next writers (this
     // tile's commit) behind barrier B
-    if constexpr (DO_STAGE) {
+    if constexpr (DO_STAGE && !X16) {
       if (tid == (ROLE == 2 ? 256 : 0)) xflag[buf ^ 1] = 0u;
     }
 
@@ -591,7 +628,7 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     // the next tile's x rows have arrived: split + store them into the other buffer (its last readers, the dW1 product of
     // the previous tile, finished before barrier A; it is read again from the next tile's P1 on, three barriers away)
     if constexpr (DO_STAGE) {
-      if (have_next) stage_commit(buf ^ 1, xr);
+      if (have_next) commit(buf ^ 1);
     }
     WSTAMP(7);
     __syncthreads();  // B2: dy of all 32 rows visible; every reader of the partial logits is done
@@ -715,6 +752,9 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
 
   // ------------------------------------------------------------------ epilogue: one slab per block (x 1/R)
   __syncthreads();
+  if constexpr (X16) {  // proof that this launch read the f16 record
+    if (st == 0 && blockIdx.x == 0 && tk.x16_launches != nullptr) atomicAdd(tk.x16_launches, 1ull);
+  }
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
   const int oB2 = mlp_off_b2(din), oB3 = mlp_off_b3(din, no);
   const int Pn = mlp_param_count(din, no);
@@ -779,14 +819,34 @@ constexpr int w8_w2r(int no, int s1, int xv) {
 template <int NO, int S1, int XV, int W2R, bool ACTOR>
 __global__ __launch_bounds__(512, 2) void ppo_train_w8_kernel(TrainTask tk, W8Layout L) {
   extern __shared__ __attribute__((aligned(16))) u8 lds[];
+  // Instances that stage pairs of floats carry both staging forms: the launch passes x16_valid only when everything the host
+  // can see allows the f16 record (launch_w8), and the word itself - written by the kernel that wrote the record - is read here,
+  // once per block, with a wave-uniform load.  The two forms are separate bodies: neither holds the other's registers.
+  constexpr bool X16_CAPABLE = XV == 2;
   if constexpr (NO == 8) {
     if (threadIdx.x < 256) {
       w8_body<NO, S1, XV, W2R, ACTOR, 1>(tk, L, lds);
     } else {
-      w8_body<NO, S1, XV, W2R, ACTOR, 2>(tk, L, lds);
+      bool x16 = false;
+      if constexpr (X16_CAPABLE) {
+        if (tk.x16_valid != nullptr) x16 = __builtin_amdgcn_readfirstlane((int)*tk.x16_valid) == 1;
+      }
+      if (X16_CAPABLE && x16) {
+        if constexpr (X16_CAPABLE) w8_body<NO, S1, XV, W2R, ACTOR, 2, true>(tk, L, lds);
+      } else {
+        w8_body<NO, S1, XV, W2R, ACTOR, 2>(tk, L, lds);
+      }
     }
   } else {
-    w8_body<NO, S1, XV, W2R, ACTOR, 0>(tk, L, lds);
+    bool x16 = false;
+    if constexpr (X16_CAPABLE) {
+      if (tk.x16_valid != nullptr) x16 = __builtin_amdgcn_readfirstlane((int)*tk.x16_valid) == 1;
+    }
+    if (X16_CAPABLE && x16) {
+      if constexpr (X16_CAPABLE) w8_body<NO, S1, XV, W2R, ACTOR, 0, true>(tk, L, lds);
+    } else {
+      w8_body<NO, S1, XV, W2R, ACTOR, 0>(tk, L, lds);
+    }
   }
 }
 
@@ -799,8 +859,17 @@ int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
                                        L.end));
     attr_set = true;
   }
+  // the f16 record of x: handed to the kernel only where it has the second staging form and the record fits it (rows of whole
+  // 16-byte chunks on a 16-byte aligned base that hold at least the din values, one input row per agent row, no forced x_lo
+  // products); whether the record is VALID is the kernel's own look at the device word
+  TrainTask tkl = tk;
+  const int ld16 = tk.x16_ld != 0 ? tk.x16_ld : tk.din;
+  const bool x16_ok = XV == 2 && tk.x16 != nullptr && tk.x16_valid != nullptr && ld16 % 8 == 0 && ld16 >= tk.din &&
+                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && tk.xshare == 1 && tk.agg <= 1;
+  tkl.x16_ld = ld16;
+  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; }
   g_train_last_instance = train_instance_id(3, ACTOR, false, false, NO, S1, XV);
-  hipLaunchKernelGGL((ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>), dim3(n_slab), dim3(512), L.end, s, tk, L);
+  hipLaunchKernelGGL((ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>), dim3(n_slab), dim3(512), L.end, s, tkl, L);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }

@@ -77,6 +77,11 @@ struct RolloutArgs {
   // mava_rollout_ff_x16_f32 (null otherwise): the f16 copy of global_state, (T+1, E, A*O) with A*O % 8 == 0, and its validity
   // word (see the prologue).  Last members: the offsets of everything above stay what they were.
   _Float16* state16; uint32_t* state16_valid;
+  // mava_rollout_ff_records16_f32 (null otherwise): the f16 record of agents_view, (T+1, E, A, RP) with RP = 8 ceil((A+O+1) / 8) -
+  // the rows of the actor's x image as they are: the observation, 1.0 (the ones column that carries b1), zeros - and its
+  // validity word, same protocol as state16_valid.
+  _Float16* view16; uint32_t* view16_valid;
+  int v16_nc; uint32_t v16_nc_m;  // RP / 8 and its div_small factor (64 rows x v16_nc chunks: 64 * 16 * 16 < 65536)
 };
 
 // The kernel's arguments read again from the argument segment AT THE POINT OF USE.  The ~40 pointers and seeds of
@@ -233,6 +238,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
       *reinterpret_cast<_Float16*>(p + xa_plane) = x1;
       lo_any |= (uint32_t)__builtin_bit_cast(uint16_t, x1) & 0x7FFFu;
     }
+    if (lo_any != 0) XLF[2] = 1u;  // (agents_view alone: what view16's validity word reports)
     if (t512 < 64) {
       u8* p = lds + L.xa + (t512 >> 5) * 2 * xa_plane + (t512 & 31) * xa_row + 2 * din_a;
       *reinterpret_cast<_Float16*>(p) = (_Float16)1.0f;
@@ -278,16 +284,20 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   // observations loaded above are exact too, the low plane is zero for the whole rollout, and layer 1 runs two MFMAs per
   // product instead of three without reading that plane (the skipped product is exactly 0: same bits).
   const bool x_lo = __builtin_amdgcn_readfirstlane((int)*XLF) != 0;
-  // The f16 copy's validity word, one per launch: 1 when no block loaded a global-state value with a low term - then the f32
-  // record of slot 0 is the conversion of the halves in the image, like every later slot's.  The word holds 0 or 1 on entry.
-  // One thread per block counts itself in bits 1 .. 30, a block with a low term sets bit 31 first; the block that finds every
-  // other one counted stores the result.  (Nobody reads the word before the launch ends.)
-  if (SHARED && ACT_ROLE && tid == 0 && a.state16_valid != nullptr) {
+  // The validity word of an f16 record, one per launch: 1 when no block loaded a slot-0 value of the recorded array with a low
+  // term - then the f32 record of slot 0 is the conversion of the halves in the image, like every later slot's.  The word holds
+  // 0 or 1 on entry.  One thread per block counts itself in bits 1 .. 30, a block with a low term sets bit 31 first; the block
+  // that finds every other one counted stores the result.  (Nobody reads the word before the launch ends.)
+  auto publish_valid = [&](uint32_t* word, bool low_term) {
     uint32_t seen = 0;
-    if (XLF[1] != 0) seen = atomicOr(a.state16_valid, 0x80000000u);
+    if (low_term) seen = atomicOr(word, 0x80000000u);
     asm volatile("" : "+v"(seen) : : "memory");  // (the count below is issued behind the returned value)
-    const uint32_t old = atomicAdd(a.state16_valid, 2u);
-    if (((old >> 1) & 0x3FFFFFFFu) == gridDim.x - 1u) *a.state16_valid = (old & 0x80000000u) ? 0u : 1u;
+    const uint32_t old = atomicAdd(word, 2u);
+    if (((old >> 1) & 0x3FFFFFFFu) == gridDim.x - 1u) *word = (old & 0x80000000u) ? 0u : 1u;
+  };
+  if (ACT_ROLE && tid == 0) {
+    if (SHARED && a.state16_valid != nullptr) publish_valid(a.state16_valid, XLF[1] != 0);  // the global state
+    if (a.view16_valid != nullptr) publish_valid(a.view16_valid, XLF[2] != 0);               // agents_view
   }
   const int rowB = r * IMG_ROW + 16 * h;  // + 32 s: features 16s + 8h .. + 7 of image row r
   const long EA = (long)E * A;
@@ -529,6 +539,23 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
       }
     }
   };
+  // view16 of slot `slot` from the actor's images (critic group, beside the f32 copy of the same slot): the record's row is the
+  // image row's first v16_nc 16-byte chunks - the observation, the ones column, zeros - and the block's rows are contiguous in
+  // the record: one 16-byte LDS read and one 16-byte store per chunk, consecutive lanes on consecutive chunks.  The chunk count
+  // and its div_small factor come from the argument segment at the point of use; nothing is held across the step loop.
+  auto write_view16 = [&](long slot) {
+    const auto& a = args_here();  // (shadows the parameter: see args_here)
+    if (a.view16 != nullptr) {
+      int tid = tid_w;
+      asm volatile("" : "+v"(tid));
+      const int NC = a.v16_nc;
+      uint4* const dst16 = reinterpret_cast<uint4*>(a.view16) + (slot * EA + (long)e0 * A) * NC;
+      for (int j = tid; j < rows_ok * NC; j += 256) {
+        const int row = (int)div_small((uint32_t)j, a.v16_nc_m), c = j - row * NC;
+        dst16[j] = *reinterpret_cast<const uint4*>(lds + L.xa + (row >> 5) * 2 * xa_plane + (row & 31) * xa_row + 16 * c);
+      }
+    }
+  };
   auto write_out = [&](long slot, bool part_gs) {  // part_gs: the global state (actor group, after sampling); else the rest
     const auto& a = args_here();  // (shadows the parameter: see args_here)
     // The cursors' start values depend on the thread alone.  Computed from a thread id the compiler cannot see through,
@@ -562,6 +589,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
         }
       }
     }
+    if (!part_gs) write_view16(slot);
     if (part_gs) write_gs(slot, true);
     if (!part_gs) {
       uint8_t* dst = a.action_mask + (slot * EA + (long)e0 * A) * no;
@@ -575,6 +603,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   const int T_steps = a.T;
   const uint32_t t0 = a.t0;
   if (SHARED && ACT_ROLE && a.state16 != nullptr) write_gs(0L, false);  // slot 0 of the f16 copy: the image the prologue filled from memory
+  if (!ACT_ROLE) write_view16(0L);  // slot 0 of view16, likewise (the group that writes its other slots)
   for (int t = 0; t < T_steps; ++t) {
     const uint32_t step = t0 + (uint32_t)t;
     forward(true, true, step);
@@ -887,7 +916,7 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
                            uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
                            uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
                            float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                           uint32_t* state16_valid, hipStream_t s) {
+                           uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 1 && A >= 1 && O >= 2 && T >= 1 && n_actions >= 1 && time_limit >= 1, 0,
                  "mava_rollout_ff_f32: bad shape E=%d A=%d O=%d T=%d nA=%d", E, A, O, T, n_actions);
   MAVA_ARG_CHECK(actor_params && critic_params && step_count && run_return && run_length && ep_return && ep_length &&
@@ -915,6 +944,10 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
   MAVA_ARG_CHECK(state16 == nullptr || (critic_shared && (A * O) % 8 == 0 && (uintptr_t)state16 % 16 == 0), 2,
                  "mava_rollout_ff_x16_f32: state16 needs the shared critic, A*O %% 8 == 0 (A*O=%d) and 16-byte alignment", A * O);
   a.state16 = reinterpret_cast<_Float16*>(state16); a.state16_valid = state16_valid;
+  MAVA_ARG_CHECK((view16 == nullptr) == (view16_valid == nullptr), 1, "mava_rollout_ff_records16_f32: view16 and view16_valid go together");
+  MAVA_ARG_CHECK(view16 == nullptr || (uintptr_t)view16 % 16 == 0, 2, "mava_rollout_ff_records16_f32: view16 needs 16-byte alignment");
+  a.view16 = reinterpret_cast<_Float16*>(view16); a.view16_valid = view16_valid;
+  a.v16_nc = (A + O + 8) / 8; a.v16_nc_m = 65536u / (uint32_t)a.v16_nc + 1u;
   if (critic_shared) {
     if (s1a == 5 && s1c == 17 && A >= 4) return launch_rollout<8, 5, 17, true>(a, s);  // RWARE tiny / small-4ag (O 66, A 4)
 #ifndef MAVA_FAST_BUILD
@@ -944,7 +977,7 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
                          t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
                          agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
                          last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, s);
+                         nullptr, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 // mava_rollout_ff_f32 that also leaves what the caller copied or added after it: last_reward / last_done (E, A) = reward /
@@ -965,7 +998,7 @@ extern "C" int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions
                          t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
                          agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
                          last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, nullptr, nullptr, s);
+                         last_done, step_counter, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 // ... that also writes the f16 copy of the shared global state and its validity word (include/mava_hip.h).  last_reward /
@@ -987,7 +1020,29 @@ extern "C" int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions,
                          t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
                          agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
                          last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, state16, state16_valid, s);
+                         last_done, step_counter, state16, state16_valid, nullptr, nullptr, s);
+}
+
+// ... and / or the f16 record of agents_view with its own validity word (include/mava_hip.h): each pair may be null on its own.
+extern "C" int mava_rollout_ff_records16_f32(const float* actor_params, int n_actions, const float* critic_params,
+                                             int critic_shared, int E, int A, int O, int T, int time_limit,
+                                             uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
+                                             uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
+                                             int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                                             float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
+                                             int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
+                                             float* last_val, float* info_return, int32_t* info_length,
+                                             uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                             float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                             uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid,
+                                             hipStream_t s) {
+  MAVA_ARG_CHECK((last_reward == nullptr) == (last_done == nullptr) && (last_reward != nullptr || step_counter == nullptr), 1,
+                 "mava_rollout_ff_records16_f32: last_reward, last_done (and step_counter) go together");
+  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
+                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
+                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
+                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
+                         last_done, step_counter, state16, state16_valid, view16, view16_valid, s);
 }
 
 // The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of the four observation

@@ -214,6 +214,16 @@ class FFLearner:
         for rep in self.reps:
             rep.state16 = torch.zeros((self.T + 1, self.E, 1, self.Oc), dtype=torch.float16, device=d) if self.x16 else None
             rep.state16_valid = torch.zeros((1,), dtype=torch.int32, device=d) if self.x16 else None
+        # The same for agents_view and the eight-wave gradient kernel (ppo_train_w8.hip): the rollout's actor image rows - the
+        # observation, the ones column, zeros: RP = 8 * ceil((Oa + 1) / 8) halves - are kept as view16 ((T + 1) * E * A * RP * 2 bytes
+        # per replica: 304 MB at the headline shape) with a word of their own, and handed to every actor gradient launch and, under a
+        # decentralised critic, to every critic launch.  MAVA_X16=0 turns both records off, MAVA_X16_ACTOR=0 this one alone.
+        self.view16 = (self.fused_rollout and not self.continuous and self.matmul_mode == "f16x2" and self.Oa + 1 <= 128
+                       and os.environ.get("MAVA_X16", "1") != "0" and os.environ.get("MAVA_X16_ACTOR", "1") != "0")
+        rp = 8 * ((self.Oa + 8) // 8)
+        for rep in self.reps:
+            rep.view16 = torch.zeros((self.T + 1, self.E, self.A, rp), dtype=torch.float16, device=d) if self.view16 else None
+            rep.view16_valid = torch.zeros((1,), dtype=torch.int32, device=d) if self.view16 else None
         self._learn_calls = 0  # guards.check_f16_range: the previous call's metrics are checked from the second call on
         # One rank: nothing sits between the gradient kernels and Adam, so both slab sums, clip + Adam, the count increment and
         # the wide critic's W1 re-split run as TWO launches (ops.ppo_finish) instead of six.  With several replicas every
@@ -385,12 +395,12 @@ class FFLearner:
                 info_terminal=rep.info_terminal[n], adv=rep.adv, tgt=rep.tgt, gamma=float(s.gamma),
                 gae_lambda=float(s.gae_lambda), last_reward=rep.last_reward, last_done=rep.last_done,
                 step_counter=self.step_dev if u == 0 else None,  # (the launch leaves all three: nothing follows it)
-                state16=rep.state16, state16_valid=rep.state16_valid)
+                state16=rep.state16, state16_valid=rep.state16_valid, view16=rep.view16, view16_valid=rep.view16_valid)
               if not ok:
                 assert u == 0
-                self.fused_rollout = self.x16 = False
-                for r in self.reps:  # (nobody writes the copy: the critic launches must not be handed it)
-                    r.state16 = r.state16_valid = None
+                self.fused_rollout = self.x16 = self.view16 = False
+                for r in self.reps:  # (nobody writes the records: the gradient launches must not be handed them)
+                    r.state16 = r.state16_valid = r.view16 = r.view16_valid = None
                 return False
         if side:
             for st in self._roll_streams:
@@ -480,7 +490,9 @@ class FFLearner:
             else:
                 self._timed("actor_grad", ops.ppo_actor_grad, pa, av, rep.action_mask[:T].view(TEA, self.nA),
                             rep.action.view(TEA), rep.log_prob.view(TEA), rep.adv.view(TEA), stats, idx, base,
-                            self.Rb, A, self.nA, float(s.clip_eps), float(s.ent_coef), slab_a, ctx=self.ctx)
+                            self.Rb, A, self.nA, float(s.clip_eps), float(s.ent_coef), slab_a, ctx=self.ctx,
+                            input16=rep.view16[:T].view(TEA, -1) if self.view16 else None,
+                            input16_valid=rep.view16_valid if self.view16 else None)
             if not self.fused_tail:
                 ops.slab_reduce2(self.slab_a, self.Pa, self.g[: self.Pa], 2, self.g[self.P : self.P + 2], accumulate=u > 0)
         # pmean "device" of ff_mappo.py:228-238, RCCL over xGMI: the actor's slice travels on RCCL's stream while
@@ -489,11 +501,15 @@ class FFLearner:
         for u, rep in enumerate(self.reps):
             av = rep.agents_view[:T].view(TEA, self.Oa)
             cx = rep.global_state[:T].view(-1, self.Oc) if self.centralised else av
+            in16 = in16_valid = None
+            if self.x16:
+                in16, in16_valid = rep.state16[:T].view(-1, self.Oc), rep.state16_valid
+            elif self.view16 and not self.centralised and self.critic_share == 1:  # (the critic reads agents_view, one input row per agent row)
+                in16, in16_valid = rep.view16[:T].view(TEA, -1), rep.view16_valid
             self._timed("critic_grad", ops.ppo_critic_grad, pc, cx, self.critic_share, rep.value.view(TEA), rep.tgt.view(TEA),
                         idx, base, self.Rb, A, float(s.clip_eps), float(s.vf_coef),
                         self.slab_c[u * ns : (u + 1) * ns] if per_rep else self.slab_c, ctx=self.ctx,
-                        input16=rep.state16[:T].view(-1, self.Oc) if self.x16 else None,
-                        input16_valid=rep.state16_valid if self.x16 else None)
+                        input16=in16, input16_valid=in16_valid)
             if not self.fused_tail:
                 ops.slab_reduce2(self.slab_c, self.Pc, self.g[self.Pa : self.P], 1, self.g[self.P + 2 : self.P + 3], accumulate=u > 0)
         if self.fused_tail:

@@ -4,7 +4,8 @@ MAVA_HIPCC_EXTRA="-DMAVA_STAMPS").  Prints, per wave of block 0, the cycles spen
 `exact`: observations exact in f16 (bits), as RobotWarehouse's are - the wide critic then runs its exact-input tile loop and
 the eight-wave actor its two-product layer 1; without it the inputs are Gaussian (general loop, three products).
 `x16` (with `exact`): the critic launch is handed an f16 copy of its input and a validity word of 1, as the learner does after a
-fused rollout - the wide critic then stages its x tiles from the copy."""
+fused rollout - the wide critic then stages its x tiles from the copy, and the eight-wave actor from a record of its rows laid
+out as the rollout's view16 (the observation, 1.0, zeros up to a multiple of 8 halves)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -56,7 +57,13 @@ for which in ("critic", "actor"):
         olp, adv = -torch.rand(TE * A, device=dev) - 1.0, torch.randn(TE * A, device=dev)
         st = ops.adv_stats(adv, perm, 0, Rb, A)
         slab = torch.zeros(256, params.numel() + 2, device=dev)
-        run = lambda: ops.ppo_actor_grad(params, x, mask, act, olp, adv, st, perm, 0, Rb, A, nA, 0.2, 0.01, slab, ctx=ctx)
+        v16 = v16_valid = None
+        if X16 and EXACT:
+            v16 = torch.zeros(TE * A, 8 * ((din + 8) // 8), dtype=torch.float16, device=dev)
+            v16[:, :din] = x.half(); v16[:, din] = 1.0
+            v16_valid = torch.ones(1, dtype=torch.int32, device=dev)
+        run = lambda: ops.ppo_actor_grad(params, x, mask, act, olp, adv, st, perm, 0, Rb, A, nA, 0.2, 0.01, slab, ctx=ctx,
+                                         input16=v16, input16_valid=v16_valid)
     w8_before = ctx.get(ctx.W8_LAUNCHES)
     for _ in range(2):
         run()
@@ -70,6 +77,7 @@ for which in ("critic", "actor"):
     if ctx.get(ctx.W8_LAUNCHES) > w8_before:  # eight equal waves: print waves 0-3 and wave 4 (the SIMD partner of wave 0)
         tot = s8.sum(1)
         ntile = -(-(Rb * A) // 32 // 256)
+        print(f"   (eight-wave launches on the f16 record so far: {ctx.get(ctx.X16_W8_LAUNCHES)})")
         print(f"== {which} (eight-wave kernel): launch {a.elapsed_time(b):.3f} ms, block 0 cycles per wave {tot.tolist()}, {ntile} tiles per block")
         for i, n in enumerate(names_w8):
             print(f"   {n:24s} " + "  ".join(f"{s8[w, i] / ntile:8.0f}" for w in (0, 1, 4, 5)) + f"   ({100 * s8[0, i] / tot[0]:5.1f} %)")
