@@ -48,7 +48,9 @@ enum {
   MAVA_CTX_H2_LAUNCHES = 4,        /* diagnostic counter: gradient launches of this handle that ran on the f16x2 kernels */
   MAVA_CTX_TRAIN_VARIANT = 5,      /* f16x2 gradient kernels, bit 0: 0 (default) = the eight-wave actor kernel (ppo_train_w8.hip) where it
                                       is instantiated, 1 = the four-wave kernels (ppo_train_h2.hip) only; bit 1: always run the x_lo
-                                      products that inputs exact in f16 skip (same bits either way: tests); for A/B measurements */
+                                      products that inputs exact in f16 skip (same bits either way: tests); bit 2: the eight-wave kernel
+                                      staging from an f16 record keeps the layer-1 weight gradient at the end of each tile instead of
+                                      running it under the next tile's loss phase (same bits either way: tests); for A/B measurements */
   MAVA_CTX_W8_LAUNCHES = 6,        /* diagnostic counter: ... of which on the eight-wave kernel */
   MAVA_CTX_W1_SPLIT_FRESH = 7,     /* read: 1 while the handle's pre-split W1 copy (wide f16x2 critic, 96..287 inputs) holds the W1 that
                                       mava_ppo_finish_f32 wrote for the critic at p + Pa, critic_din inputs.  The next
@@ -64,9 +66,12 @@ enum {
   MAVA_CTX_X16_LAUNCHES = 9,       /* diagnostic counter on the device: wide f16x2 critic launches of the handle that staged their input
                                       from the caller's f16 copy (mava_ppo_critic_grad_x16_f32 with a valid copy).  Reading it waits for
                                       the device; 0 is the only value that can be written */
-  MAVA_CTX_X16_W8_LAUNCHES = 10    /* the same for the eight-wave f16x2 kernel (discrete actor <= 16 actions, value network on <= 127
+  MAVA_CTX_X16_W8_LAUNCHES = 10,   /* the same for the eight-wave f16x2 kernel (discrete actor <= 16 actions, value network on <= 127
                                       inputs): launches of mava_ppo_actor_grad_x16_f32 / mava_ppo_critic_grad_x16_f32 that staged their
                                       input from the f16 record */
+  MAVA_CTX_W8_DEFER_LAUNCHES = 11  /* ... of which ran the deferred-dW1 tile loop (role-split instances, <= 8 actions, unless
+                                      MAVA_CTX_TRAIN_VARIANT bit 2 is set).  Reading it waits for the device; 0 is the only value that
+                                      can be written */
 };
 int mava_ctx_create(mava_ctx** out);
 int mava_ctx_destroy(mava_ctx* ctx); /* frees the handle's workspaces; NULL is a no-op */

@@ -175,6 +175,7 @@ class Ctx:
     EXACT_TILES = 8  # wide f16x2 critic: tiles run in the exact-input loop (a device counter; reading it synchronises)
     X16_LAUNCHES = 9  # wide f16x2 critic: launches that staged x from the f16 copy (a device counter; reading it synchronises)
     X16_W8_LAUNCHES = 10  # eight-wave f16x2 kernel: launches that staged x from an f16 record (likewise)
+    W8_DEFER_LAUNCHES = 11  # ... of which ran the deferred-dW1 tile loop (likewise)
 
     def __init__(self, matmul_mode: str = "f32", critic_aggregation: bool = True):
         if matmul_mode not in ("f32", "f16x2"):

@@ -41,6 +41,11 @@ struct TrainTask {
   // x16_ld halves apart (0: din) and, where x16_ld > din, laid out like the kernel's x image row: din values, 1.0 (the ones
   // column), zeros up to a multiple of 8 halves.  Its x16_launches is the word behind MAVA_CTX_X16_W8_LAUNCHES.
   int x16_ld;
+  // ... and, on its role-split instances, runs the tile loop in the deferred-dW1 form when it stages from the record (the dW1
+  // product of tile n inside the loss phase of tile n + 1): no_defer != 0 keeps the record path on the schedule with dW1 at
+  // the tile's end (MAVA_CTX_TRAIN_VARIANT bit 2); defer_launches is the word behind MAVA_CTX_W8_DEFER_LAUNCHES, or null.
+  int no_defer;
+  unsigned long long* defer_launches;
 };
 
 // ppo_train_h2.hip: the same fused kernel on v_mfma_f32_32x32x16_f16 with every operand split into two f16 terms

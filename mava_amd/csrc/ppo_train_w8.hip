@@ -40,6 +40,18 @@ constexpr int STATS_BLOCKS = 128;  // == ppo_train.hip (mava_adv_stats_blocks)
 #define MAVA_W8_GWD 1
 #endif
 constexpr int GWD = MAVA_W8_GWD;  // operand prefetch depth of the weight-gradient products
+// Deferred-dW1 form of the role-split tile loop on the f16 record (w8_body, DF): 2 = both wave groups run a tile's dW1 product
+// inside the next tile's loss phase; 1 = only the staging waves 4-7 do, waves 0-3 keep theirs at the tile's end, alone on their
+// SIMDs; 0 = neither (the schedule with dW1 as the last phase of its own tile, which MAVA_CTX_TRAIN_VARIANT bit 2 selects at run
+// time).  Measured once each (profiles/defer_*): a 32-row tile of the headline instance takes 9092 cycles at 0, 8748
+// at 2 and 8488 at 1 - on waves 0-3 the product does not hide under the loss, it lengthens P3 by ~540 cycles (the wave stalls at
+// each MFMA's issue, its SIMD partner running the same product at the same time), where at the tile's end, with the partner gone
+// ahead into the next tile's P1 and to barrier A, it takes ~480 instead of ~920.
+#ifndef MAVA_W8_DEFER
+#define MAVA_W8_DEFER 1
+#endif
+constexpr int W8_DEFER = MAVA_W8_DEFER;
+static_assert(W8_DEFER >= 0 && W8_DEFER <= 2, "MAVA_W8_DEFER is 0, 1 or 2");
 
 #ifdef MAVA_STAMPS
 #define WSTAMP_DECL unsigned long long ws_prev = __builtin_readcyclecounter(), ws_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -101,18 +113,22 @@ __host__ __device__ inline int w8_sw(int row) { return ((row & 3) << 1) | (((row
 __host__ __device__ inline int w8_off(int row, int chunk) { return WROW * row + 16 * (chunk ^ w8_sw(row)); }
 
 struct W8Layout {
-  int h1, dz2, dz1, w2, xs, dy, small, end;
+  int h1, dz2, dz1, w2, xs, dy, small, h2hi, h2lo, end;
 };
+// One layout for every form of the tile loop.  The deferred-dW1 form (w8_body, DF != 0) reads the four planes of the x region
+// differently - three hi planes of x, a ring, and the hi plane of an h2 image of its own - and is the only one that touches h2lo.
 inline W8Layout make_w8_layout() {
   W8Layout L;
   L.h1 = 0;
   L.dz2 = L.h1 + WIMG;   // also the partial logits (f32), idle between barriers A and B2
-  L.dz1 = L.dz2 + WIMG;  // also the h2 image: every wave reads back only its OWN 16 columns of either
+  L.dz1 = L.dz2 + WIMG;  // also the h2 image (DF == 0): every wave reads back only its OWN 16 columns of either
   L.w2 = L.dz1 + WIMG;   // W2 [128 k][128 n]: row reads for dh1 = W2 . dz2 (the forward operand lives in registers)
   L.xs = L.w2 + 2 * W2PLANE;
-  L.dy = L.xs + 2 * WIMG;  // two x buffers
+  L.dy = L.xs + 2 * WIMG;  // two x buffers (hi, lo | hi, lo); DF != 0: x ring slots 0, 1, 2 | h2 hi plane
   L.small = L.dy + 2 * DYPLANE;
-  L.end = L.small + (32 + 16 + 16) * 4;  // f32: b3[32] | misc[16] | dummy
+  L.h2hi = L.xs + 3 * WPLANE32;                         // DF != 0: the fourth plane of the x region
+  L.h2lo = (L.small + (32 + 16 + 16) * 4 + 15) & ~15;  // f32: b3[32] | misc[16] | dummy, then DF != 0: the h2 image's lo plane
+  L.end = L.h2lo + WPLANE32;
   return L;
 }
 
@@ -131,10 +147,27 @@ inline W8Layout make_w8_layout() {
 // X16 (staging roles): the x tiles come from the task's f16 record of x (TrainTask::x16, rows x16_ld halves apart, laid out
 // like an x image row) - 16-byte loads and 16-byte LDS stores of the halves as they are into the hi plane: no split, no low
 // plane, no flag; every tile takes the two-product paths of P1 and dW1 (the loss role reads a flag that stays 0).
-template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE, bool X16 = false>
+// DF (roles 1 and 2 of a block whose staging role is the X16 twin; both roles read the same device word and agree): the
+// deferred-dW1 form of the tile loop.  The dW1 product of a tile has no place in the tile's dependency chain - it reads the
+// tile's x image and the wave's own columns of the dz1 image and adds into gW1[], which nobody reads before the epilogue - and
+// since the record the staging waves commit the next x tile in ~220 cycles and then wait ~860 at barrier B2 while waves 0-3 run
+// the loss, one dependent chain of vector instructions that leaves the matrix pipe and the LDS idle
+// (profiles/view16_after_phase_stamps.txt).  With DF == 2 the product of tile n runs inside P3 of tile n + 1 (once more behind
+// the loop for the block's last tile); DF == 1 has this form's storage and keeps the product at the tile's end.  Storage:
+//  - x lives in a ring of three hi planes of the x region (the record path never touches a lo plane): tile n of the block in
+//    slot n mod 3; P1 of tile n reads it, P3 of tile n commits tile n + 1 into slot (n + 1) mod 3, the deferred product in P3
+//    of tile n reads slot (n - 1) mod 3 (the argument for each slot stands at the commit);
+//  - h2 has an image of its own (L.h2hi: the fourth plane of the x region, L.h2lo), because the wave's dz1 columns of tile n
+//    must survive P2 of tile n + 1; DZ1I then holds dz1 only, and every wave still reads back only columns it wrote itself:
+//    program order is all the ordering either image needs;
+//  - no x_lo flag is read: both products of layer 1 are the two-product ones.
+// Same accumulators, same products, same tile order as DF == 0: the same bits.  Same __syncthreads sequence in every role.
+template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE, bool X16 = false, int DF = 0>
 __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, u8* lds) {
   constexpr bool DO_LOSS = ROLE != 2, DO_STAGE = ROLE != 1;
   static_assert(!X16 || (DO_STAGE && XV == 2), "the f16 record is read by a staging role of an XV = 2 instance");
+  static_assert(DF == 0 || (NO == 8 && XV == 2 && (ROLE == 1 || (ROLE == 2 && X16 && DF == 2))),
+                "the deferred-dW1 form belongs to the role-split instances on the f16 record; its staging role always defers");
   // ACTOR = false: the value network on narrow inputs (ff_ippo's critic, ff_mappo.py:183-213): one output, the clipped value
   // loss on lane 0 of a row's NO loss lanes; its weights are split as WS * w and the layer accumulators unscaled by WU
   // (h2_core.h W_SCALE_CRITIC: the low terms of the weights leave f16's subnormal range)
@@ -145,6 +178,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   u8* const DZ1I = lds + L.dz1;
   u8* const W2I = lds + L.w2;
   u8* const DYI = lds + L.dy;
+  u8* const H2HI = lds + (DF != 0 ? L.h2hi : L.dz1);            // the h2 image's planes
+  u8* const H2LO = lds + (DF != 0 ? L.h2lo : L.dz1 + WPLANE32);
   float* const YP = reinterpret_cast<float*>(lds + L.dz2);
   constexpr int YSTR = (NO == 8) ? 9 : NO;  // floats per (wave, row) of partial logits: 8 x 32 x YSTR x 4 bytes <= one image
   float* const B3s = reinterpret_cast<float*>(lds + L.small);
@@ -166,9 +201,9 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   for (int o = tid * 16; o < L.end; o += 512 * 16) *reinterpret_cast<uint4*>(lds + o) = make_uint4(0, 0, 0, 0);
   __syncthreads();
   if (tid < no) B3s[tid] = P[mlp_off_b3(din, no) + tid];
-  if (tid < 64) {  // the ones column of both x buffers: "row din" of W1 in the flat parameter vector is b1
-    const int b = tid >> 5, row = tid & 31;
-    *reinterpret_cast<_Float16*>(lds + L.xs + b * WIMG + w8_off(row, din >> 3) + 2 * (din & 7)) = (_Float16)1.0f;
+  if (tid < (DF != 0 ? 96 : 64)) {  // the ones column of both x buffers: "row din" of W1 in the flat parameter vector is b1
+    const int b = tid >> 5, row = tid & 31;  // (DF != 0: of the three ring slots - threads of the loss role, which knows the form)
+    *reinterpret_cast<_Float16*>(lds + L.xs + b * (DF != 0 ? WPLANE32 : WIMG) + w8_off(row, din >> 3) + 2 * (din & 7)) = (_Float16)1.0f;
   }
   {
     // W2 image: thread = (output feature n, quarter of the k range), sequential over k with the error-diffusion carry of
@@ -316,8 +351,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       xq[k] = xrow[(c < nv16) ? c : 0];
     }
   };
-  auto stage_commit16 = [&](int buf, const u32x4 (&xq)[NPC16]) {
-    u8* base = lds + L.xs + buf * WIMG + WROW * srow;
+  auto stage_commit16 = [&](int xo, const u32x4 (&xq)[NPC16]) {  // xo: byte offset of the hi plane in the x region
+    u8* base = lds + L.xs + xo + WROW * srow;
 #pragma unroll
     for (int k = 0; k < NPC16; ++k) {
       const int c = l16 + TPR * k;
@@ -376,8 +411,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   auto issue = [&](uint32_t fr) __attribute__((always_inline)) {
     if constexpr (X16) stage_issue16(fr, xq); else stage_issue(fr, xr);
   };
-  auto commit = [&](int b) __attribute__((always_inline)) {
-    if constexpr (X16) stage_commit16(b, xq); else stage_commit(b, xr);
+  auto commit = [&](int b) __attribute__((always_inline)) {  // b: x buffer; DF != 0: byte offset of the ring slot
+    if constexpr (X16) stage_commit16(DF != 0 ? b : b * WIMG, xq); else stage_commit(b, xr);
   };
   int r_act = 0, n_act = 0;
   float r_f0 = 0.0f, r_f1 = 0.0f, n_f0 = 0.0f, n_f1 = 0.0f;
@@ -435,13 +470,32 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   const int dyRd = DYROW * i + 8 * kg;
   const int dyTr = DYROW * trow + 8 * tp;
   int buf = 0;
+  // DF != 0: byte offsets in the x region of the ring slots of this tile, the next and the previous one (rotated at the loop's end)
+  int xo_cur = 0, xo_nxt = WPLANE32, xo_prv = 2 * WPLANE32;
+  // DF != 0: gW1[k][n = 16 v + i] += sum_rows x[row][k] dz1[row][n] for the tile whose x sits at `xsi` and whose dz1 columns this
+  // wave wrote last.  All operand reads first, then one product per accumulator and pass: the twelve MFMAs are independent of
+  // their neighbours and of the loss chain that follows them on waves 0-3 (each accumulator still takes a_hi . b_lo, then
+  // a_hi . b_hi, as mfma2w_alo0 does).
+  auto dw1_exact = [&](const u8* xsi) __attribute__((always_inline)) {
+    const Frag b = read_tr(DZ1I, WPLANE32, trOwn);
+    half8 a[KT1];
+#pragma unroll
+    for (int t = 0; t < KT1; ++t) a[t] = read_tr8(xsi + tr_addr(t), WROW);
+#pragma unroll
+    for (int t = 0; t < KT1; ++t) gW1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b.lo, gW1[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < KT1; ++t) gW1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b.hi, gW1[t], 0, 0, 0);
+  };
 
   WSTAMP_DECL
   for (; it < ntiles; it += gridDim.x, buf ^= 1) {
     WSTAMP(14);
     const long itn = it + gridDim.x;
     const bool have_next = itn < ntiles;
-    const u8* const XSI = lds + L.xs + buf * WIMG;
+    // (wave-uniform) DF == 2: no product is pending yet.  The guard saves the work, the bits do not depend on it: until the block's
+    // first P4 the dz1 image holds the prologue's zeros, and the product would add +0 to accumulators that are +0.
+    const bool first_tile = it == (long)blockIdx.x;
+    const u8* const XSI = lds + L.xs + (DF != 0 ? xo_cur : buf * WIMG);
     // rows of the next tile from the indices loaded a tile ago
     uint32_t xrow_next = DO_STAGE ? stage_row(ps_next, as_next) : 0u, lrow_next = DO_LOSS ? ((uint32_t)pl_next * Au + al_next) : 0u;
     if constexpr (DO_STAGE) asm volatile("" : "+v"(xrow_next));
@@ -449,7 +503,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
 
     // ---------------------------------------------------------------- P1: z1 = W1^T x^T (+ b1 through the ones column)
     f32x4 acc[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
-    const bool x_lo = __builtin_amdgcn_readfirstlane((int)xflag[buf]) != 0 || tk.force_xlo != 0;  // (wave-uniform: one branch per phase)
+    // (wave-uniform: one branch per phase; DF != 0: the record is exact in f16 and the launch does not force the low products)
+    const bool x_lo = DF == 0 && (__builtin_amdgcn_readfirstlane((int)xflag[buf]) != 0 || tk.force_xlo != 0);
     if (x_lo) {
       Frag xb[2];
 #pragma unroll
@@ -548,8 +603,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       }
       const Frag4 f = split4(h2[nt]);
       // h2 image: only this wave's own columns are ever read back (dy^T . h2 below)
-      *reinterpret_cast<half4*>(DZ1I + 4096 * nt + wrA) = f.hi;
-      *reinterpret_cast<half4*>(DZ1I + 4096 * nt + WPLANE32 + wrA) = f.lo;
+      *reinterpret_cast<half4*>(H2HI + 4096 * nt + wrA) = f.hi;
+      *reinterpret_cast<half4*>(H2LO + 4096 * nt + wrA) = f.lo;
       // partial logits of this wave's 16 features: the accumulator tile is the B operand of the 16-deep product
       const f32x4 y = mfma3k16(W3h, f, f32x4{0, 0, 0, 0});
       // register r of lane (row i, kg) is output 4 kg + r
@@ -563,6 +618,11 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     WSTAMP(6);
 
     // ---------------------------------------------------------------- P3: loss, d loss / d logits (x R) -> dy image
+    if constexpr (DO_LOSS && DF == 2) {
+      // the previous tile's dW1: its reads ahead of the partial-logit reads, its MFMAs ahead of the loss chain and executing under it
+      if (!first_tile) dw1_exact(lds + L.xs + xo_prv);
+      WSTAMP(15);
+    }
     if constexpr (DO_LOSS) {
       const float lo_c = 1.0f - tk.clip_eps, hi_c = 1.0f + tk.clip_eps;
       const bool rvalid = (it * 32 + lrow) < R;
@@ -627,10 +687,20 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     }
     // the next tile's x rows have arrived: split + store them into the other buffer (its last readers, the dW1 product of
     // the previous tile, finished before barrier A; it is read again from the next tile's P1 on, three barriers away)
+    // DF != 0, tile n of the block: the commit writes ring slot (n + 1) mod 3.  Its last readers were the deferred dW1 product of
+    // tile n - 2 (slot (n - 2) mod 3 is the same slot), run by every wave in P3 of tile n - 1, hence finished before barrier B2 of
+    // tile n - 1 (with DF == 1 waves 0-3 read it last at the end of tile n - 2, before barrier A of tile n - 1); its next readers are
+    // P1 of tile n + 1, behind barriers B2 and C of this tile.  Slot n mod 3 is only read in this phase's neighbourhood (P1 of this
+    // tile; the product of this tile in P3 of tile n + 1 or at this tile's end); slot (n - 1) mod 3 is read by the deferred
+    // product below and on waves 0-3 above, and written next by the commit of tile n + 1, behind barrier B2 of this tile.
     if constexpr (DO_STAGE) {
-      if (have_next) commit(buf ^ 1);
+      if (have_next) commit(DF != 0 ? xo_nxt : (buf ^ 1));
     }
     WSTAMP(7);
+    if constexpr (DO_STAGE && DF == 2) {
+      if (!first_tile) dw1_exact(lds + L.xs + xo_prv);  // the previous tile's dW1, in time this role spent waiting at B2
+      WSTAMP(15);
+    }
     __syncthreads();  // B2: dy of all 32 rows visible; every reader of the partial logits is done
     WSTAMP(8);
 
@@ -640,7 +710,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       Frag a, b;
       a.hi = read_tr8(DYI + dyTr, DYROW);
       a.lo = read_tr8(DYI + DYPLANE + dyTr, DYROW);
-      b = read_tr(DZ1I, WPLANE32, trOwn);
+      b.hi = read_tr8(H2HI + trOwn, WROW);
+      b.lo = read_tr8(H2LO + trOwn, WROW);
       gW3 = mfma3w(a, b, gW3);
     }
     f32x4 dz[2];
@@ -712,7 +783,11 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       }
     }
     WSTAMP(12);
-    {
+    if constexpr (DF == 2) {
+      // this tile's dW1 runs in P3 of the block's next tile, or behind the loop
+    } else if constexpr (DF == 1) {
+      dw1_exact(XSI);
+    } else {
       // gW1[k][n = 16 v + i] += sum_rows x[row][k] dz1[row][n]   (row din of gW1 = db1 through the ones column)
       const Frag b = read_tr(DZ1I, WPLANE32, trOwn);
       constexpr int D1 = GWD < KT1 ? GWD : KT1;
@@ -743,6 +818,15 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     WSTAMP(13);
     // no barrier here: the next tile's P1 reads the other x buffer (complete since B2) and writes the h1 image, whose
     // last readers (dW2) sit before barrier C; every other image is rewritten only behind barriers A .. B2
+    if constexpr (DF != 0) {
+      const int t = xo_prv;
+      xo_prv = xo_cur; xo_cur = xo_nxt; xo_nxt = t;
+    }
+  }
+  if constexpr (DF == 2) {
+    // the dW1 product of the block's last tile (a block without a tile has none pending)
+    if ((long)blockIdx.x < ntiles) dw1_exact(lds + L.xs + xo_prv);
+    WSTAMP(15);
   }
 #ifdef MAVA_STAMPS
   if (tk.stamps != nullptr && blockIdx.x == 0 && l == 0) {
@@ -754,6 +838,9 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   __syncthreads();
   if constexpr (X16) {  // proof that this launch read the f16 record
     if (st == 0 && blockIdx.x == 0 && tk.x16_launches != nullptr) atomicAdd(tk.x16_launches, 1ull);
+    if constexpr (DF == 2) {  // ... in the deferred-dW1 form
+      if (st == 0 && blockIdx.x == 0 && tk.defer_launches != nullptr) atomicAdd(tk.defer_launches, 1ull);
+    }
   }
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
   const int oB2 = mlp_off_b2(din), oB3 = mlp_off_b3(din, no);
@@ -824,7 +911,20 @@ __global__ __launch_bounds__(512, 2) void ppo_train_w8_kernel(TrainTask tk, W8La
   // once per block, with a wave-uniform load.  The two forms are separate bodies: neither holds the other's registers.
   constexpr bool X16_CAPABLE = XV == 2;
   if constexpr (NO == 8) {
-    if (threadIdx.x < 256) {
+    // The deferred-dW1 form of the tile loop (w8_body, DF) is chosen for the whole block, ahead of the role split: every wave reads
+    // the word (nothing writes it during the launch: the roles agree), the loss role to take the twin that shares the form's
+    // storage with the X16 staging twin.  The other branch is the role split as it stands without the form.
+    constexpr bool DEFER_CAPABLE = X16_CAPABLE && W8_DEFER != 0;
+    bool defer = false;
+    if constexpr (DEFER_CAPABLE) {
+      if (tk.x16_valid != nullptr && tk.no_defer == 0) defer = __builtin_amdgcn_readfirstlane((int)*tk.x16_valid) == 1;
+    }
+    if (DEFER_CAPABLE && defer) {
+      if constexpr (DEFER_CAPABLE) {
+        if (threadIdx.x < 256) w8_body<NO, S1, XV, W2R, ACTOR, 1, false, W8_DEFER>(tk, L, lds);
+        else w8_body<NO, S1, XV, W2R, ACTOR, 2, true, 2>(tk, L, lds);
+      }
+    } else if (threadIdx.x < 256) {
       w8_body<NO, S1, XV, W2R, ACTOR, 1>(tk, L, lds);
     } else {
       bool x16 = false;
@@ -853,6 +953,7 @@ __global__ __launch_bounds__(512, 2) void ppo_train_w8_kernel(TrainTask tk, W8La
 template <int NO, int S1, int XV, bool ACTOR>
 int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
   const W8Layout L = make_w8_layout();
+  MAVA_ARG_CHECK(L.end <= 163840, 8, "ppo_train_w8: %d bytes of LDS exceed the 160 KiB of a CU", L.end);
   static bool attr_set = false;
   if (!attr_set) {
     MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -867,7 +968,7 @@ int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
   const bool x16_ok = XV == 2 && tk.x16 != nullptr && tk.x16_valid != nullptr && ld16 % 8 == 0 && ld16 >= tk.din &&
                       (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && tk.xshare == 1 && tk.agg <= 1;
   tkl.x16_ld = ld16;
-  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; }
+  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; tkl.defer_launches = nullptr; }
   g_train_last_instance = train_instance_id(3, ACTOR, false, false, NO, S1, XV);
   hipLaunchKernelGGL((ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>), dim3(n_slab), dim3(512), L.end, s, tkl, L);
   MAVA_LAUNCH_CHECK();

@@ -28,7 +28,9 @@ if MODE == 1:  # phases of ppo_train_h2.hip
 # phases of ppo_train_w8.hip (the eight-wave actor kernel, default for the discrete actor; `w4` as a second argument keeps
 # the four-wave kernel)
 names_w8 = ["P1 mfma", "P1 relu+image", "gather issue", "barrier A", "P2 mfma", "P2 image+head", "barrier B", "P3 loss | x commit",
-            "barrier B2", "gW3+dz2+image", "gW2", "barrier C", "dh1+dz1 image", "gW1", "loop top", "-"]
+            "barrier B2", "gW3+dz2+image", "gW2", "barrier C", "dh1+dz1 image", "gW1", "loop top", "gW1 of prev tile (P3)"]
+# (the last one: the deferred-dW1 form on the f16 record, `exact x16` - inside P3, ahead of the loss on waves 0-3 and behind the
+# commit on waves 4-7; the "gW1" phase at the tile's end then reads about 0)
 l = lib()
 ctx = Ctx("f16x2" if MODE == 1 else "f32")
 if "w4" in sys.argv[2:]:
