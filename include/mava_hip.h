@@ -50,7 +50,9 @@ enum {
                                       is instantiated, 1 = the four-wave kernels (ppo_train_h2.hip) only; bit 1: always run the x_lo
                                       products that inputs exact in f16 skip (same bits either way: tests); bit 2: the eight-wave kernel
                                       staging from an f16 record keeps the layer-1 weight gradient at the end of each tile instead of
-                                      running it under the next tile's loss phase (same bits either way: tests); for A/B measurements */
+                                      running it under the next tile's loss phase (same bits either way: tests); bit 3: that deferred form
+                                      keeps its row gathers and cursor updates in front of barrier A instead of a tile further ahead
+                                      (same bits either way: tests); for A/B measurements */
   MAVA_CTX_W8_LAUNCHES = 6,        /* diagnostic counter: ... of which on the eight-wave kernel */
   MAVA_CTX_W1_SPLIT_FRESH = 7,     /* read: 1 while the handle's pre-split W1 copy (wide f16x2 critic, 96..287 inputs) holds the W1 that
                                       mava_ppo_finish_f32 wrote for the critic at p + Pa, critic_din inputs.  The next
@@ -69,9 +71,11 @@ enum {
   MAVA_CTX_X16_W8_LAUNCHES = 10,   /* the same for the eight-wave f16x2 kernel (discrete actor <= 16 actions, value network on <= 127
                                       inputs): launches of mava_ppo_actor_grad_x16_f32 / mava_ppo_critic_grad_x16_f32 that staged their
                                       input from the f16 record */
-  MAVA_CTX_W8_DEFER_LAUNCHES = 11  /* ... of which ran the deferred-dW1 tile loop (role-split instances, <= 8 actions, unless
+  MAVA_CTX_W8_DEFER_LAUNCHES = 11, /* ... of which ran the deferred-dW1 tile loop (role-split instances, <= 8 actions, unless
                                       MAVA_CTX_TRAIN_VARIANT bit 2 is set).  Reading it waits for the device; 0 is the only value that
                                       can be written */
+  MAVA_CTX_W8_AHEAD_LAUNCHES = 12  /* ... of which issued the x gathers a tile further ahead (the discrete actor's instances, unless
+                                      MAVA_CTX_TRAIN_VARIANT bit 3 is set; the value network keeps its gathers).  Likewise */
 };
 int mava_ctx_create(mava_ctx** out);
 int mava_ctx_destroy(mava_ctx* ctx); /* frees the handle's workspaces; NULL is a no-op */

@@ -176,6 +176,7 @@ class Ctx:
     X16_LAUNCHES = 9  # wide f16x2 critic: launches that staged x from the f16 copy (a device counter; reading it synchronises)
     X16_W8_LAUNCHES = 10  # eight-wave f16x2 kernel: launches that staged x from an f16 record (likewise)
     W8_DEFER_LAUNCHES = 11  # ... of which ran the deferred-dW1 tile loop (likewise)
+    W8_AHEAD_LAUNCHES = 12  # ... of which issued the row gathers a tile further ahead (likewise)
 
     def __init__(self, matmul_mode: str = "f32", critic_aggregation: bool = True):
         if matmul_mode not in ("f32", "f16x2"):

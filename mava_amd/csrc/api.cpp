@@ -20,7 +20,11 @@ extern "C" const char* mava_last_error(void) { return g_err; }
 extern "C" int mava_abi_version(void) { return 3; }  // 3: round-3 signatures (mava_ctx handle instead of process-wide setters)
 
 // ---- context handle (ctx.h) -------------------------------------------------------------------------------------------
-enum { CTX_MATMUL_MODE = 0, CTX_CRITIC_AGGREGATION = 1, CTX_GAE_VARIANT = 2, CTX_POLICY_VARIANT = 3, CTX_H2_LAUNCHES = 4, CTX_TRAIN_VARIANT = 5, CTX_W8_LAUNCHES = 6, CTX_W1_SPLIT_FRESH = 7, CTX_EXACT_TILES = 8, CTX_X16_LAUNCHES = 9, CTX_X16_W8_LAUNCHES = 10, CTX_W8_DEFER_LAUNCHES = 11 };
+enum { CTX_MATMUL_MODE = 0, CTX_CRITIC_AGGREGATION = 1, CTX_GAE_VARIANT = 2, CTX_POLICY_VARIANT = 3, CTX_H2_LAUNCHES = 4, CTX_TRAIN_VARIANT = 5, CTX_W8_LAUNCHES = 6, CTX_W1_SPLIT_FRESH = 7, CTX_EXACT_TILES = 8, CTX_X16_LAUNCHES = 9, CTX_X16_W8_LAUNCHES = 10, CTX_W8_DEFER_LAUNCHES = 11, CTX_W8_AHEAD_LAUNCHES = 12 };
+// word of the handle's device counters (ctx.h exact_tiles) behind a key
+static int ctx_counter_word(int key) {
+  return key == CTX_W8_AHEAD_LAUNCHES ? 4 : key == CTX_W8_DEFER_LAUNCHES ? 3 : key == CTX_X16_W8_LAUNCHES ? 2 : key == CTX_X16_LAUNCHES ? 1 : 0;
+}
 
 extern "C" int mava_ctx_create(mava_ctx** out) {
   MAVA_ARG_CHECK(out != nullptr, 0, "mava_ctx_create: null output pointer");
@@ -80,10 +84,11 @@ extern "C" int mava_ctx_set(mava_ctx* c, int key, long value) {
     case CTX_X16_LAUNCHES:
     case CTX_X16_W8_LAUNCHES:
     case CTX_W8_DEFER_LAUNCHES:
-      MAVA_ARG_CHECK(value == 0, 1, "mava_ctx_set: MAVA_CTX_X16_LAUNCHES / _W8_LAUNCHES / MAVA_CTX_W8_DEFER_LAUNCHES can only be reset (0) by the caller");
-      if (c->exact_tiles != nullptr) {  // (the second / third / fourth word of the same allocation)
+    case CTX_W8_AHEAD_LAUNCHES:
+      MAVA_ARG_CHECK(value == 0, 1, "mava_ctx_set: MAVA_CTX_X16_LAUNCHES / _W8_LAUNCHES / MAVA_CTX_W8_DEFER_LAUNCHES / _AHEAD_LAUNCHES can only be reset (0) by the caller");
+      if (c->exact_tiles != nullptr) {  // (the second .. fifth word of the same allocation)
         MAVA_HIP_CHECK(hipDeviceSynchronize());
-        MAVA_HIP_CHECK(hipMemset(c->exact_tiles + (key == CTX_W8_DEFER_LAUNCHES ? 3 : key == CTX_X16_W8_LAUNCHES ? 2 : 1), 0, sizeof(unsigned long long)));
+        MAVA_HIP_CHECK(hipMemset(c->exact_tiles + ctx_counter_word(key), 0, sizeof(unsigned long long)));
       }
       return MAVA_OK;
     default: mava_set_error("mava_ctx_set: unknown key %d", key); return MAVA_EARG(2);
@@ -104,11 +109,12 @@ extern "C" int mava_ctx_get(const mava_ctx* c, int key, long* value) {
     case CTX_EXACT_TILES:
     case CTX_X16_LAUNCHES:
     case CTX_X16_W8_LAUNCHES:
-    case CTX_W8_DEFER_LAUNCHES: {  // a device word: waits for the launches that add to it
+    case CTX_W8_DEFER_LAUNCHES:
+    case CTX_W8_AHEAD_LAUNCHES: {  // a device word: waits for the launches that add to it
       unsigned long long n = 0;
       if (c->exact_tiles != nullptr) {
         MAVA_HIP_CHECK(hipDeviceSynchronize());
-        MAVA_HIP_CHECK(hipMemcpy(&n, c->exact_tiles + (key == CTX_W8_DEFER_LAUNCHES ? 3 : key == CTX_X16_W8_LAUNCHES ? 2 : key == CTX_X16_LAUNCHES ? 1 : 0), sizeof(n), hipMemcpyDeviceToHost));
+        MAVA_HIP_CHECK(hipMemcpy(&n, c->exact_tiles + ctx_counter_word(key), sizeof(n), hipMemcpyDeviceToHost));
       }
       *value = (long)n;
       return MAVA_OK;

@@ -12,7 +12,8 @@ struct mava_ctx {
   int gae_variant;         // 0: default chunk / lane mapping of mava_gae_f32 (others: tools/gae_sweep.py)
   int policy_variant;      // 0: default acting-step launch (others: tools/policy_bench.py)
   int train_variant;       // f16x2 gradient kernels: bit 0 = four-wave kernels only (default: eight-wave actor kernel where instantiated); bit 1 = never skip the x_lo products;
-                           // bit 2 = the eight-wave kernel on an f16 record keeps dW1 at the tile's end (no deferred-dW1 tile loop)
+                           // bit 2 = the eight-wave kernel on an f16 record keeps dW1 at the tile's end (no deferred-dW1 tile loop);
+                           // bit 3 = its deferred-dW1 tile loop keeps the row gathers in front of barrier A (no gathers-ahead form)
   long h2_launches;        // diagnostic: gradient launches of this handle that ran on the f16x2 kernels
   long w8_launches;        // diagnostic: ... of which on the eight-wave kernel (ppo_train_w8.hip)
   void* w1_split[2];       // f16x2, inputs wider than 95: pre-split W1 in fragment order (actor, critic), lazily allocated
@@ -23,10 +24,10 @@ struct mava_ctx {
   int w1_key_din[2];              // instantiation's, 12 or 18); a wide launch skips its own pack only when all three match.  What the
   int w1_key_steps[2];            // key cannot see: a caller who rewrites the CONTENTS of the same buffer between the finish launch and
                                   // the next gradient launch must clear the flag
-  unsigned long long* exact_tiles;  // four device words (allocated by the first launch that may add to one, null before).  [0]: 32-row tiles
+  unsigned long long* exact_tiles;  // five device words (allocated by the first launch that may add to one, null before).  [0]: 32-row tiles
                                     // that the wide kernels' blocks ran in their exact-input tile loop (ppo_train_h2.hip), summed over
                                     // launches; [1]: wide critic launches that staged x from the caller's f16 copy (TrainTask::x16);
-                                    // [2]: eight-wave launches (ppo_train_w8.hip) that did; [3]: ... of which in the deferred-dW1 form
+                                    // [2]: eight-wave launches (ppo_train_w8.hip) that did; [3]: ... of which in the deferred-dW1 form; [4]: ... of which with the row gathers a tile ahead
 };
 
 static inline int mava_ctx_matmul_mode(const mava_ctx* c) { return c ? c->matmul_mode : 0; }

@@ -1326,14 +1326,14 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 2 : 1) void ppo_train_h2_k
 // use and freed by mava_ctx_destroy (18 steps x 256 lanes x 32 bytes = 147 KB); filled by pack_w1_kernel on the launch
 // stream ahead of every launch - launches that share a handle must therefore be on one stream.
 // the handle's device counters (ctx.h): exact tiles, wide critic launches and eight-wave launches on an f16 record of x, and the
-// eight-wave launches in the deferred-dW1 form;
+// eight-wave launches in the deferred-dW1 form and in its gathers-ahead form;
 // allocated with the first launch that may add to one of them
 int ctx_counters(mava_ctx* ctx, hipStream_t s) {
   if (ctx->exact_tiles == nullptr) {
     void* word = nullptr;
-    MAVA_HIP_CHECK(hipMalloc(&word, 4 * sizeof(unsigned long long)));
+    MAVA_HIP_CHECK(hipMalloc(&word, 5 * sizeof(unsigned long long)));
     ctx->exact_tiles = static_cast<unsigned long long*>(word);
-    MAVA_HIP_CHECK(hipMemsetAsync(word, 0, 4 * sizeof(unsigned long long), s));
+    MAVA_HIP_CHECK(hipMemsetAsync(word, 0, 5 * sizeof(unsigned long long), s));
   }
   return MAVA_OK;
 }
@@ -1434,12 +1434,14 @@ int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk_in, int n_slab, bool
   TrainTask tk = tk_in;
   tk.force_xlo = (ctx->train_variant & 2) != 0;
   tk.no_defer = (ctx->train_variant & 4) != 0;
+  tk.no_ahead = (ctx->train_variant & 8) != 0;
   if ((ctx->train_variant & 1) == 0) {  // the eight-wave kernel: the discrete actor and the value network on narrow inputs
     if (tk.x16 != nullptr && tk.x16_valid != nullptr) {  // (its launches on the f16 record are counted in the third word)
       const int rcc = ctx_counters(ctx, s);
       if (rcc != MAVA_OK) return rcc;
       tk.x16_launches = ctx->exact_tiles + 2;
       tk.defer_launches = ctx->exact_tiles + 3;
+      tk.ahead_launches = ctx->exact_tiles + 4;
     }
     const int rc8 = mava_train_w8_launch(tk, n_slab, actor, s);
     if (rc8 <= 0) {

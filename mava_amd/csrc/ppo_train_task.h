@@ -46,6 +46,11 @@ struct TrainTask {
   // the tile's end (MAVA_CTX_TRAIN_VARIANT bit 2); defer_launches is the word behind MAVA_CTX_W8_DEFER_LAUNCHES, or null.
   int no_defer;
   unsigned long long* defer_launches;
+  // ... and, in that form, issues the row gathers and advances the cursors a tile further ahead, off the path to barrier A
+  // (w8_body, AH): no_ahead != 0 keeps them where they were (MAVA_CTX_TRAIN_VARIANT bit 3); ahead_launches is the word behind
+  // MAVA_CTX_W8_AHEAD_LAUNCHES, or null.
+  int no_ahead;
+  unsigned long long* ahead_launches;
 };
 
 // ppo_train_h2.hip: the same fused kernel on v_mfma_f32_32x32x16_f16 with every operand split into two f16 terms

@@ -52,16 +52,33 @@ constexpr int GWD = MAVA_W8_GWD;  // operand prefetch depth of the weight-gradie
 #endif
 constexpr int W8_DEFER = MAVA_W8_DEFER;
 static_assert(W8_DEFER >= 0 && W8_DEFER <= 2, "MAVA_W8_DEFER is 0, 1 or 2");
+// Gathers-ahead form of the deferred-dW1 tile loop (w8_body, AH).  MAVA_W8_AHEAD_ROLES, bit 0: the staging role takes it, bit 1:
+// the loss role does; MAVA_W8_AHEAD_POS: where the staging waves' block of row gathers and cursor updates sits in P3 - 0: behind
+// the commit, in front of the deferred dW1 product; 1: behind the product.  Measured (profiles/ahead_bench.json,
+// headline ms per update against the parent in the same calls): roles 1 / pos 0 -0.05, roles 1 / pos 1 -0.04, roles 3 / pos 1 -0.03
+// and -0.04, roles 3 / pos 0 -0.02, roles 2 +0.03 - the loss role's block costs more in front of barrier C than it frees in front
+// of barrier A, where waves 0-3 wait anyway.  Default: the staging role alone, behind the commit.
+#ifndef MAVA_W8_AHEAD_ROLES
+#define MAVA_W8_AHEAD_ROLES 1
+#endif
+#ifndef MAVA_W8_AHEAD_POS
+#define MAVA_W8_AHEAD_POS 0
+#endif
+constexpr int W8_AHEAD_ROLES = MAVA_W8_AHEAD_ROLES, W8_AHEAD_POS = MAVA_W8_AHEAD_POS;
+static_assert(W8_AHEAD_ROLES >= 0 && W8_AHEAD_ROLES <= 3 && (W8_AHEAD_POS == 0 || W8_AHEAD_POS == 1), "MAVA_W8_AHEAD_ROLES is 0 .. 3, MAVA_W8_AHEAD_POS 0 or 1");
 
 #ifdef MAVA_STAMPS
-#define WSTAMP_DECL unsigned long long ws_prev = __builtin_readcyclecounter(), ws_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define WSTAMP(i)                                                   \
-  do {                                                              \
-    __builtin_amdgcn_sched_barrier(0);                              \
-    const unsigned long long ws_now = __builtin_readcyclecounter(); \
-    ws_acc[i] += ws_now - ws_prev;                                  \
-    ws_prev = ws_now;                                               \
-    __builtin_amdgcn_sched_barrier(0);                              \
+// Cycle sums per phase: accumulator i is lane i of ONE vector register, 32 bits each (a launch is ~1.2 M cycles) - sixteen 64-bit
+// sums in scalar registers cost the kernel, which is at its scalar register limit, spills and kernel-argument reloads inside the
+// stamped blocks, and the stamps then measured those
+#define WSTAMP_DECL unsigned ws_prev = (unsigned)__builtin_readcyclecounter(), ws_v = 0u;
+#define WSTAMP(i)                                                                                        \
+  do {                                                                                                   \
+    __builtin_amdgcn_sched_barrier(0);                                                                   \
+    const unsigned ws_now = (unsigned)__builtin_readcyclecounter();                                      \
+    ws_v += ((threadIdx.x & 63u) == (unsigned)(i)) ? (ws_now - ws_prev) : 0u;                            \
+    ws_prev = ws_now;                                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                                   \
   } while (0)
 #else
 #define WSTAMP_DECL
@@ -162,9 +179,22 @@ inline W8Layout make_w8_layout() {
 //    program order is all the ordering either image needs;
 //  - no x_lo flag is read: both products of layer 1 are the two-product ones.
 // Same accumulators, same products, same tile order as DF == 0: the same bits.  Same __syncthreads sequence in every role.
-template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE, bool X16 = false, int DF = 0>
+// AH (either role of a block in the deferred form; the roles need not agree: MAVA_W8_AHEAD_ROLES, default the staging role alone):
+// the row gathers, the index loads and the cursor updates leave the stretch in front of barrier A, which every wave is on the path
+// to, for places where the role waits:
+//  - staging role: P3, behind the commit.  The staging registers are free the moment the commit has stored them, so P3 of tile n
+//    commits the x of tile n + 1 and at once issues the gathers of tile n + 2 into the same registers, from the index that P3 of
+//    tile n - 1 loaded, and loads the index of tile n + 3.  The gathers are in flight for a whole tile; the role issues no other
+//    global load but that index load BEHIND them (loads retire in order: the commit waits for all but the last one);
+//  - loss role (measured, not the default): in front of barrier C, behind gW2.  The row of tile n + 1 is loaded straight into r_*, which P3 of tile n is done
+//    with - one tile later than without AH, still two barriers and two matrix phases ahead of its use - and the index of tile n + 2
+//    is loaded behind it.
+// The rule above cursor_gather holds: an index is consumed one tile after the block that loads it.  Same rows, same order: the
+// same bits.
+template <int NO, int S1, int XV, int W2R, bool ACTOR, int ROLE, bool X16 = false, int DF = 0, bool AH = false>
 __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, u8* lds) {
   constexpr bool DO_LOSS = ROLE != 2, DO_STAGE = ROLE != 1;
+  static_assert(!AH || DF != 0, "the gathers-ahead form is a form of the deferred-dW1 tile loop");
   static_assert(!X16 || (DO_STAGE && XV == 2), "the f16 record is read by a staging role of an XV = 2 instance");
   static_assert(DF == 0 || (NO == 8 && XV == 2 && (ROLE == 1 || (ROLE == 2 && X16 && DF == 2))),
                 "the deferred-dW1 form belongs to the role-split instances on the f16 record; its staging role always defers");
@@ -420,6 +450,11 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
   Cursor cs = cursor_at(DO_STAGE ? srow : 0), cl = cursor_at(DO_LOSS ? lrow : 0);
   int32_t ps_next = 0, pl_next = 0;
   uint32_t as_next = 0, al_next = 0;
+  // AH: the loads of this role stay in flight across the loop's back edge.  Everything the prologue loaded is waited for here,
+  // once (vmcnt(0); expcnt and lgkmcnt left alone): a prologue load the compiler still counts as pending at the loop's head -
+  // b2r, which the actor never touches before P2 - would put a wait for ALL loads, the gathers among them, in front of its first
+  // use in every tile
+  if constexpr (AH) __builtin_amdgcn_s_waitcnt(0x0F70);
   if (it < ntiles) {
     if constexpr (DO_STAGE) {
       cursor_gather(cs, ps_next, as_next);
@@ -437,6 +472,11 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     if (it + gridDim.x < ntiles) {
       if constexpr (DO_STAGE) { cursor_gather(cs, ps_next, as_next); cursor_advance(cs); }
       if constexpr (DO_LOSS) { cursor_gather(cl, pl_next, al_next); cursor_advance(cl); }
+      if constexpr (DO_STAGE && AH) {
+        // one stage more: the block's second tile in flight, the index of its third one loaded
+        issue(stage_row(ps_next, as_next));
+        if (it + 2 * (long)gridDim.x < ntiles) { cursor_gather(cs, ps_next, as_next); cursor_advance(cs); }
+      }
     }
   }
   __syncthreads();
@@ -497,9 +537,20 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     const bool first_tile = it == (long)blockIdx.x;
     const u8* const XSI = lds + L.xs + (DF != 0 ? xo_cur : buf * WIMG);
     // rows of the next tile from the indices loaded a tile ago
-    uint32_t xrow_next = DO_STAGE ? stage_row(ps_next, as_next) : 0u, lrow_next = DO_LOSS ? ((uint32_t)pl_next * Au + al_next) : 0u;
-    if constexpr (DO_STAGE) asm volatile("" : "+v"(xrow_next));
-    if constexpr (DO_LOSS) asm volatile("" : "+v"(lrow_next));
+    // (AH: formed where the role issues its loads)
+    uint32_t xrow_next = (DO_STAGE && !AH) ? stage_row(ps_next, as_next) : 0u, lrow_next = (DO_LOSS && !AH) ? ((uint32_t)pl_next * Au + al_next) : 0u;
+    if constexpr (DO_STAGE && !AH) asm volatile("" : "+v"(xrow_next));
+    if constexpr (DO_LOSS && !AH) asm volatile("" : "+v"(lrow_next));
+    // AH, staging role, tile n of the block: gathers of tile n + 2 into the registers that the commit of tile n + 1 has just
+    // emptied, then the index of tile n + 3
+    auto stage_ahead = [&]() __attribute__((always_inline)) {
+      if constexpr (DO_STAGE && AH) {
+        if (itn + gridDim.x < ntiles) {
+          issue(stage_row(ps_next, as_next));
+          if (itn + 2 * (long)gridDim.x < ntiles) { cursor_gather(cs, ps_next, as_next); cursor_advance(cs); }
+        }
+      }
+    };
 
     // ---------------------------------------------------------------- P1: z1 = W1^T x^T (+ b1 through the ones column)
     f32x4 acc[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
@@ -551,7 +602,7 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     }
     WSTAMP(1);
     // next tile's gathers: their latency hides under P2 .. P3
-    if (have_next) {
+    if (!AH && have_next) {
       if constexpr (DO_STAGE) issue(xrow_next);
       if constexpr (DO_LOSS) load_row(lrow_next, n_act, n_f0, n_f1, n_m);
       if (itn + gridDim.x < ntiles) {
@@ -683,7 +734,7 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
         loss_a += pg_row * invR;
         loss_b += ent_row * invR;
       }
-      r_act = n_act; r_f0 = n_f0; r_f1 = n_f1; r_m = n_m;
+      if constexpr (!AH) { r_act = n_act; r_f0 = n_f0; r_f1 = n_f1; r_m = n_m; }
     }
     // the next tile's x rows have arrived: split + store them into the other buffer (its last readers, the dW1 product of
     // the previous tile, finished before barrier A; it is read again from the next tile's P1 on, three barriers away)
@@ -697,9 +748,17 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       if (have_next) commit(DF != 0 ? xo_nxt : (buf ^ 1));
     }
     WSTAMP(7);
+    if constexpr (DO_STAGE && AH && W8_AHEAD_POS == 0) {
+      stage_ahead();
+      WSTAMP(16);
+    }
     if constexpr (DO_STAGE && DF == 2) {
       if (!first_tile) dw1_exact(lds + L.xs + xo_prv);  // the previous tile's dW1, in time this role spent waiting at B2
       WSTAMP(15);
+    }
+    if constexpr (DO_STAGE && AH && W8_AHEAD_POS != 0) {
+      stage_ahead();
+      WSTAMP(16);
     }
     __syncthreads();  // B2: dy of all 32 rows visible; every reader of the partial logits is done
     WSTAMP(8);
@@ -749,6 +808,14 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
       }
     }
     WSTAMP(10);
+    if constexpr (DO_LOSS && AH) {
+      // the next tile's row straight into r_* (P3 of this tile is done with it), then the index of the tile after next
+      if (have_next) {
+        load_row((uint32_t)pl_next * Au + al_next, r_act, r_f0, r_f1, r_m);
+        if (itn + gridDim.x < ntiles) { cursor_gather(cl, pl_next, al_next); cursor_advance(cl); }
+      }
+      WSTAMP(17);
+    }
     __syncthreads();  // C: dz2 image complete
     WSTAMP(11);
 
@@ -829,9 +896,8 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     WSTAMP(15);
   }
 #ifdef MAVA_STAMPS
-  if (tk.stamps != nullptr && blockIdx.x == 0 && l == 0) {
-    for (int k = 0; k < 16; ++k) tk.stamps[v * 16 + k] = ws_acc[k];
-  }
+  // (phases 16 and 17 behind the 8 x 16 words of every kernel: the buffer holds 144)
+  if (tk.stamps != nullptr && blockIdx.x == 0 && l < 18) tk.stamps[l < 16 ? v * 16 + l : 128 + 2 * v + (l - 16)] = ws_v;
 #endif
 
   // ------------------------------------------------------------------ epilogue: one slab per block (x 1/R)
@@ -840,6 +906,9 @@ __device__ __forceinline__ void w8_body(const TrainTask& tk, const W8Layout& L, 
     if (st == 0 && blockIdx.x == 0 && tk.x16_launches != nullptr) atomicAdd(tk.x16_launches, 1ull);
     if constexpr (DF == 2) {  // ... in the deferred-dW1 form
       if (st == 0 && blockIdx.x == 0 && tk.defer_launches != nullptr) atomicAdd(tk.defer_launches, 1ull);
+    }
+    if constexpr (AH) {  // ... with the gathers a tile ahead
+      if (st == 0 && blockIdx.x == 0 && tk.ahead_launches != nullptr) atomicAdd(tk.ahead_launches, 1ull);
     }
   }
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
@@ -919,7 +988,17 @@ __global__ __launch_bounds__(512, 2) void ppo_train_w8_kernel(TrainTask tk, W8La
     if constexpr (DEFER_CAPABLE) {
       if (tk.x16_valid != nullptr && tk.no_defer == 0) defer = __builtin_amdgcn_readfirstlane((int)*tk.x16_valid) == 1;
     }
-    if (DEFER_CAPABLE && defer) {
+    // ... and so is its gathers-ahead form (AH), on the actor's instances.  None of them has a scratch access in a tile loop with
+    // the staged rows held across a tile (kernel resources and ISA).  The value network keeps the gathers in front of
+    // barrier A: its loss is a dozen instructions, so its staging waves - commit, deferred dW1 - are the last at barrier B2 already
+    // and the block lengthens the tile there (ff_ippo 8.01 -> 8.08 - 8.13 ms per update with the form on both networks)
+    constexpr bool AHEAD_CAPABLE = DEFER_CAPABLE && ACTOR && W8_AHEAD_ROLES != 0;
+    if (DEFER_CAPABLE && defer && AHEAD_CAPABLE && tk.no_ahead == 0) {
+      if constexpr (AHEAD_CAPABLE) {
+        if (threadIdx.x < 256) w8_body<NO, S1, XV, W2R, ACTOR, 1, false, W8_DEFER, (W8_AHEAD_ROLES & 2) != 0>(tk, L, lds);
+        else w8_body<NO, S1, XV, W2R, ACTOR, 2, true, 2, (W8_AHEAD_ROLES & 1) != 0>(tk, L, lds);
+      }
+    } else if (DEFER_CAPABLE && defer) {
       if constexpr (DEFER_CAPABLE) {
         if (threadIdx.x < 256) w8_body<NO, S1, XV, W2R, ACTOR, 1, false, W8_DEFER>(tk, L, lds);
         else w8_body<NO, S1, XV, W2R, ACTOR, 2, true, 2>(tk, L, lds);
@@ -968,7 +1047,7 @@ int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
   const bool x16_ok = XV == 2 && tk.x16 != nullptr && tk.x16_valid != nullptr && ld16 % 8 == 0 && ld16 >= tk.din &&
                       (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && tk.xshare == 1 && tk.agg <= 1;
   tkl.x16_ld = ld16;
-  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; tkl.defer_launches = nullptr; }
+  if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; tkl.defer_launches = nullptr; tkl.ahead_launches = nullptr; }
   g_train_last_instance = train_instance_id(3, ACTOR, false, false, NO, S1, XV);
   hipLaunchKernelGGL((ppo_train_w8_kernel<NO, S1, XV, w8_w2r(NO, S1, XV), ACTOR>), dim3(n_slab), dim3(512), L.end, s, tkl, L);
   MAVA_LAUNCH_CHECK();

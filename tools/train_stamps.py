@@ -28,15 +28,18 @@ if MODE == 1:  # phases of ppo_train_h2.hip
 # phases of ppo_train_w8.hip (the eight-wave actor kernel, default for the discrete actor; `w4` as a second argument keeps
 # the four-wave kernel)
 names_w8 = ["P1 mfma", "P1 relu+image", "gather issue", "barrier A", "P2 mfma", "P2 image+head", "barrier B", "P3 loss | x commit",
-            "barrier B2", "gW3+dz2+image", "gW2", "barrier C", "dh1+dz1 image", "gW1", "loop top", "gW1 of prev tile (P3)"]
-# (the last one: the deferred-dW1 form on the f16 record, `exact x16` - inside P3, ahead of the loss on waves 0-3 and behind the
-# commit on waves 4-7; the "gW1" phase at the tile's end then reads about 0)
+            "barrier B2", "gW3+dz2+image", "gW2", "barrier C", "dh1+dz1 image", "gW1", "loop top", "gW1 of prev tile (P3)",
+            "gathers ahead (P3)", "row loads ahead (<C)"]
+# ("gW1 of prev tile": the deferred-dW1 form on the f16 record, `exact x16` - inside P3, ahead of the loss on waves 0-3 and behind
+# the commit on waves 4-7; the "gW1" phase at the tile's end then reads about 0.  The last two: the gathers-ahead form of that
+# loop - the staging waves' x gathers, index load and cursor update behind the commit, the loss waves' row loads, index load and
+# cursor update behind gW2; "gather issue" then reads about 0.  Their sums sit behind the 8 x 16 words of the other phases.)
 l = lib()
 ctx = Ctx("f16x2" if MODE == 1 else "f32")
 if "w4" in sys.argv[2:]:
     ctx.set(ctx.TRAIN_VARIANT, 1)
 l.mava_debug_set_stamps.argtypes = [C.c_void_p]
-stamps = torch.zeros(128, dtype=torch.int64, device=dev)  # waves 0-3 (chain / only group), 4-7 (loader group of wide launches)
+stamps = torch.zeros(144, dtype=torch.int64, device=dev)  # waves 0-3 (chain / only group), 4-7 (loader group of wide launches)
 l.mava_debug_set_stamps(stamps.data_ptr())
 perm = torch.randperm(TE, device=dev).to(torch.int32)
 for which in ("critic", "actor"):
@@ -72,11 +75,12 @@ for which in ("critic", "actor"):
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); run(); b.record(); torch.cuda.synchronize()
-    s8 = stamps.cpu().numpy().reshape(8, 16)
+    s8 = stamps.cpu().numpy()[:128].reshape(8, 16)
     if which == "critic" and MODE == 1:
         print(f"   (exact-loop tiles of the three launches: {ctx.get(ctx.EXACT_TILES)} of {3 * -(-Rb // 32)}; "
               f"launches on the f16 copy: {ctx.get(ctx.X16_LAUNCHES)})")
     if ctx.get(ctx.W8_LAUNCHES) > w8_before:  # eight equal waves: print waves 0-3 and wave 4 (the SIMD partner of wave 0)
+        s8 = np.concatenate([s8, stamps.cpu().numpy()[128:].reshape(8, 2)], axis=1)  # (the eight-wave kernel's two extra phases)
         tot = s8.sum(1)
         ntile = -(-(Rb * A) // 32 // 256)
         print(f"   (eight-wave launches on the f16 record so far: {ctx.get(ctx.X16_W8_LAUNCHES)})")
