@@ -131,7 +131,8 @@ int mava_ppo_finish_f32(mava_ctx* ctx, const float* slab_a, long stride_a, const
                         float b2, float eps, float vf_coef, float ent_coef, float* metrics_out, int critic_din,
                         void* workspace, size_t workspace_bytes, mava_stream_t s);
 
-/* out[i] = (accumulate ? out[i] : 0) + sum_b slab[b*slab_stride + i], b ascending. */
+/* out[i] = (accumulate ? out[i] : 0) + sum_b slab[b*slab_stride + i], b ascending.  n_slab == 0: the sum is zero and
+ * slab is not read (it may be NULL); the same holds for mava_slab_reduce2_f32. */
 int mava_slab_reduce_f32(const float* slab, int n_slab, long slab_stride, int n, int accumulate,
                          float* out, mava_stream_t s);
 

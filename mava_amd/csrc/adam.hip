@@ -462,7 +462,8 @@ extern "C" int mava_slab_reduce2_f32(const float* slab, int n_slab, long slab_st
   MAVA_ARG_CHECK(n_main >= 0 && n_tail >= 0 && n_slab >= 0 && slab_stride >= n_main + n_tail, 0,
                  "mava_slab_reduce2_f32: bad shape");
   if (n_main + n_tail == 0) return MAVA_OK;
-  MAVA_ARG_CHECK(slab && (n_main == 0 || out_main) && (n_tail == 0 || out_tail), 1,
+  // (no slab: nothing is read - the sum is zero - so an empty slab array may come without a pointer)
+  MAVA_ARG_CHECK((slab || n_slab == 0) && (n_main == 0 || out_main) && (n_tail == 0 || out_tail), 1,
                  "mava_slab_reduce2_f32: null pointer argument");
   hipLaunchKernelGGL(slab_reduce2_kernel, dim3(mava_cdiv(n_main + n_tail, 64)), dim3(256), 0, s, slab,
                      n_slab, slab_stride, n_main, n_tail, accumulate, out_main, out_tail);
@@ -476,7 +477,7 @@ extern "C" int mava_slab_reduce_f32(const float* slab, int n_slab, long slab_str
                  "mava_slab_reduce_f32: bad shape n=%d n_slab=%d stride=%ld", n, n_slab,
                  slab_stride);
   if (n == 0) return MAVA_OK;
-  MAVA_ARG_CHECK(slab && out, 1, "mava_slab_reduce_f32: null pointer argument");
+  MAVA_ARG_CHECK((slab || n_slab == 0) && out, 1, "mava_slab_reduce_f32: null pointer argument");
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(mava_cdiv(n, 64)), dim3(256), 0, s, slab, n_slab,
                      slab_stride, n, accumulate, out);
   MAVA_LAUNCH_CHECK();

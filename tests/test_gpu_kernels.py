@@ -466,10 +466,11 @@ def test_train_kernels_full_launch_shape(dev, matmul_mode):
     assert_close(gc[Pc : Pc + 1], np.array([acc_c[1]]), 1e-5, "value loss", scale=1.0)
 
 
-@pytest.mark.parametrize("variant", [1, 11, 21, 22, 23, 24, 41, 42, 43, 44, 45, 46, 47])
-@pytest.mark.parametrize("T,N,rec", [(128, 16384, False), (37, 136, True), (300, 264, False)])
+@pytest.mark.parametrize("variant", [1, 11, 12, 13, 14, 15, 16, 21, 22, 23, 24, 41, 42, 43, 44, 45, 46, 47])
+@pytest.mark.parametrize("T,N,rec", [(128, 16384, False), (37, 136, True), (300, 264, False), (17, 66, True), (256, 132, True)])
 def test_gae_variants(dev, variant, T, N, rec):
-    """Every chunk/lane mapping of the GAE kernel gives the same scan (incl. ragged T and multi-slab T)."""
+    """Every chunk/lane mapping of the GAE kernel gives the same scan (incl. ragged T and multi-slab T; recurrent masking
+    one row past a chunk, and across slabs on the fast path)."""
     from mava_amd import ops
     from mava_amd._lib import Ctx
 

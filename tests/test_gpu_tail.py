@@ -26,9 +26,11 @@ def _pcount(din, n_out):  # Dense(din,128)-Dense(128,128)-Dense(128,n_out), weig
 
 
 @functools.lru_cache(maxsize=None)
-def _slabs(din_c, n_slab, scale):
-    """Random slabs [gradient | loss sums] of both networks (read-only: shared between tests)."""
-    Pa, Pc = _pcount(DIN_A, N_ACT), _pcount(din_c, 1)
+def _slabs(din_c, n_slab, scale, Pa=None, Pc=None):
+    """Random slabs [gradient | loss sums] of both networks (read-only: shared between tests).  Pa / Pc: the networks'
+    sizes, by default those of the MLPs on DIN_A and din_c inputs (the fused finish takes any)."""
+    Pa = _pcount(DIN_A, N_ACT) if Pa is None else Pa
+    Pc = _pcount(din_c, 1) if Pc is None else Pc
     rng = np.random.default_rng(1000 * din_c + n_slab)
     a = (rng.standard_normal((n_slab, Pa + 2)) * scale / n_slab).astype(np.float32)
     c = (rng.standard_normal((n_slab, Pc + 1)) * scale / n_slab).astype(np.float32)
@@ -49,10 +51,10 @@ def _column_sums(slab):
 
 
 @functools.lru_cache(maxsize=None)
-def _reduced(din_c, n_slab, scale, grad_scale):
+def _reduced(din_c, n_slab, scale, grad_scale, Pa=None, Pc=None):
     """g = [actor grad | critic grad | actor_loss, entropy, value_loss] and the (n_partial, 2) f64 norm partials: per network
     the squares of f32(sum * grad_scale) over 64 consecutive virtual columns of [actor Pa + 2 | critic Pc + 1], ascending."""
-    a, c = _slabs(din_c, n_slab, scale)
+    a, c = _slabs(din_c, n_slab, scale, Pa, Pc)
     Pa, Pc = a.shape[1] - 2, c.shape[1] - 1
     sa, sc = _column_sums(a), _column_sums(c)
     g = np.concatenate([sa[:Pa], sc[:Pc], sa[Pa:], sc[Pc:]]).astype(np.float32)
