@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from ._lib import launch, lib, ptr, stream_ptr
-from .learner import NUM_CU
+from .ppo_learner import NUM_CU
 from .learner_common import bind_learn
 from .networks import MLPTorso
 from .replay_learner import ReplayLearner

@@ -20,6 +20,11 @@ Data layout (per GPU; U = update_batch_size replicas share parameters, ff_mappo.
                                     it and rows are gathered inside the gradient kernels.
 One process drives one GPU; with world_size > 1 the env axis is sharded over ranks and the flat
 gradient is summed with one all-reduce per minibatch (ff_mappo.py:224-238 pmean "device").
+
+The replica buffers, the constructor's prologue, the flat parameter storage with init_params / adopt / the state trees,
+the slot-0 observation view, the clip+Adam hyper-parameter block, learn() and learner_setup() are PPOLearner's
+(mava_amd/ppo_learner.py); the networks, the fused / per-step / graph-captured rollout, the batched permutations and
+advantage statistics, the gradient launches and the fused update tail are this module's.
 """
 from __future__ import annotations
 
@@ -30,97 +35,18 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops, parallel
-from .guards import check_f16_range
-from .learner_common import bind_learn, matmul_ctx
-from .networks import FeedForwardActor, FeedForwardValueNet, MLPTorso, make_action_head
-from .types import (AdamState, ExperimentOutput, LearnerState, Observation, ObservationGlobalState, OptStates, Params,
-                    TimeStep)
-
-NUM_CU = 256  # MI355X compute units: one persistent gradient block per CU
+from . import ops, parallel, ppo_learner
+from .networks import FeedForwardActor, FeedForwardValueNet, MLPTorso
+from .ppo_learner import PPOLearner
+from .types import LearnerState, TimeStep
 
 
-def _dist_info() -> Tuple[int, int]:
-    return parallel.rank_world()
-
-
-class _Replica:
-    """Trajectory + env buffers of one update-batch replica (the vmapped axis of ff_mappo.py:319)."""
-
-    def __init__(self, env, T: int, n_upd: int, critic_uses_state: bool, device, continuous: bool = False):
-        E, A = env.num_envs, env.num_agents
-        self.env = env
-        self.state = env.alloc_state()
-        d = device
-        self.agents_view = torch.empty((T + 1, E, A, env.obs_dim), device=d)
-        self.global_state = torch.empty((T + 1, E, env.gs_tiles, env.state_dim), device=d)
-        self.action_mask = torch.empty((T + 1, E, A, env.action_dim), dtype=torch.uint8, device=d)
-        self.step_count = torch.empty((T + 1, E, A), dtype=torch.int32, device=d)
-        # discrete: action index per agent; continuous head: action vector in (-1, 1) per agent
-        self.action = (torch.empty((T, E, A, env.action_dim), device=d) if continuous
-                       else torch.empty((T, E, A), dtype=torch.int32, device=d))
-        self.value = torch.empty((T, E, A), device=d)
-        self.reward = torch.empty((T, E, A), device=d)
-        self.log_prob = torch.empty((T, E, A), device=d)
-        self.done = torch.empty((T, E, A), dtype=torch.uint8, device=d)
-        self.last_val = torch.empty((E, A), device=d)
-        self.adv = torch.empty((T, E, A), device=d)
-        self.tgt = torch.empty((T, E, A), device=d)
-        # episode metrics of every update of one learn() call: (N_upd, T, E)
-        self.info_return = torch.zeros((n_upd, T, E), device=d)
-        self.info_length = torch.zeros((n_upd, T, E), dtype=torch.int32, device=d)
-        self.info_terminal = torch.zeros((n_upd, T, E), dtype=torch.uint8, device=d)
-        # the rollout writes the metrics of the CURRENT update here (fixed addresses: one captured HIP graph serves
-        # every update index n); FFLearner._rollout copies them to slot n afterwards
-        self.cur_return = torch.zeros((T, E), device=d)
-        self.cur_length = torch.zeros((T, E), dtype=torch.int32, device=d)
-        self.cur_terminal = torch.zeros((T, E), dtype=torch.uint8, device=d)
-        self.last_reward = torch.zeros((E, A), device=d)
-        self.last_done = torch.zeros((E, A), dtype=torch.uint8, device=d)
-
-    def obs_slot(self, t: int) -> Dict[str, torch.Tensor]:
-        return {"agents_view": self.agents_view[t], "global_state": self.global_state[t],
-                "action_mask": self.action_mask[t], "step_count": self.step_count[t]}
-
-
-class FFLearner:
+class FFLearner(PPOLearner):
     def __init__(self, env, config, centralised_critic: bool, device: Optional[torch.device] = None):
-        self.config = config
-        self.centralised = centralised_critic
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.rank, self.world = _dist_info()
-        s, arch = config.system, config.arch
-        self.E, self.U, self.T = int(arch.num_envs), int(s.update_batch_size), int(s.rollout_length)
-        self.K, self.M = int(s.ppo_epochs), int(s.num_minibatches)
-        if (self.T * self.E) % self.M:
-            raise ValueError("rollout_length * num_envs must be divisible by num_minibatches (ff_mappo.py:277-279)")
-        self.n_upd = int(s.get("num_updates_per_eval", 1))
-        # one env object per replica; global env ids are disjoint over (rank, replica)
-        self.reps: List[_Replica] = []
-        if env.num_envs != self.E:
-            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
-        if centralised_critic and not getattr(env, "add_global_state", False):
-            raise ValueError("Global state must be provided to the centralised critic.")  # networks.py:196-197
-        # ff_mappo.py:348-350: the action head of the configuration, sized by the env's action dimension
-        action_head = make_action_head(config.network.get("action_head", None), env.action_dim)
-        self.continuous = type(action_head).__name__ == "ContinuousActionHead"
-        self.min_scale = float(getattr(action_head, "min_scale", 1e-3))
-        # a discrete env reads the action index; of the continuous ones only an env with `continuous_actions` reads the
-        # f32 action vector (the synthetic stand-in ignores it)
-        self._env_reads_action = not self.continuous or getattr(env, "continuous_actions", False)
-        for u in range(self.U):
-            rep_env = env.clone(env_offset=getattr(env, "env_offset", 0) + (self.rank * self.U + u) * self.E)
-            self.reps.append(_Replica(rep_env, self.T, self.n_upd, centralised_critic, self.device, self.continuous))
-        env0 = self.reps[0].env
-        self.A, self.nA = env0.num_agents, env0.action_dim
-        config.system.num_agents = self.A  # ff_mappo.py:341
-        self.Oa = env0.obs_dim
-        if centralised_critic:
-            self.Oc = env0.state_dim
-            self.critic_share = self.A if env0.global_state_shared else 1
-        else:
-            self.Oc = self.Oa
-            self.critic_share = 1
+        # (critic aggregation is a setting of the learner's context handle, like the arithmetic mode: mava_ctx_*)
+        super().__init__(env, config, centralised_critic, device,
+                         ctx_kwargs={"critic_aggregation": os.environ.get("MAVA_CRITIC_AGGREGATION", "1") != "0"})
+        s, env0, action_head = config.system, self.reps[0].env, self.action_head
 
         # networks (ff_mappo.py:347-354) - hydra.utils.instantiate is replaced by direct construction
         net = config.network
@@ -146,36 +72,18 @@ class FFLearner:
             self.actor_network = FeedForwardActor(a_torso, action_head, self.Oa)
             self.critic_network = FeedForwardValueNet(c_torso, centralised_critic, self.Oc)
         self.Pa, self.Pc = self.actor_network.num_params, self.critic_network.num_params
-        self.P = self.Pa + self.Pc
+        self._alloc_params([(self.actor_network, s.actor_lr), (self.critic_network, s.critic_lr)])
 
         d = self.device
-        self.p = torch.zeros(self.P, device=d)
-        self.m = torch.zeros(self.P, device=d)
-        self.v = torch.zeros(self.P, device=d)
-        self.count = torch.zeros(2, dtype=torch.int32, device=d)
-        self.g = torch.zeros(self.P + 4, device=d)  # [actor grad | critic grad | actor_loss, entropy, value_loss, pad]
-        self.seg_off = [0, self.Pa, self.P]
-        self.seg_lr = [float(s.actor_lr), float(s.critic_lr)]
-
         self.Rb = self.T * self.E // self.M  # env rows per minibatch
-        ntiles = (self.Rb * self.A + 31) // 32
-        # The gradient kernels are persistent blocks that own a CU each (all of its registers and LDS): with several ranks
-        # a few CUs stay free of them, so that RCCL's all-reduce kernel of the actor's slice can really run WHILE the
-        # critic's gradient kernel does (parallel.allreduce_sum_async below); system.rccl_cus / MAVA_RCCL_CUS, default 8
-        # with a process group (a ~0.3 MB message uses a handful of channels), 0 on a single rank.
-        self.rccl_cus = int(s.get("rccl_cus", None) if s.get("rccl_cus", None) is not None
-                            else os.environ.get("MAVA_RCCL_CUS", "8" if self.world > 1 else "0"))
-        self.n_slab = max(1, min(NUM_CU - max(0, min(self.rccl_cus, NUM_CU - 1)), ntiles))
+        # (with several ranks the actor's slice is all-reduced WHILE the critic's gradient kernel runs,
+        # parallel.allreduce_sum_async below: PPOLearner._slab_count leaves RCCL its CUs)
+        self.n_slab = self._slab_count((self.Rb * self.A + 31) // 32)
         self.slab_a = torch.zeros((self.n_slab, self.Pa + 2), device=d)
         self.slab_c = torch.zeros((self.n_slab, self.Pc + 2), device=d)
-        self.stats = torch.zeros((ops.lib().mava_adv_stats_blocks(), 2), dtype=torch.float64, device=d)
-        self.train_metrics = torch.zeros((self.n_upd, self.K, self.M, 4), device=d)
-        self.perm_count = 0  # epoch permutations drawn so far (counter of mava_permutation_i32)
-        self.t_global = 0  # env steps taken per env so far (Philox step counter)
-        self.ent_step = 0  # minibatches trained so far: counter of the continuous head's entropy sample
         # the same counter on the device: the kernels add it to their relative step, so a rollout captured in a HIP
         # graph replays with the next counters
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=d)
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=d)  # (t_global)
         # Single-rank jobs only: with a process group the replay measured SLOWER (RCCL, one rank, forced exchange:
         # 22.5 vs 22.1 ms per update; two gloo ranks on one card: 100x slower), see tools/graph_pg_rehearsal.py.
         # MAVA_GRAPH_ROLLOUT=0 turns it off, =force keeps it on with several ranks.
@@ -183,15 +91,8 @@ class FFLearner:
         self.graph_rollout = (mode == "force" or (mode != "0" and self.world == 1)) and not self.generic
         self._graphs: Dict[int, Any] = {}  # keyed by the seed: ONE graph for every update index n
         self._graph_seen: set = set()
-        self.seed = int(s.seed)
-        self.timers: Optional[Dict[str, list]] = None  # bench.py: name -> [(start_event, end_event)]
-        # Arithmetic of the matrix products (not a Mava key): "f16x2" (default) = every operand split into two f16
-        # terms, three f16 MFMAs per product with f32 accumulation (ppo_train_h2.hip, rollout_h2.hip: ~22 mantissa bits
-        # per operand, the 1e-4 gradient parity tests run on it) for the shapes those kernels instantiate; "f32" = the
-        # exact-f32 MFMA kernels everywhere (learner_common.matmul_ctx).
-        # the library keeps no process-wide settings: arithmetic mode, critic aggregation and the kernels' own workspaces
-        # belong to this learner's context handle (include/mava_hip.h mava_ctx_*)
-        self.matmul_mode, self.ctx = matmul_ctx(s, critic_aggregation=os.environ.get("MAVA_CRITIC_AGGREGATION", "1") != "0")
+        # ("f16x2" here: three f16 MFMAs per product with f32 accumulation - ppo_train_h2.hip, rollout_h2.hip: ~22 mantissa
+        # bits per operand, the 1e-4 gradient parity tests run on it - for the shapes those kernels instantiate)
         # MAVA_TRAIN_VARIANT=1: the four-wave gradient kernels only (A/B measurements against the eight-wave actor kernel)
         self.ctx.set(self.ctx.TRAIN_VARIANT, int(os.environ.get("MAVA_TRAIN_VARIANT", "0")))
         for net_ in (self.actor_network, self.critic_network):
@@ -224,7 +125,6 @@ class FFLearner:
         for rep in self.reps:
             rep.view16 = torch.zeros((self.T + 1, self.E, self.A, rp), dtype=torch.float16, device=d) if self.view16 else None
             rep.view16_valid = torch.zeros((1,), dtype=torch.int32, device=d) if self.view16 else None
-        self._learn_calls = 0  # guards.check_f16_range: the previous call's metrics are checked from the second call on
         # One rank: nothing sits between the gradient kernels and Adam, so both slab sums, clip + Adam, the count increment and
         # the wide critic's W1 re-split run as TWO launches (ops.ppo_finish) instead of six.  With several replicas every
         # replica's gradient kernels write their own rows of the slab matrices and the one sum runs over all U * n_slab rows
@@ -239,6 +139,10 @@ class FFLearner:
             self.slab_a = torch.zeros((self.U * self.n_slab, self.Pa + 2), device=d)
             self.slab_c = torch.zeros((self.U * self.n_slab, self.Pc + 2), device=d)
 
+    def _refuse(self, env, config) -> None:
+        if (self.T * self.E) % self.M:
+            raise ValueError("rollout_length * num_envs must be divisible by num_minibatches (ff_mappo.py:277-279)")
+
     def _timed(self, name: str, fn, *args, **kwargs):
         """Run one kernel launch, optionally bracketed by HIP events on the launch stream."""
         if self.timers is None:
@@ -251,45 +155,13 @@ class FFLearner:
         return out
 
     # ------------------------------------------------------------------------------------ setup
-    def init_params(self, actor_seed: int, critic_seed: int) -> None:
-        self.p[: self.Pa].copy_(self.actor_network.init_flat(actor_seed))
-        self.p[self.Pa :].copy_(self.critic_network.init_flat(critic_seed))
-        self.m.zero_()
-        self.v.zero_()
-        self.count.zero_()
-
     def reset_envs(self) -> None:
-        for rep in self.reps:
-            rep.env.step_into(rep.state, 0, rep.obs_slot(0), is_reset=True)
-        self.t_global = 0
-        self.ent_step = 0
+        super().reset_envs()
         self.step_dev.zero_()
-        self.perm_count = 0
 
     # ---------------------------------------------------------------------------- state <-> views
-    def _params_tree(self) -> Params:
-        lead = (1, self.U)
-        return Params(self.actor_network.tree(self.p[: self.Pa], lead), self.critic_network.tree(self.p[self.Pa :], lead))
-
-    def _opt_tree(self) -> OptStates:
-        lead = (1, self.U)
-        out = []
-        for i, (net, sl) in enumerate(((self.actor_network, slice(0, self.Pa)), (self.critic_network, slice(self.Pa, self.P)))):
-            out.append(AdamState(self.count[i].expand(1, self.U), net.tree(self.m[sl], lead), net.tree(self.v[sl], lead)))
-        return OptStates(*out)
-
     def _timestep(self, slot: int) -> TimeStep:
-        def stack(f):
-            return torch.stack([f(r) for r in self.reps], 0).unsqueeze(0)  # (1, U, E, ...)
-
-        av = stack(lambda r: r.agents_view[slot])
-        mask = stack(lambda r: r.action_mask[slot]).bool()
-        sc = stack(lambda r: r.step_count[slot])
-        if self.centralised:
-            gs = stack(lambda r: r.global_state[slot].expand(-1, self.A, -1) if r.env.gs_tiles == 1 else r.global_state[slot])
-            obs: Any = ObservationGlobalState(av, mask, gs, sc)
-        else:
-            obs = Observation(av, mask, sc)
+        stack, obs = self._stack, self._observation(slot)
         done = stack(lambda r: r.last_done[:, 0]).bool()
         step_type = torch.where(done, 2, 1).to(torch.int8)
         reward = stack(lambda r: r.last_reward)
@@ -301,30 +173,15 @@ class FFLearner:
         return TimeStep(step_type, reward, 1.0 - stack(lambda r: r.last_done).float(), obs, extras)
 
     def learner_state(self) -> LearnerState:
-        key = torch.tensor([[[self.seed, self.t_global]] * self.U], dtype=torch.int64)  # (1, U, 2) host tensor
-        env_state = {
-            "step_count": torch.stack([r.state.step_count for r in self.reps], 0).unsqueeze(0),
-            "running_count_episode_return": torch.stack([r.state.run_return for r in self.reps], 0).unsqueeze(0),
-            "running_count_episode_length": torch.stack([r.state.run_length for r in self.reps], 0).unsqueeze(0),
-            "episode_return": torch.stack([r.state.ep_return for r in self.reps], 0).unsqueeze(0),
-            "episode_length": torch.stack([r.state.ep_length for r in self.reps], 0).unsqueeze(0),
-        }
-        return LearnerState(self._params_tree(), self._opt_tree(), key, env_state, self._timestep(0))
+        env_state = self._env_state()
+        env_state["running_count_episode_return"] = self._stack(lambda r: r.state.run_return)
+        env_state["running_count_episode_length"] = self._stack(lambda r: r.state.run_length)
+        return LearnerState(self._params_tree(), self._opt_tree(), self._key(), env_state, self._timestep(0))
 
-    def adopt(self, state: LearnerState) -> None:
-        """Make the device buffers equal to `state` (no-op for leaves that already alias them), so that
-        learn() is a function of its argument like the reference's pure learner_fn."""
-        pa = self.actor_network.first_leaf(state.params.actor_params)
-        if pa.data_ptr() != self.p.data_ptr():
-            self.actor_network.flat_from_tree(state.params.actor_params, self.p[: self.Pa])
-            self.critic_network.flat_from_tree(state.params.critic_params, self.p[self.Pa :])
-            for i, (net, sl, st) in enumerate(((self.actor_network, slice(0, self.Pa), state.opt_states.actor_opt_state),
-                                               (self.critic_network, slice(self.Pa, self.P), state.opt_states.critic_opt_state))):
-                net.flat_from_tree(st.mu, self.m[sl])
-                net.flat_from_tree(st.nu, self.v[sl])
-                self.count[i] = int(st.count.reshape(-1)[0])
-            # the same buffer with other contents: the W1 copy the last finish launch left in the handle is stale
-            self.ctx.set(self.ctx.W1_SPLIT_FRESH, 0)
+    def _adopted(self) -> None:
+        # the same buffer with other contents: the W1 copy the last finish launch left in the handle is stale (the wide
+        # critic kernels and their W1 cache are this learner's alone)
+        self.ctx.set(self.ctx.W1_SPLIT_FRESH, 0)
 
     # ------------------------------------------------------------------------------------ update
     def _rollout(self, n: int) -> None:
@@ -513,31 +370,21 @@ class FFLearner:
             if not self.fused_tail:
                 ops.slab_reduce2(self.slab_c, self.Pc, self.g[self.Pa : self.P], 1, self.g[self.P + 2 : self.P + 3], accumulate=u > 0)
         if self.fused_tail:
-            self._timed("finish", ops.ppo_finish, self.ctx, self.slab_a, self.slab_c, self.Pa, self.Pc, self.g, self.p, self.m, self.v,
-                        self.count, self.seg_lr[0], self.seg_lr[1], grad_scale=1.0 / self.U, max_norm=float(s.max_grad_norm),
-                        decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                        num_updates=int(s.get("num_updates", 1) or 1), vf_coef=float(s.vf_coef), ent_coef=float(s.ent_coef),
-                        metrics_out=self.train_metrics[n, k, mb], critic_din=self.Oc, workspace=self._finish_ws)
-            self.ent_step += 1
+            self._ppo_finish("finish", n, k, mb, self.slab_a, self.slab_c, self._finish_ws)
             return
         w_rest = parallel.allreduce_sum_async(self.g[self.Pa :])  # critic gradient + the loss scalars
         for wk in (w_actor, w_rest):
             if wk is not None:
                 wk.wait()
         if self._finish_ws_mr is not None:  # several ranks: Adam + count increment + W1 re-split as one launch on the all-reduced g
-            self._timed("clip_adam", ops.ppo_finish, self.ctx, None, None, self.Pa, self.Pc, self.g, self.p, self.m, self.v, self.count,
-                        self.seg_lr[0], self.seg_lr[1], grad_scale=1.0 / (self.U * self.world), max_norm=float(s.max_grad_norm),
-                        decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                        num_updates=int(s.get("num_updates", 1) or 1), vf_coef=float(s.vf_coef), ent_coef=float(s.ent_coef),
-                        metrics_out=self.train_metrics[n, k, mb], critic_din=self.Oc, workspace=self._finish_ws_mr)
-            self.ent_step += 1
-            return
-        self._timed("clip_adam", ops.clip_adam, self.p, self.g, self.m, self.v, self.count, self.seg_off, self.seg_lr,
-                      grad_scale=1.0 / (self.U * self.world), max_norm=float(s.max_grad_norm),
-                      decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                      num_updates=int(s.get("num_updates", 1) or 1), loss_sums=self.g[self.P :], vf_coef=float(s.vf_coef),
-                      ent_coef=float(s.ent_coef), metrics_out=self.train_metrics[n, k, mb])
-        self.ent_step += 1
+            self._ppo_finish("clip_adam", n, k, mb, None, None, self._finish_ws_mr)
+        else:
+            self._timed("clip_adam", self._clip_adam, n, k, mb)
+
+    def _ppo_finish(self, name: str, n: int, k: int, mb: int, slab_a, slab_c, workspace) -> None:
+        """Slab sums (none when slab_a is None), clip + Adam, the count increment and the W1 re-split (ops.ppo_finish)."""
+        self._timed(name, ops.ppo_finish, self.ctx, slab_a, slab_c, self.Pa, self.Pc, self.g, self.p, self.m, self.v, self.count,
+                    self.seg_lr[0], self.seg_lr[1], critic_din=self.Oc, workspace=workspace, **self._adam_kwargs(n, k, mb))
 
     # ---------------------------------------------------------------- general network path (mava_amd/generic_networks.py)
     def _generic_setup(self) -> None:
@@ -622,12 +469,7 @@ class FFLearner:
         for wk in (w_actor, w_rest):
             if wk is not None:
                 wk.wait()
-        ops.clip_adam(self.p, self.g, self.m, self.v, self.count, self.seg_off, self.seg_lr,
-                      grad_scale=1.0 / (self.U * self.world), max_norm=float(s.max_grad_norm),
-                      decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                      num_updates=int(s.get("num_updates", 1) or 1), loss_sums=self.g[self.P :], vf_coef=float(s.vf_coef),
-                      ent_coef=float(s.ent_coef), metrics_out=self.train_metrics[n, k, mb])
-        self.ent_step += 1
+        self._clip_adam(n, k, mb)
 
     def _permutations(self) -> List[torch.Tensor]:
         """ff_mappo.py:272-273: one permutation of the T*E rows per epoch, identical on every replica and rank (the
@@ -660,44 +502,18 @@ class FFLearner:
                 ops.adv_stats_batched(rep.adv.view(-1), self._perm_all.view(-1), self.Rb, self.A, self.K * self.M,
                                       out=self._stats_all[u])
         for k in range(self.K):
-            perm = permutations[k]
-            for mb in range(self.M):
-                self._minibatch(n, k, mb, perm)
-        # the bootstrap observation becomes the first observation of the next rollout
-        for rep in self.reps:
-            ops.rollout_carry(rep.agents_view, rep.global_state, rep.action_mask, rep.step_count)
+            self._epoch(n, k, permutations[k])
+        self._carry_observation()
 
-    def learn(self, learner_state: LearnerState) -> ExperimentOutput:
-        """LearnerFn (mava/types.py:154): num_updates_per_eval updates, asynchronous on the current
-        stream - the caller synchronises before reading the clock (ff_mappo.py:497-498)."""
-        self.adopt(learner_state)
-        if self.matmul_mode == "f16x2":
-            obs = [t for r in self.reps for t in (r.agents_view[0], r.global_state[0] if self.centralised else None)]
-            check_f16_range(self.p, obs, self.train_metrics if self._learn_calls else None, type(self).__name__)
-        self._learn_calls += 1
-        for n in range(self.n_upd):
-            self.update(n)
-        U = self.U
-        episode_metrics = {
-            "episode_return": torch.stack([r.info_return for r in self.reps], 1).unsqueeze(0),  # (1,N,U,T,E)
-            "episode_length": torch.stack([r.info_length for r in self.reps], 1).unsqueeze(0),
-            "is_terminal_step": torch.stack([r.info_terminal for r in self.reps], 1).unsqueeze(0).bool(),
-        }
-        tm = self.train_metrics.unsqueeze(1).expand(self.n_upd, U, self.K, self.M, 4).unsqueeze(0)  # (1,N,U,K,M,4)
-        train_metrics = {"total_loss": tm[..., 0], "value_loss": tm[..., 1], "actor_loss": tm[..., 2], "entropy": tm[..., 3]}
-        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
+    def _carry_observation(self) -> None:
+        for rep in self.reps:  # (one launch per replica)
+            ops.rollout_carry(rep.agents_view, rep.global_state, rep.action_mask, rep.step_count)
 
 
 def learner_setup(env, keys, config, centralised_critic: bool, device=None):
     """Counterpart of learner_setup (ff_mappo.py:333-432): returns (learn, actor_network,
     init_learner_state).  `keys` = (key, actor_net_key, critic_net_key) integer seeds."""
-    key, actor_key, critic_key = (int(k) for k in keys)
-    learner = FFLearner(env, config, centralised_critic, device)
-    learner.seed = key
-    learner.init_params(actor_key, critic_key)
-    parallel.broadcast_(learner.p, src=0)
-    learner.reset_envs()
-    return bind_learn(learner), learner.actor_network, learner.learner_state()
+    return ppo_learner.learner_setup(FFLearner, env, keys, config, centralised_critic, device=device)
 
 
 def get_final_step_metrics(metrics: Dict[str, torch.Tensor]) -> Tuple[Dict[str, torch.Tensor], bool]:

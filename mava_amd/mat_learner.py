@@ -18,6 +18,10 @@ writes the gradient of an input that has none yet and adds to one that has (the 
 residual input of a LayerNorm shares the gradient buffer of the branch it was added to.
 
 Parameters: one flat vector [encoder | decoder], one global-norm clip and one Adam (ops.clip_adam, one segment).
+
+MATLearner is the one-replica, one-segment case of PPOLearner (mava_amd/ppo_learner.py), which owns the replica buffers,
+the constructor's prologue, the flat parameter storage with init_params / adopt, update(), the clip+Adam launch, learn() and
+learner_setup(); the refusals, the network, the tapes and every launch of the rollout and of a minibatch are this module's.
 """
 from __future__ import annotations
 
@@ -26,15 +30,13 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops, parallel
+from . import ops, ppo_learner
 from ._lib import MavaHipError, launch, lib, ptr, stream_ptr
 from .generic_networks import GenericMLPTorso, GenericNet
-from .guards import check_f16_range
-from .learner import _Replica
-from .learner_common import bind_learn, episode_metrics, matmul_ctx, pad32
+from .learner_common import pad32
 from .networks import _orthogonal_
-from .types import AdamState, ExperimentOutput, LearnerState, Observation, TimeStep
-from .utils.tree import tree_to
+from .ppo_learner import PPOLearner
+from .types import LearnerState, TimeStep
 
 MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
 
@@ -411,43 +413,20 @@ class MATActor:
         return action
 
 
-class MATLearner:
+class MATLearner(PPOLearner):
     def __init__(self, env, config, device: Optional[torch.device] = None):
-        self.config = config
-        s, arch, net = config.system, config.arch, config.network
-        self.rank, self.world = parallel.rank_world()
-        head = net.get("action_head", None) or {}
+        net = config.network
         self.D, self.H, self.n_block = int(net.get("n_embd", 64)), int(net.get("n_head", 1)), int(net.get("n_block", 1))
-        check_supported(num_agents=int(env.num_agents), n_actions=int(env.action_dim), n_embd=self.D, n_head=self.H,
-                        continuous="ContinuousActionHead" in str(dict(head).get("_target_", "")), world=self.world,
-                        update_batch_size=int(s.update_batch_size))
-        if self.n_block < 1:
-            raise ValueError(f"network.n_block must be >= 1, got {self.n_block}")
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.E, self.U, self.T = int(arch.num_envs), 1, int(s.rollout_length)
-        self.K, self.M = int(s.ppo_epochs), int(s.num_minibatches)
-        if (self.T * self.E) % self.M:
-            raise ValueError("rollout_length * num_envs must be divisible by num_minibatches")
-        if env.num_envs != self.E:
-            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
-        self.n_upd = int(s.get("num_updates_per_eval", 1))
-        self.matmul_mode, self.ctx = matmul_ctx(s)
-        rep_env = env.clone(env_offset=getattr(env, "env_offset", 0))
-        self.rep = _Replica(rep_env, self.T, self.n_upd, False, self.device, False)
-        self.reps = [self.rep]
-        self.A, self.nA, self.O = rep_env.num_agents, rep_env.action_dim, rep_env.obs_dim  # (image observations: their flat row)
+        super().__init__(env, config, False, device)
+        s, self.rep = config.system, self.reps[0]
+        self.O = self.Oa  # (image observations: their flat row)
         if self.O > 1024:
             raise MavaHipError(f"ff_mat: observations of up to 1024 features (mava_rec_gather_t32_f32), got {self.O}")
-        config.system.num_agents = self.A
         self.net = MATNet(self.O, self.nA, self.A, self.D, self.H, self.n_block)
-        self.P = self.net.num_params
-        d = self.device
-        self.p, self.m, self.v = (torch.zeros(self.P, device=d) for _ in range(3))
-        self.g = torch.zeros(self.P + 4, device=d)  # [gradient | actor_loss, entropy, value_loss, pad]
-        self.count = torch.zeros(2, dtype=torch.int32, device=d)
         # actor_lr is the single learning rate of the one Adam; critic_lr is accepted and unused (encoder and decoder
         # share one optimiser, as upstream MAT does)
-        self.lr = float(s.actor_lr)
+        self._alloc_params([(self.net, s.actor_lr)])
+        d = self.device
         self.Bm = self.T * self.E // self.M  # (t, env) samples per minibatch
         self.actor_network = MATActor(self.net, self.ctx, d)
         self.roll = self.actor_network.pass_for(self.E)
@@ -458,48 +437,33 @@ class MATLearner:
         self.dvalues = torch.zeros(rows, device=d)
         self.loss_blocks = max(1, min(256, -(-rows // 256)))
         self.partials = torch.zeros((self.loss_blocks, 3), device=d)
-        self.stats = torch.zeros((lib().mava_adv_stats_blocks(), 2), dtype=torch.float64, device=d)
-        self.train_metrics = torch.zeros((self.n_upd, self.K, self.M, 4), device=d)
-        self.perm_count = 0
-        self.t_global = 0
-        self.seed = int(s.seed)
-        self._learn_calls = 0
         self.debug: Optional[Dict[str, list]] = None  # tests: {"grads": [], "perms": [], "state": []} records every minibatch (and "slot0")
 
-    # ------------------------------------------------------------------------------------ setup
-    def init_params(self, seed: int) -> None:
-        self.p.copy_(self.net.init_flat(seed))
-        self.m.zero_()
-        self.v.zero_()
-        self.count.zero_()
-
-    def reset_envs(self) -> None:
-        rep = self.rep
-        rep.env.step_into(rep.state, 0, rep.obs_slot(0), is_reset=True)
-        self.t_global = 0
-        self.perm_count = 0
+    def _refuse(self, env, config) -> None:
+        head = config.network.get("action_head", None) or {}
+        check_supported(num_agents=int(env.num_agents), n_actions=int(env.action_dim), n_embd=self.D, n_head=self.H,
+                        continuous="ContinuousActionHead" in str(dict(head).get("_target_", "")), world=self.world,
+                        update_batch_size=self.U)
+        if self.n_block < 1:
+            raise ValueError(f"network.n_block must be >= 1, got {self.n_block}")
+        if (self.T * self.E) % self.M:
+            raise ValueError("rollout_length * num_envs must be divisible by num_minibatches")
 
     # ---------------------------------------------------------------------------- state views
-    def learner_state(self) -> LearnerState:
-        lead, rep = (1, 1), self.rep
-        opt = AdamState(self.count[0].expand(1, 1), self.net.tree(self.m, lead), self.net.tree(self.v, lead))
-        key = torch.tensor([[[self.seed, self.t_global]]], dtype=torch.int64)
-        st = lambda t: t.unsqueeze(0).unsqueeze(0)
-        obs = Observation(st(rep.agents_view[0]), st(rep.action_mask[0]).bool(), st(rep.step_count[0]))
-        done = st(rep.last_done)
-        ts = TimeStep(torch.where(done[..., 0].bool(), 2, 1).to(torch.int8), st(rep.last_reward), 1.0 - done.float(), obs, {})
-        env_state = {"step_count": st(rep.state.step_count), "episode_return": st(rep.state.ep_return),
-                     "episode_length": st(rep.state.ep_length)}
-        return LearnerState(self.net.tree(self.p, lead), opt, key, env_state, ts)
+    def _params_tree(self) -> MATParams:
+        return self._trees(self.p)[0]
 
-    def adopt(self, state: LearnerState) -> None:
-        leaf = self.net.first_leaf(state.params)
-        if not isinstance(leaf, torch.Tensor) or leaf.data_ptr() != self.p.data_ptr():
-            to = lambda tree: tree_to(tree, self.p.device)
-            self.net.flat_from_tree(to(state.params), self.p)
-            self.net.flat_from_tree(to(state.opt_states.mu), self.m)
-            self.net.flat_from_tree(to(state.opt_states.nu), self.v)
-            self.count[0] = int(torch.as_tensor(state.opt_states.count).reshape(-1)[0])
+    def _opt_tree(self):
+        return self._adam_states()[0]
+
+    def _state_segments(self, state: LearnerState):
+        return [(state.params, state.opt_states)]
+
+    def learner_state(self) -> LearnerState:
+        done = self._stack(lambda r: r.last_done)
+        ts = TimeStep(torch.where(done[..., 0].bool(), 2, 1).to(torch.int8), self._stack(lambda r: r.last_reward), 1.0 - done.float(),
+                      self._observation(), {})
+        return LearnerState(self._params_tree(), self._opt_tree(), self._key(), self._env_state(), ts)
 
     # ------------------------------------------------------------------------------------ update
     def _rollout(self, n: int) -> None:
@@ -525,6 +489,8 @@ class MATLearner:
     def _minibatch(self, n: int, k: int, mb: int, perm: torch.Tensor) -> None:
         s, rep, tr, T, Bm = self.config.system, self.rep, self.train, self.T, self.Bm
         if self.debug is not None:
+            if mb == 0:
+                self.debug["perms"].append(perm.clone())
             self.debug["state"].append((self.p.clone(), self.m.clone(), self.v.clone()))
         tr.idx[:Bm].copy_(perm[mb * Bm : (mb + 1) * Bm])
         tr.gather_obs(rep.agents_view[:T], T * self.E)
@@ -540,46 +506,14 @@ class MATLearner:
         tr.backward(self.p, self.g, self.dlogits, self.dvalues, self.grad_scale)
         if self.debug is not None:
             self.debug["grads"].append(self.g.clone())
-        ops.clip_adam(self.p, self.g, self.m, self.v, self.count, [0, self.P], [self.lr], grad_scale=1.0,
-                      max_norm=float(s.max_grad_norm), decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                      num_updates=int(s.get("num_updates", 1) or 1), loss_sums=self.g[self.P :], vf_coef=float(s.vf_coef),
-                      ent_coef=float(s.ent_coef), metrics_out=self.train_metrics[n, k, mb])
+        self._clip_adam(n, k, mb)
 
-    def update(self, n: int) -> None:
-        self._rollout(n)
-        self._bootstrap_and_gae()
-        for k in range(self.K):
-            perm = ops.permutation(self.T * self.E, self.seed, self.perm_count)
-            self.perm_count += 1
-            if self.debug is not None:
-                self.debug["perms"].append(perm.clone())
-            for mb in range(self.M):
-                self._minibatch(n, k, mb, perm)
-        rep = self.rep
+    def _carry_observation(self) -> None:
         if self.debug is not None:  # slot 0 of the trajectory is about to become the next rollout's first observation
-            self.debug["slot0"] = (rep.agents_view[0].clone(), rep.action_mask[0].clone())
-        for buf in (rep.agents_view, rep.global_state, rep.action_mask, rep.step_count):
-            buf[0].copy_(buf[self.T])
-
-    def learn(self, learner_state: LearnerState) -> ExperimentOutput:
-        self.adopt(learner_state)
-        if self.matmul_mode == "f16x2":
-            check_f16_range(self.p, [self.rep.agents_view[0]], self.train_metrics if self._learn_calls else None, type(self).__name__)
-        self._learn_calls += 1
-        for n in range(self.n_upd):
-            self.update(n)
-        rep = self.rep
-        ep_metrics = episode_metrics(rep.info_return, rep.info_length, rep.info_terminal)
-        tm = self.train_metrics.unsqueeze(1).unsqueeze(0)
-        train_metrics = {"total_loss": tm[..., 0], "value_loss": tm[..., 1], "actor_loss": tm[..., 2], "entropy": tm[..., 3]}
-        return ExperimentOutput(self.learner_state(), ep_metrics, train_metrics)
+            self.debug["slot0"] = (self.rep.agents_view[0].clone(), self.rep.action_mask[0].clone())
+        super()._carry_observation()
 
 
 def learner_setup(env, keys, config, device=None):
     """(learn, actor_network, initial LearnerState), as mava_amd/learner.py::learner_setup; keys[1] seeds the parameters."""
-    key, net_key = int(keys[0]), int(keys[1])
-    learner = MATLearner(env, config, device)
-    learner.seed = key
-    learner.init_params(net_key)
-    learner.reset_envs()
-    return bind_learn(learner), learner.actor_network, learner.learner_state()
+    return ppo_learner.learner_setup(MATLearner, env, keys, config, device=device)

@@ -13,31 +13,32 @@ rec_ippo.py is the same file with a decentralised critic.  Differences from the 
 Kernel chain per network and minibatch (mava_amd/rec_networks.py): dense(pre) -> dense(gi) -> GRU scan ->
 dense(post) -> dense(head) -> sequence loss -> dense(dpost) -> dense(dh) -> GRU BPTT scan -> dense(dxpre)
 -> five X^T Y weight-gradient products; then [all-reduce] and the same fused clip+Adam as the ff systems.
+
+The replica's trajectory buffers, the constructor's prologue, the flat parameter storage with init_params / adopt / the
+state trees, the slot-0 observation view, update(), the clip+Adam launch, learn() and learner_setup() are PPOLearner's
+(mava_amd/ppo_learner.py); the hidden-state carry, the networks and every launch of the rollout and of a minibatch are
+this module's.
 """
 from __future__ import annotations
 
 import math
 import os
 
-from typing import Any, Dict, List, Optional
+from typing import Optional
 
 import torch
 
-from . import ops, parallel
+from . import ops, parallel, ppo_learner
 from ._lib import check, launch, lib, ptr, stream_ptr
-from .guards import check_f16_range
-from .learner import NUM_CU, _Replica
-from .learner_common import bind_learn, matmul_ctx
-from .networks import MLPTorso, make_action_head
-from .rec_networks import H, RecurrentActor, RecurrentValueNet, RecWorkspace, rows_to_t32, t32_to_rows
-from .types import (AdamState, ExperimentOutput, HiddenStates, Observation, ObservationGlobalState, OptStates, Params,
-                    RNNLearnerState, TimeStep)
-from .utils.tree import tree_to
+from .networks import MLPTorso
+from .ppo_learner import PPOLearner, _Replica
+from .rec_networks import H, RecurrentActor, RecurrentValueNet, RecWorkspace, t32_to_rows
+from .types import HiddenStates, RNNLearnerState, TimeStep
 
 
 class _RecReplica(_Replica):
-    def __init__(self, env, T, n_upd, central, device, continuous: bool = False, hidden: int = H):
-        super().__init__(env, T, n_upd, central, device, continuous)
+    def __init__(self, env, T, n_upd, device, continuous: bool = False, hidden: int = H):
+        super().__init__(env, T, n_upd, device, continuous)
         self.Hd = int(hidden)  # network.hidden_state_dim
         E, A = env.num_envs, env.num_agents
         EA = E * A
@@ -67,52 +68,16 @@ class _RecReplica(_Replica):
         self.value_env = torch.zeros(E, device=dev)
 
 
-class RecLearner:
+class RecLearner(PPOLearner):
     def __init__(self, env, config, centralised_critic: bool, device: Optional[torch.device] = None):
-        self.config = config
-        self.centralised = centralised_critic
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.rank, self.world = parallel.rank_world()
-        s, arch = config.system, config.arch
-        self.E, self.U, self.T = int(arch.num_envs), int(s.update_batch_size), int(s.rollout_length)
-        self.K, self.M = int(s.ppo_epochs), int(s.num_minibatches)
-        chunk = s.get("recurrent_chunk_size", None)
-        if chunk is not None and int(chunk) != self.T:
-            # rec_mappo.py:342-349 reshapes (T,E,..)->(chunk, E*n,..) row-major, which interleaves time and env
-            # unless chunk == T (SURVEY.md Q6); the default (null -> T, :586-587) is the only meaningful setting.
-            raise ValueError("recurrent_chunk_size must be null or equal to rollout_length")
-        if self.E % self.M:
-            raise ValueError("num_envs must be divisible by num_minibatches (rec_mappo.py:354-357)")
-        self.n_upd = int(s.get("num_updates_per_eval", 1))
-        # arithmetic of the dense / X^T Y products on T32 operands: "f16x2" (default, rec_dense_h2.hip) or "f32"
-        self.matmul_mode, self.ctx = matmul_ctx(s)
-        if env.num_envs != self.E:
-            raise ValueError(f"env.num_envs={env.num_envs} != arch.num_envs={self.E}")
-        if centralised_critic and not getattr(env, "add_global_state", False):
-            raise ValueError("Global state must be provided to the centralised critic.")  # networks.py:315-316
-        self.reps: List[_RecReplica] = []
-        # rec_mappo.py:361-363: the action head of the configuration, sized by the env's action dimension
-        action_head = make_action_head(config.network.get("action_head", None), env.action_dim)
-        self.continuous = type(action_head).__name__ == "ContinuousActionHead"
-        self.min_scale = float(getattr(action_head, "min_scale", 1e-3))
-        # of the continuous envs only one with `continuous_actions` reads the f32 action vector (FFLearner.__init__)
-        self._env_reads_action = not self.continuous or getattr(env, "continuous_actions", False)
+        # (arithmetic of the dense / X^T Y products on T32 operands: "f16x2" is rec_dense_h2.hip)
+        super().__init__(env, config, centralised_critic, device, replica=_RecReplica,
+                         replica_kwargs={"hidden": int(config.network.get("hidden_state_dim", 128))})
+        s, action_head = config.system, self.action_head
         # ContinuousActionHead(independent_std=False): the log_std layer is a second head of the actor's post-torso, which then
         # runs on the general layer kernels (mava_amd/generic_networks.py) whatever its torsos are
         self.dep_std = self.continuous and not getattr(action_head, "independent_std", True)
-        for u in range(self.U):
-            rep_env = env.clone(env_offset=getattr(env, "env_offset", 0) + (self.rank * self.U + u) * self.E)
-            self.reps.append(_RecReplica(rep_env, self.T, self.n_upd, centralised_critic, self.device, self.continuous,
-                                         hidden=int(config.network.get("hidden_state_dim", 128))))
-        env0 = self.reps[0].env
-        self.A, self.nA = env0.num_agents, env0.action_dim
-        config.system.num_agents = self.A
-        self.Oa = env0.obs_dim
-        if centralised_critic:
-            self.Oc = env0.state_dim
-            self.critic_share = self.A if env0.global_state_shared else 1
-        else:
-            self.Oc, self.critic_share = self.Oa, 1
+        self.perm_rows = self.E  # rec_mappo.py:277-279: a permutation of the env axis per epoch
         self.Em = self.E // self.M
         self.Rm = self.Em * self.A
         if self.Rm % 32:
@@ -156,16 +121,9 @@ class RecLearner:
             for rep in self.reps:
                 rep.set_critic_rows(1)
         self.Pa, self.Pc = self.actor_network.num_params, self.critic_network.num_params
-        self.P = self.Pa + self.Pc
+        self._alloc_params([(self.actor_network, s.actor_lr), (self.critic_network, s.critic_lr)])
 
         d = self.device
-        self.p = torch.zeros(self.P, device=d)
-        self.m = torch.zeros(self.P, device=d)
-        self.v = torch.zeros(self.P, device=d)
-        self.count = torch.zeros(2, dtype=torch.int32, device=d)
-        self.g = torch.zeros(self.P + 4, device=d)
-        self.seg_off = [0, self.Pa, self.P]
-        self.seg_lr = [float(s.actor_lr), float(s.critic_lr)]
         self.ws_roll = RecWorkspace(self.E * self.A, max(self.nA, 1), d, training=False)
         self.ws = RecWorkspace(self.T * self.Rm, max(self.nA, 1), d, training=True, din_max=max(self.Oa, self.Oc))
         # the backward chain runs in units of a power of two near the row count (mava_seq_actor_loss_f32: f16 range)
@@ -175,10 +133,8 @@ class RecLearner:
                           and os.environ.get("MAVA_REC_FUSED_OUT", "1") != "0")
         self.pack_a = torch.empty(lib().mava_rec_step_pack_bytes(self.Oa), dtype=torch.uint8, device=d)
         self.pack_c = torch.empty(lib().mava_rec_step_pack_bytes(self.Oc), dtype=torch.uint8, device=d)
-        # (with several ranks a few CUs stay free of the persistent X^T Y blocks for RCCL's kernels: learner.py)
-        self.rccl_cus = int(s.get("rccl_cus", None) if s.get("rccl_cus", None) is not None
-                            else os.environ.get("MAVA_RCCL_CUS", "8" if self.world > 1 else "0"))
-        n_slab = max(1, min(NUM_CU - max(0, min(self.rccl_cus, NUM_CU - 1)), (self.T * self.Rm) // 32))
+        # (with several ranks a few CUs stay free of the persistent X^T Y blocks for RCCL's kernels: PPOLearner._slab_count)
+        n_slab = self._slab_count((self.T * self.Rm) // 32)
         self.slabs = torch.zeros((n_slab, H * 3 * H + 3 * H + 8), device=d)
         # The two networks are independent between the parameters of one Adam step and the next (rec_mappo.py:210-266 computes
         # both losses from the same params): the critic's forward / loss / backward runs on a second stream with its own
@@ -194,59 +150,36 @@ class RecLearner:
             c_rows = self.T * (self.Rmc if self.critic_agg else self.Rm)
             self.ws_c = RecWorkspace(c_rows, 1, d, training=True, din_max=self.Oc)
             self.slabs_c = torch.zeros_like(self.slabs)
-        self.stats = torch.zeros((lib().mava_adv_stats_blocks(), 2), dtype=torch.float64, device=d)
-        self.train_metrics = torch.zeros((self.n_upd, self.K, self.M, 4), device=d)
-        self.perm_count = 0  # epoch permutations drawn so far (counter of mava_permutation_i32)
-        self.t_global = 0
-        self.ent_step = 0  # minibatches trained so far: counter of the continuous head's entropy sample
         self.dscale_partials = torch.zeros((self.ws.loss_partials.shape[0], max(self.nA, 1)), device=d)
-        self.seed = int(s.seed)
         self._t_range = torch.arange(self.T, device=d, dtype=torch.int64)[:, None] * self.E
         self._t_range32 = self._t_range.to(torch.int32)
-        self._learn_calls = 0  # guards.check_f16_range
+
+    def _refuse(self, env, config) -> None:
+        chunk = config.system.get("recurrent_chunk_size", None)
+        if chunk is not None and int(chunk) != self.T:
+            # rec_mappo.py:342-349 reshapes (T,E,..)->(chunk, E*n,..) row-major, which interleaves time and env
+            # unless chunk == T (SURVEY.md Q6); the default (null -> T, :586-587) is the only meaningful setting.
+            raise ValueError("recurrent_chunk_size must be null or equal to rollout_length")
+        if self.E % self.M:
+            raise ValueError("num_envs must be divisible by num_minibatches (rec_mappo.py:354-357)")
 
     # ------------------------------------------------------------------------------------ setup
-    def init_params(self, actor_seed: int, critic_seed: int) -> None:
-        self.p[: self.Pa].copy_(self.actor_network.init_flat(actor_seed))
-        self.p[self.Pa :].copy_(self.critic_network.init_flat(critic_seed))
-        self.m.zero_()
-        self.v.zero_()
-        self.count.zero_()
-
     def reset_envs(self) -> None:
+        super().reset_envs()
         for rep in self.reps:
-            rep.env.step_into(rep.state, 0, rep.obs_slot(0), is_reset=True)
             rep.dones.zero_()      # rec_mappo.py:555-558
             rep.h_actor.zero_()    # ScannedRNN.initialize_carry: zeros (:497-502)
             rep.h_critic.zero_()
-        self.t_global = 0
-        self.ent_step = 0
-        self.perm_count = 0
 
     # ---------------------------------------------------------------------------- state views
     def learner_state(self) -> RNNLearnerState:
-        lead = (1, self.U)
-        params = Params(self.actor_network.tree(self.p[: self.Pa], lead), self.critic_network.tree(self.p[self.Pa :], lead))
-        opts = []
-        for i, (net, sl) in enumerate(((self.actor_network, slice(0, self.Pa)), (self.critic_network, slice(self.Pa, self.P)))):
-            opts.append(AdamState(self.count[i].expand(1, self.U), net.tree(self.m[sl], lead), net.tree(self.v[sl], lead)))
-        key = torch.tensor([[[self.seed, self.t_global]] * self.U], dtype=torch.int64)
-        st = lambda f: torch.stack([f(r) for r in self.reps], 0).unsqueeze(0)
-        E, A = self.E, self.A
-        av, mask, sc = st(lambda r: r.agents_view[0]), st(lambda r: r.action_mask[0]).bool(), st(lambda r: r.step_count[0])
-        if self.centralised:
-            gs = st(lambda r: r.global_state[0].expand(-1, A, -1) if r.env.gs_tiles == 1 else r.global_state[0])
-            obs: Any = ObservationGlobalState(av, mask, gs, sc)
-        else:
-            obs = Observation(av, mask, sc)
+        st, E, A, D = self._stack, self.E, self.A, self.Hd
         dones = st(lambda r: r.dones).bool()
-        ts = TimeStep(torch.where(dones[..., 0], 2, 1).to(torch.int8), st(lambda r: r.last_reward), 1.0 - dones.float(), obs, {})
-        D = self.Hd
+        ts = TimeStep(torch.where(dones[..., 0], 2, 1).to(torch.int8), st(lambda r: r.last_reward), 1.0 - dones.float(),
+                      self._observation(), {})
         hst = HiddenStates(st(lambda r: t32_to_rows(r.h_actor, D, E * A).view(E, A, D)),
                            st(lambda r: t32_to_rows(r.h_critic, D, E * self.Ac).view(E, self.Ac, D).expand(E, A, D)))
-        env_state = {"step_count": st(lambda r: r.state.step_count), "episode_return": st(lambda r: r.state.ep_return),
-                     "episode_length": st(lambda r: r.state.ep_length)}
-        return RNNLearnerState(params, OptStates(*opts), key, env_state, ts, dones, hst)
+        return RNNLearnerState(self._params_tree(), self._opt_tree(), self._key(), self._env_state(), ts, dones, hst)
 
     # ------------------------------------------------------------------------------------ update
     def _critic_x(self, rep, lo, hi):
@@ -464,71 +397,9 @@ class RecLearner:
             actor_part(self.ws, self.slabs)
             critic_part(self.ws, self.slabs)
         parallel.allreduce_sum_(self.g)
-        ops.clip_adam(self.p, self.g, self.m, self.v, self.count, self.seg_off, self.seg_lr,
-                      grad_scale=1.0 / (self.U * self.world), max_norm=float(s.max_grad_norm),
-                      decay=bool(s.decay_learning_rates), steps_per_update=self.K * self.M,
-                      num_updates=int(s.get("num_updates", 1) or 1), loss_sums=self.g[self.P :], vf_coef=float(s.vf_coef),
-                      ent_coef=float(s.ent_coef), metrics_out=self.train_metrics[n, k, mb])
-        self.ent_step += 1
-
-    def update(self, n: int, permutations: Optional[List[torch.Tensor]] = None) -> None:
-        self._rollout(n)
-        self._bootstrap_and_gae()
-        for k in range(self.K):
-            if permutations is not None:
-                perm = permutations[k]
-            else:  # rec_mappo.py:277-279: a permutation of the env axis per epoch
-                perm = ops.permutation(self.E, self.seed, self.perm_count)
-                self.perm_count += 1
-            for mb in range(self.M):
-                self._minibatch(n, k, mb, perm)
-        for rep in self.reps:
-            rep.agents_view[0].copy_(rep.agents_view[self.T])
-            rep.global_state[0].copy_(rep.global_state[self.T])
-            rep.action_mask[0].copy_(rep.action_mask[self.T])
-            rep.step_count[0].copy_(rep.step_count[self.T])
-
-    def adopt(self, state: RNNLearnerState) -> None:
-        """Make the parameter / optimiser buffers equal to `state` (no-op for trees that already alias them), so
-        that learn() follows its argument like the reference's pure learner_fn - e.g. params restored from a
-        checkpoint (rec_mappo.py:558-566).  Environment and hidden state stay with the learner."""
-        pa = next(iter(state.params.actor_params["params"]["pre_torso"].values()))["kernel"]  # Dense_0 | Conv_0: the flat buffer's start
-        if not isinstance(pa, torch.Tensor) or pa.data_ptr() != self.p.data_ptr():
-            dev = self.p.device
-            to = lambda tree: tree_to(tree, dev)
-            self.actor_network.flat_from_tree(to(state.params.actor_params), self.p[: self.Pa])
-            self.critic_network.flat_from_tree(to(state.params.critic_params), self.p[self.Pa :])
-            for i, (net, sl, st) in enumerate(((self.actor_network, slice(0, self.Pa), state.opt_states.actor_opt_state),
-                                               (self.critic_network, slice(self.Pa, self.P), state.opt_states.critic_opt_state))):
-                net.flat_from_tree(to(st.mu), self.m[sl])
-                net.flat_from_tree(to(st.nu), self.v[sl])
-                self.count[i] = int(torch.as_tensor(st.count).reshape(-1)[0])
-
-    def learn(self, learner_state: RNNLearnerState) -> ExperimentOutput:
-        self.adopt(learner_state)
-        if self.matmul_mode == "f16x2":
-            obs = [t for r in self.reps for t in (r.agents_view[0], r.global_state[0] if self.centralised else None)]
-            check_f16_range(self.p, obs, self.train_metrics if self._learn_calls else None, type(self).__name__)
-        self._learn_calls += 1
-        for n in range(self.n_upd):
-            self.update(n)
-        U = self.U
-        episode_metrics = {
-            "episode_return": torch.stack([r.info_return for r in self.reps], 1).unsqueeze(0),
-            "episode_length": torch.stack([r.info_length for r in self.reps], 1).unsqueeze(0),
-            "is_terminal_step": torch.stack([r.info_terminal for r in self.reps], 1).unsqueeze(0).bool(),
-        }
-        tm = self.train_metrics.unsqueeze(1).expand(self.n_upd, U, self.K, self.M, 4).unsqueeze(0)
-        train_metrics = {"total_loss": tm[..., 0], "value_loss": tm[..., 1], "actor_loss": tm[..., 2], "entropy": tm[..., 3]}
-        return ExperimentOutput(self.learner_state(), episode_metrics, train_metrics)
+        self._clip_adam(n, k, mb)
 
 
 def learner_setup(env, keys, config, centralised_critic: bool, device=None):
     """Counterpart of learner_setup (rec_mappo.py:437-576): (learn, actor_network, init RNNLearnerState)."""
-    key, actor_key, critic_key = (int(k) for k in keys)
-    learner = RecLearner(env, config, centralised_critic, device)
-    learner.seed = key
-    learner.init_params(actor_key, critic_key)
-    parallel.broadcast_(learner.p, src=0)
-    learner.reset_envs()
-    return bind_learn(learner), learner.actor_network, learner.learner_state()
+    return ppo_learner.learner_setup(RecLearner, env, keys, config, centralised_critic, device=device)

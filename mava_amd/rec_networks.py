@@ -178,6 +178,9 @@ class _RecurrentNet:
         tree.update(self._head_tree(head))
         return {"params": tree}
 
+    def first_leaf(self, tree: Dict[str, Any]) -> torch.Tensor:
+        return next(iter(tree["params"]["pre_torso"].values()))["kernel"]  # Dense_0 | Conv_0: the flat buffer's start
+
     def flat_from_tree(self, tree: Dict[str, Any], out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inverse of tree(): gathers a Flax-shaped parameter tree (leading replica dims allowed: replica 0 is
         taken, like unreplicate_n_dims, mava/utils/jax_utils.py:52-59) into the flat layout the kernels read."""
