@@ -66,10 +66,10 @@ enum {
                                       only, two MFMAs per product, the next x tile staged beside this one (ppo_train_h2.hip) -, summed
                                       over launches.  Reading it waits for the device; 0 is the only value that can be written */
   MAVA_CTX_X16_LAUNCHES = 9,       /* diagnostic counter on the device: wide f16x2 critic launches of the handle that staged their input
-                                      from the caller's f16 copy (mava_ppo_critic_grad_x16_f32 with a valid copy).  Reading it waits for
+                                      from the caller's f16 copy (mava_ppo_critic_grad_f32 with a valid input16).  Reading it waits for
                                       the device; 0 is the only value that can be written */
   MAVA_CTX_X16_W8_LAUNCHES = 10,   /* the same for the eight-wave f16x2 kernel (discrete actor <= 16 actions, value network on <= 127
-                                      inputs): launches of mava_ppo_actor_grad_x16_f32 / mava_ppo_critic_grad_x16_f32 that staged their
+                                      inputs): launches of mava_ppo_actor_grad_f32 / mava_ppo_critic_grad_f32 that staged their
                                       input from the f16 record */
   MAVA_CTX_W8_DEFER_LAUNCHES = 11, /* ... of which ran the deferred-dW1 tile loop (role-split instances, <= 8 actions, unless
                                       MAVA_CTX_TRAIN_VARIANT bit 2 is set).  Reading it waits for the device; 0 is the only value that
@@ -194,13 +194,16 @@ int mava_adv_stats_f64(const float* advantages, const int32_t* idx, long idx_bas
 int mava_adv_stats_batched_f64(const float* advantages, const int32_t* idx, long idx_stride, int Rb, int A,
                                int n_batch, double* partials, mava_stream_t s);
 
-/* _actor_loss_fn, ff_mappo.py:150-180.  slab tail: [actor_loss, entropy]. */
+/* _actor_loss_fn, ff_mappo.py:150-180.  slab tail: [actor_loss, entropy].
+ * input16 / input16_valid / input16_ld (NULL, NULL, 0: none): an f16 record of agents_view under the contract stated at
+ * mava_ppo_critic_grad_f32: input16 (rows of agents_view, input16_ld) IEEE binary16, input16_valid its device word.  The
+ * eight-wave kernel reads the word once per block and with 1 stages its input with 16-byte loads and LDS stores of the
+ * halves - no conversion; the gradient has the same bits either way. */
 int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
-                            const uint8_t* action_mask, const int32_t* action,
-                            const float* old_log_prob, const float* advantages,
-                            const double* adv_stats, const int32_t* idx, long idx_base, int Rb,
-                            int A, float clip_eps, float ent_coef, float* slab, long slab_stride,
-                            int n_slab, mava_stream_t s);
+                            const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
+                            const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base, int Rb,
+                            int A, float clip_eps, float ent_coef, float* slab, long slab_stride, int n_slab,
+                            const uint16_t* input16, const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
 
 /* Continuous action head: Independent(TanhTransformed(Normal(loc, softplus(log_std) + 1e-3))),
  * mava/networks.py:127-169 + mava/distributions.py:24-91 (log_prob clipped at +-0.999, sampled entropy).
@@ -228,42 +231,28 @@ int mava_ppo_actor_grad_continuous_f32(const float* params, int din, int action_
                                        mava_stream_t s);
 
 /* _critic_loss_fn, ff_mappo.py:182-201.  critic_input row = agent_row / x_share.
- * slab tail: [value_loss, unused]. */
+ * slab tail: [value_loss, unused].
+ * input16 / input16_valid / input16_ld (NULL, NULL, 0: none): an f16 copy of critic_input: input16 (rows of critic_input, din)
+ * IEEE binary16, contiguous, 16-byte aligned, and input16_valid, one 32-bit device word written by whoever wrote the copy
+ * (mava_rollout_ff_f32's state16_valid): 1 = input16 holds, for every element, the f16 high term f16(critic_input) that the
+ * kernel would form itself, and the low term f16(critic_input - high) is zero everywhere (an input whose remainder
+ * underflows f16, such as 1 + 2^-30, counts as exact there too: the f32 path drops the same remainder).  The wide f16x2
+ * critic kernel (96..287 inputs) then reads the word on the device, once per block, and with 1 stages its input from the
+ * copy - half the bytes, no conversion, every tile in the exact-input loop (MAVA_CTX_X16_LAUNCHES counts such launches);
+ * the gradient has the same bits either way.  The copy is NOT read when the word is not 1, when either pointer is NULL,
+ * din % 8 != 0, critic_input is not 16-byte aligned, MAVA_CTX_TRAIN_VARIANT bit 1 is set, or another kernel takes the
+ * launch.  The host never reads the word.  Arguments rather than handle keys: the rollout takes no handle, and a learner
+ * with several replicas has one copy per replica.
+ * input16_ld: halves between rows of input16; 0 = din (all the wide kernel takes).  The eight-wave kernel (din <= 127,
+ * x_share == 1, no aggregation) reads a record with input16_ld % 8 == 0 and input16_ld >= din on a 16-byte aligned base;
+ * where input16_ld > din the row is laid out like mava_rollout_ff_f32's view16 (din values, 1.0, zeros to a multiple of
+ * 8).  Such launches are counted by MAVA_CTX_X16_W8_LAUNCHES.  Odd din, a misaligned base or row, MAVA_CTX_TRAIN_VARIANT
+ * bit 1, a word that is not 1: the record is not read. */
 int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
                              const float* old_value, const float* targets, const int32_t* idx,
                              long idx_base, int Rb, int A, float clip_eps, float vf_coef,
-                             float* slab, long slab_stride, int n_slab, mava_stream_t s);
-
-/* mava_ppo_critic_grad_f32 with an f16 copy of critic_input: input16 (rows of critic_input, din) IEEE binary16, contiguous,
- * 16-byte aligned, and input16_valid, one 32-bit device word written by whoever wrote the copy (mava_rollout_ff_x16_f32):
- * 1 = input16 holds, for every element, the f16 high term f16(critic_input) that the kernel would form itself, and the low term
- * f16(critic_input - high) is zero everywhere (an input whose remainder underflows f16, such as 1 + 2^-30, counts as exact there
- * too: the f32 path drops the same remainder).  The wide f16x2 critic kernel (96..287 inputs) then reads the word on the
- * device, once per block, and with 1 stages its input from the copy - half the bytes, no conversion, every tile in the
- * exact-input loop (MAVA_CTX_X16_LAUNCHES counts such launches); the gradient has the same bits either way.  The copy is
- * NOT read, and the call is mava_ppo_critic_grad_f32, when the word is not 1, when either pointer is NULL, din % 8 != 0,
- * critic_input is not 16-byte aligned, MAVA_CTX_TRAIN_VARIANT bit 1 is set, or another kernel takes the launch.  The host
- * never reads the word.  New entry points rather than handle keys: the rollout takes no handle, and a learner with several
- * replicas has one copy per replica. */
-int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
-                                 const float* old_value, const float* targets, const int32_t* idx,
-                                 long idx_base, int Rb, int A, float clip_eps, float vf_coef,
-                                 float* slab, long slab_stride, int n_slab, const uint16_t* input16,
-                                 const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
-/* input16_ld: halves between rows of input16; 0 = din (all the wide kernel takes).  The eight-wave kernel (din <= 127, x_share == 1,
- * no aggregation) reads a record with input16_ld % 8 == 0 and input16_ld >= din on a 16-byte aligned base; where input16_ld > din
- * the row is laid out like mava_rollout_ff_records16_f32's view16 (din values, 1.0, zeros to a multiple of 8).  Such launches are
- * counted by MAVA_CTX_X16_W8_LAUNCHES.  Odd din, a misaligned base or row, MAVA_CTX_TRAIN_VARIANT bit 1, a word that is not 1:
- * the record is not read. */
-
-/* mava_ppo_actor_grad_f32 with an f16 record of agents_view under the same contract: input16 (rows of agents_view, input16_ld)
- * IEEE binary16 as above, input16_valid its device word.  The eight-wave kernel reads the word once per block and with 1 stages
- * its input with 16-byte loads and LDS stores of the halves - no conversion; the gradient has the same bits either way. */
-int mava_ppo_actor_grad_x16_f32(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
-                                const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
-                                const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base, int Rb,
-                                int A, float clip_eps, float ent_coef, float* slab, long slab_stride, int n_slab,
-                                const uint16_t* input16, const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
+                             float* slab, long slab_stride, int n_slab, const uint16_t* input16,
+                             const uint32_t* input16_valid, int input16_ld, mava_stream_t s);
 
 /* Both gradient kernels read MAVA_CTX_MATMUL_MODE, the critic also MAVA_CTX_CRITIC_AGGREGATION, from their handle. */
 
@@ -299,29 +288,22 @@ int mava_synth_rware_step(int E, int A, int O, int n_actions, int gs_tiles, int 
  *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a terminal step regenerates
  *      that env and returns the reset observation (AutoResetWrapper).  Randomness: Philox4x32-10 with key `seed`, counter
  *      (env_offset + e, t + *t_base, block, "LBFS"); t_base (a device word, may be NULL) is added on the device, so the
- *      step replays from a captured graph.  No host state, no synchronisation. */
+ *      step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL): what AutoResetWrapper keeps in extras["real_next_obs"]
+ *      (mava/wrappers/auto_reset_wrapper.py:52-101), for rec_iql's replay buffer: real_view (E, A, A + 3 (F + A)) /
+ *      real_mask (E, A, 6) are the observation of the state the rules produced BEFORE any auto-reset (equal to agents_view
+ *      / action_mask where the step did not end), and terminated (E) is 1 only when every food was eaten - a time-limit end
+ *      is a truncation (termination vs truncation as in Jumanji's LBF).  Every other output is the same with or without
+ *      them.  None of the three is written on a reset call.  All three NULL: none of this is computed (the plain kernel
+ *      instance); one or two of them NULL is an argument error; on a step they must not alias agents_view / action_mask. */
 int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop, int individual_rewards,
                   int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
                   int32_t* agent_pos, int32_t* agent_level, int32_t* food_pos, int32_t* food_level, uint8_t* food_alive,
-                  float* total_food_level, int32_t* step_count, float* run_return, int32_t* run_length,
-                  float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                  uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                  int32_t* info_length, uint8_t* info_terminal, const int32_t* action, mava_stream_t s);
-
-/* The same step plus what AutoResetWrapper keeps in extras["real_next_obs"] (mava/wrappers/auto_reset_wrapper.py:52-101),
- * for rec_iql's replay buffer: real_view (E, A, A + 3 (F + A)) / real_mask (E, A, 6) are the observation of the state
- * the rules produced BEFORE any auto-reset (equal to agents_view / action_mask where the step did not end), and
- * terminated (E) is 1 only when every food was eaten - a time-limit end is a truncation (termination vs truncation as in
- * Jumanji's LBF).  None of the three is written on a reset call (they may then be NULL); otherwise they must not alias
- * agents_view / action_mask.  Every other output equals mava_lbf_step's. */
-int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop, int individual_rewards,
-                            int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
-                            int32_t* agent_pos, int32_t* agent_level, int32_t* food_pos, int32_t* food_level, uint8_t* food_alive,
-                            float* total_food_level, int32_t* step_count, float* run_return, int32_t* run_length,
-                            float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                            uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                            int32_t* info_length, uint8_t* info_terminal, const int32_t* action, float* real_view,
-                            uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+                  float* total_food_level, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                  int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                  int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
+                  uint8_t* info_terminal, const int32_t* action, float* real_view, uint8_t* real_mask, uint8_t* terminated,
+                  mava_stream_t s);
 
 /* ---- Robot Warehouse environment step (mava_amd/csrc/rware.hip; rules in DESIGN.md "Robot Warehouse", restated in
  *      tests/rware_model.py; parity with Jumanji's RobotWarehouse is unpinned).  E environments of an H x W grid
@@ -346,7 +328,12 @@ int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_l
  *      (reward, done, info_* and action may then be NULL); a terminal step regenerates that env and returns the reset
  *      observation.  Randomness: Philox4x32-10, key `seed`, counter (env_offset + e, t + *t_base, block, "RWRS") for a
  *      reset and (.., agent / 4, "RWRQ") word agent % 4 for a refill; t_base (a device word, may be NULL) is added on the
- *      device, so the step replays from a captured graph.  No host state, no synchronisation. */
+ *      device, so the step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL), as in mava_lbf_step: real_view (E, A, A + raw) /
+ *      real_mask (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is 1 only on a
+ *      collision termination - a time-limit end is a truncation.  None of the three is written on a reset call.  All three
+ *      NULL: none of this is computed (the plain kernel instance); one or two of them NULL is an argument error; on a step
+ *      they must not alias agents_view / action_mask. */
 int mava_rware_step(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit, int collision_terminates,
                     const uint32_t* highway_rows, const int32_t* shelf_home, uint64_t seed, uint32_t t,
                     const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_dir,
@@ -354,21 +341,7 @@ int mava_rware_step(int E, int A, int S, int R, int H, int W, int sensor_range, 
                     float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
                     float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
                     float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                    mava_stream_t s);
-
-/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
- * (E, A, A + raw) / real_mask (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
- * 1 only on a collision termination - a time-limit end is a truncation.  None of the three is written on a reset call
- * (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
-int mava_rware_step_real_next(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit,
-                              int collision_terminates, const uint32_t* highway_rows, const int32_t* shelf_home,
-                              uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
-                              int32_t* agent_pos, int32_t* agent_dir, int32_t* agent_carry, int32_t* shelf_pos,
-                              int32_t* request_queue, int32_t* step_count, float* run_return, int32_t* run_length,
-                              float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                              uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                              float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                              float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+                    float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
 /* ---- Connector environment step (mava_amd/csrc/connector.hip; rules in DESIGN.md "Connector", stated in
  *      tests/connector_model.py, which is the contract; parity with Jumanji's MaConnector is unpinned).  E environments
@@ -388,25 +361,19 @@ int mava_rware_step_real_next(int E, int A, int S, int R, int H, int W, int sens
  *      info_* (E).  is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a terminal step
  *      regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`, counter
  *      (env_offset + e, t + *t_base, block, "CONR"); t_base (a device word, may be NULL) is added on the device, so the
- *      step replays from a captured graph.  No host state, no synchronisation. */
+ *      step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL), as in mava_lbf_step: real_view (E, A, G G 5) / real_mask
+ *      (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is 1 when no agent has a
+ *      legal move - a time-limit end alone is a truncation.  None of the three is written on a reset call.  All three NULL:
+ *      none of this is computed (the plain kernel instance); one or two of them NULL is an argument error; on a step they
+ *      must not alias agents_view / action_mask. */
 int mava_connector_step(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
                         uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
                         uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
                         int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
                         int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
-                        uint8_t* info_terminal, const int32_t* action, mava_stream_t s);
-
-/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
- * (E, A, G G 5) / real_mask (E, A, 5) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
- * 1 when no agent has a legal move - a time-limit end alone is a truncation.  None of the three is written on a reset
- * call (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
-int mava_connector_step_real_next(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                                  uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
-                                  uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length,
-                                  float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                                  uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                  float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                                  float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+                        uint8_t* info_terminal, const int32_t* action, float* real_view, uint8_t* real_mask,
+                        uint8_t* terminated, mava_stream_t s);
 
 /* ---- Cleaner environment step (mava_amd/csrc/cleaner.hip; rules in DESIGN.md "Cleaner", stated in
  *      tests/cleaner_model.py, which is the contract; parity with Jumanji's Cleaner is unpinned).  E environments of an
@@ -433,25 +400,18 @@ int mava_connector_step_real_next(int E, int A, int G, int time_limit, uint64_t 
  *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL, info_won is not written); a
  *      terminal step regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`,
  *      counter (env_offset + e, t + *t_base, block, "CLNR"); t_base (a device word, may be NULL) is added on the device,
- *      so the step replays from a captured graph.  No host state, no synchronisation. */
+ *      so the step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL), as in mava_lbf_step: real_view (E, A, R C 4) / real_mask
+ *      (E, A, 4) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is won | invalid - a time-
+ *      limit end alone is a truncation.  None of the three is written on a reset call.  All three NULL: none of this is
+ *      computed (the plain kernel instance); one or two of them NULL is an argument error; on a step they must not alias
+ *      agents_view / action_mask. */
 int mava_cleaner_step(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
                       uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid, int32_t* step_count,
                       float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
                       float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
                       float* info_return, int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won,
-                      const int32_t* action, mava_stream_t s);
-
-/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
- * (E, A, R C 4) / real_mask (E, A, 4) observe the state the rules produced BEFORE any auto-reset, and terminated (E) is
- * won | invalid - a time-limit end alone is a truncation.  None of the three is written on a reset call (they may then
- * be NULL); otherwise they must not alias agents_view / action_mask. */
-int mava_cleaner_step_real_next(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t,
-                                const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid,
-                                int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                                int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
-                                float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
+                      const int32_t* action, float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
 /* ---- SMAX environment step (mava_amd/csrc/smax.hip; rules in DESIGN.md "SMAX", stated in tests/smax_model.py, which is
  *      the contract; parity with JaxMARL's SMAX is unpinned).  E environments of A allies (the agents, 1 <= A <= 16)
@@ -489,28 +449,19 @@ int mava_cleaner_step_real_next(int E, int A, int R, int C, int time_limit, uint
  *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL, info_won is not written); a
  *      terminal step regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`,
  *      counter (env_offset + e, t + *t_base, block, "SMAX"); t_base (a device word, may be NULL) is added on the device,
- *      so the step replays from a captured graph.  No host state, no synchronisation. */
+ *      so the step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL), as in mava_lbf_step: real_view (E, A, obs_dim) /
+ *      real_mask (E, A, 5 + Ne) observe the state the rules produced BEFORE any auto-reset, and terminated (E) says that a
+ *      side was wiped out - a time-limit end alone is a truncation.  None of the three is written on a reset call.  All
+ *      three NULL: none of this is computed (the plain kernel instance); one or two of them NULL is an argument error; on a
+ *      step they must not alias agents_view / action_mask. */
 int mava_smax_step(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit, int see_enemy_actions,
                    int walls_cause_death, uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset,
                    int is_reset, float* pos, float* health, int32_t* cd, int32_t* last_action, int32_t* step_count,
                    float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
                    float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
                    float* info_return, int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won,
-                   const int32_t* action, mava_stream_t s);
-
-/* The same step plus the pre-reset observation for rec_iql's replay buffer, as mava_lbf_step_real_next: real_view
- * (E, A, obs_dim) / real_mask (E, A, 5 + Ne) observe the state the rules produced BEFORE any auto-reset, and terminated
- * (E) says that a side was wiped out - a time-limit end alone is a truncation.  None of the three is written on a reset
- * call (they may then be NULL); otherwise they must not alias agents_view / action_mask. */
-int mava_smax_step_real_next(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit,
-                             int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t,
-                             const uint32_t* t_base, uint32_t env_offset, int is_reset, float* pos, float* health,
-                             int32_t* cd, int32_t* last_action, int32_t* step_count, float* run_return,
-                             int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                             float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward,
-                             uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                             uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
-                             uint8_t* terminated, mava_stream_t s);
+                   const int32_t* action, float* real_view, uint8_t* real_mask, uint8_t* terminated, mava_stream_t s);
 
 /* ---- Spread environment step (mava_amd/csrc/spread.hip; rules in DESIGN.md "Spread", stated in tests/spread_model.py,
  *      which is the contract).  This project's own continuous-action task, modelled on MPE simple_spread; it restates no
@@ -531,27 +482,19 @@ int mava_smax_step_real_next(int E, int A, int Ne, uint64_t ally_types, uint64_t
  *      is_reset 1 generates every env (reward, done, info_* and action may then be NULL); a step that reaches the time
  *      limit regenerates that env and returns the reset observation.  Randomness: Philox4x32-10, key `seed`, counter
  *      (env_offset + e, t + *t_base, block, "SPRD"); t_base (a device word, may be NULL) is added on the device, so the
- *      step replays from a captured graph.  No host state, no synchronisation. */
+ *      step replays from a captured graph.  No host state, no synchronisation.
+ *      real_view / real_mask / terminated (all three or all NULL), as in mava_lbf_step, for an off-policy replay: real_view
+ *      (E, A, obs_dim) / real_mask (E, A, 2) observe the state the rules produced BEFORE any auto-reset; terminated (E) is
+ *      always 0 - a time-limit end is a truncation; real_state (E, 1, 4A), which may be NULL with them given and must be
+ *      NULL without them, is the pre-reset global_state (ff_masac's next state).  None of them is written on a reset call.
+ *      The three NULL: none of this is computed (the plain kernel instance); one or two of them NULL is an argument error;
+ *      on a step they must not alias agents_view / action_mask / global_state. */
 int mava_spread_step(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
                      uint32_t env_offset, int is_reset, float* agent_pos, float* landmark_pos, int32_t* step_count,
                      float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
                      float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
                      float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
-                     mava_stream_t s);
-
-/* The same step plus the pre-reset observation for an off-policy replay, as mava_lbf_step_real_next: real_view
- * (E, A, obs_dim) / real_mask (E, A, 2) observe the state the rules produced BEFORE any auto-reset; terminated (E) is
- * always 0 - a time-limit end is a truncation; real_state (E, 1, 4A), which may be NULL, is the pre-reset global_state
- * (ff_masac's next state).  None of them is written on a reset call (they may then be NULL); otherwise they must not
- * alias agents_view / action_mask / global_state. */
-int mava_spread_step_real_next(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t,
-                               const uint32_t* t_base, uint32_t env_offset, int is_reset, float* agent_pos,
-                               float* landmark_pos, int32_t* step_count, float* run_return, int32_t* run_length,
-                               float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                               uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                               float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
-                               float* real_view, uint8_t* real_mask, uint8_t* terminated, float* real_state,
-                               mava_stream_t s);
+                     float* real_view, uint8_t* real_mask, uint8_t* terminated, float* real_state, mava_stream_t s);
 
 /* ---- fused rollout: the whole `lax.scan(_env_step, length=T)` of mava/systems/ppo/ff_mappo.py:76-106 for one
  *      update-batch replica on the synthetic RWARE-shaped environment, plus the bootstrap value of :109-110, in ONE
@@ -565,6 +508,25 @@ int mava_spread_step_real_next(int E, int A, int add_agent_id, int time_limit, u
  *      action_mask must hold the current observation; slots 1..T are written, the env state is advanced in place.
  *      adv / tgt (T, E, A) or both NULL: when given, every (env, agent) column's GAE (ff_mappo.py:112-139, sequential
  *      f32 recurrence) runs in the kernel's tail on the rewards / values / dones just written - no separate pass.
+ *      Three optional groups of outputs, each NULL or given on its own:
+ *      last_reward / last_done (E, A) = reward[T-1] / done[T-1], what a caller otherwise copies after the launch; only with
+ *      them, step_counter: when not NULL, *step_counter += T (one thread, at the kernel's end: pass it for ONE replica of
+ *      an update; the launch counts from t0 and never reads it).
+ *      state16 / state16_valid, an f16 copy of the shared global state for mava_ppo_critic_grad_f32's input16: state16
+ *      (T+1, E, A*O) IEEE binary16, contiguous, 16-byte aligned - every slot, slot 0 included, is written by the launch
+ *      with the halves the kernel's LDS image holds (global_state is their conversion to f32) - and state16_valid, one
+ *      32-bit device word that must hold 0 or 1 on entry (allocate it zeroed) and is left 1 when every value the launch
+ *      loaded from slot 0 of global_state had a zero low f16 term f16(x - f16(x)), else 0; with 1, state16[t] is the f16
+ *      high term of global_state[t] that the critic kernel would form itself, for every t < T (slots 1 .. T-1 are
+ *      float(state16[t]) == global_state[t] bit for bit always; slot 0 is the caller's, and a value there whose remainder
+ *      underflows f16 counts as exact, as it does in the f32 staging path).  (Between entry and the end of the launch the
+ *      word counts blocks; the last block stores the result.)  Needs critic_shared and A*O % 8 == 0.
+ *      view16 / view16_valid, an f16 record of agents_view for mava_ppo_actor_grad_f32's input16 (and
+ *      mava_ppo_critic_grad_f32's under a decentralised critic): view16 (T+1, E, A, RP) IEEE binary16 with RP =
+ *      8 * ceil((A + O + 1) / 8), contiguous, 16-byte aligned - every slot's row is the row of the kernel's LDS image:
+ *      halves [0, A+O) the observation (agents_view is their conversion to f32), half A+O 1.0, the rest 0 - and
+ *      view16_valid, a device word under state16_valid's protocol (0 or 1 on entry; left 1 when every slot-0 value of
+ *      agents_view had a zero low f16 term, else 0).  Every instance takes it, shared critic or not.
  *      Returns 0, a negative error, or 1 when the shape is not instantiated (the caller then runs mava_policy_step_f32
  *      + mava_synth_rware_step per step): needs 64 % A == 0, n_actions <= 8, the RWARE-style global state. */
 int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
@@ -574,54 +536,9 @@ int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* c
                         int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
                         int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
                         uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                        uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda, mava_stream_t s);
-/* mava_rollout_ff_f32 that also writes what a caller otherwise copies or adds after it: last_reward / last_done (E, A) =
- * reward[T-1] / done[T-1], and, when step_counter is not NULL, *step_counter += T (one thread, at the kernel's end: pass
- * it for ONE replica of an update; the launch counts from t0 and never reads it). */
-int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                             int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                             uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                             int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                             uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                             uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                             float* last_reward, uint8_t* last_done, int32_t* step_counter, mava_stream_t s);
-/* mava_rollout_ff_tail_f32 that also writes an f16 copy of the shared global state, for mava_ppo_critic_grad_x16_f32:
- * state16 (T+1, E, A*O) IEEE binary16, contiguous, 16-byte aligned - every slot, slot 0 included, is written by the launch
- * with the halves the kernel's LDS image holds (global_state is their conversion to f32) - and state16_valid, one 32-bit
- * device word that must hold 0 or 1 on entry (allocate it zeroed) and is left 1 when every value the launch loaded from slot 0
- * of global_state had a zero low f16 term f16(x - f16(x)), else 0; with 1, state16[t] is the f16 high term of global_state[t] that
- * the critic kernel would form itself, for every t < T (slots 1 .. T-1 are float(state16[t]) == global_state[t] bit for bit always; slot 0
- * is the caller's, and a value there whose remainder underflows f16 counts as exact, as it does in the f32 staging path).  (Between
- * entry and the end of the launch the word counts blocks; the last block stores the result.)  Needs critic_shared and
- * A*O % 8 == 0.  Both NULL (and last_reward / last_done NULL or not, as in the two calls above): exactly those calls. */
-int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                            int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                            uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                            int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                            int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                            int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                            uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                            uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                            float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                            uint32_t* state16_valid, mava_stream_t s);
-/* ... and / or an f16 record of agents_view, for mava_ppo_actor_grad_x16_f32 (and mava_ppo_critic_grad_x16_f32 under a
- * decentralised critic): view16 (T+1, E, A, RP) IEEE binary16 with RP = 8 * ceil((A + O + 1) / 8), contiguous, 16-byte aligned - every
- * slot's row is the row of the kernel's LDS image: halves [0, A+O) the observation (agents_view is their conversion to f32), half
- * A+O 1.0, the rest 0 - and view16_valid, a device word under state16_valid's protocol (0 or 1 on entry; left 1 when every
- * slot-0 value of agents_view had a zero low f16 term, else 0).  Every instance takes it, shared critic or not; each of the two
- * pairs may be NULL on its own. */
-int mava_rollout_ff_records16_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                                  int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                                  uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                                  int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                  int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                  int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                                  uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                                  uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                                  float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                                  uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, mava_stream_t s);
+                        uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                        float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                        uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, mava_stream_t s);
 /* The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of agents_view
  * (T+1, E, A, obs_dim) f32, global_state (T+1, E, gs_dim) f32 (NULL with gs_dim 0: none), action_mask (T+1, E, A,
  * n_actions) u8 and step_count (T+1, E, A) i32, in one launch.  Slots 1..T are not touched. */

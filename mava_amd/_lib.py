@@ -59,24 +59,15 @@ _SIGNATURES = {
     "mava_adv_stats_f64": [vp, vp, lng, i32, i32, vp, vp],
     "mava_adv_stats_batched_f64": [vp, vp, lng, i32, i32, i32, vp, vp],
     "mava_ppo_actor_grad_f32": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32,
-                                vp],
-    "mava_ppo_critic_grad_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp],
-    "mava_ppo_critic_grad_x16_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp, vp, i32, vp],
-    "mava_ppo_actor_grad_x16_f32": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32,
-                                    vp, vp, i32, vp],
+                                vp, vp, i32, vp],
+    "mava_ppo_critic_grad_f32": [vp, vp, i32, vp, i32, vp, vp, vp, lng, i32, i32, f32, f32, vp, lng, i32, vp, vp, i32, vp],
     "mava_synth_rware_step": [i32, i32, i32, i32, i32, i32, i32, u64, u32, vp, u32, i32] + [vp] * 14 + [vp, i32, vp],
-    "mava_lbf_step": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
-    "mava_lbf_step_real_next": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 24 + [vp],
-    "mava_rware_step": [i32] * 9 + [vp, vp, u64, u32, vp, u32, i32] + [vp] * 20 + [vp],
-    "mava_rware_step_real_next": [i32] * 9 + [vp, vp, u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
-    "mava_connector_step": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 19 + [vp],
-    "mava_connector_step_real_next": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 22 + [vp],
-    "mava_cleaner_step": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 18 + [vp],
-    "mava_cleaner_step_real_next": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
-    "mava_smax_step": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 20 + [vp],
-    "mava_smax_step_real_next": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
-    "mava_spread_step": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 17 + [vp],
-    "mava_spread_step_real_next": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
+    "mava_lbf_step": [i32] * 9 + [u64, u32, vp, u32, i32] + [vp] * 24 + [vp],
+    "mava_rware_step": [i32] * 9 + [vp, vp, u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
+    "mava_connector_step": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 22 + [vp],
+    "mava_cleaner_step": [i32] * 5 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
+    "mava_smax_step": [i32] * 3 + [u64, u64] + [i32] * 3 + [u64, u32, vp, u32, i32] + [vp] * 23 + [vp],
+    "mava_spread_step": [i32] * 4 + [u64, u32, vp, u32, i32] + [vp] * 21 + [vp],
     "mava_rec_q_step_f32": [vp, i32, i32, vp, vp, vp, vp, vp, i32, f32, u64, u32, u32, vp, vp, vp],
     "mava_replay_add_f32": [i32] * 6 + [vp] * 16 + [vp],
     "mava_replay_sample_f32": [i32] * 5 + [u32, i32, i32, i32, u64, u32] + [vp] * 17 + [vp],
@@ -91,13 +82,8 @@ _SIGNATURES = {
     "mava_sac_q_loss_f32": [i32] * 3 + [vp] * 8 + [f32, f32] + [vp] * 4 + [i32, vp],
     "mava_sac_actor_grad_f32": [i32] * 4 + [f32] + [vp] * 9 + [i32, i32, i32, f32, f32] + [vp] * 3 + [i32, vp],
     "mava_sac_alpha_loss_f32": [i32, i32, vp, vp, f32, vp, vp, vp],
-    "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18 + [vp, vp, f32, f32, vp],
-    "mava_rollout_ff_tail_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
-                                + [vp, vp, f32, f32, vp, vp, vp, vp],
-    "mava_rollout_ff_x16_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
-                               + [vp, vp, f32, f32, vp, vp, vp, vp, vp, vp],
-    "mava_rollout_ff_records16_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
-                                     + [vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
+                           + [vp, vp, f32, f32] + [vp] * 7 + [vp],
     "mava_rollout_carry": [i32, i32, i32, i32, lng, i32, vp, vp, vp, vp, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],

@@ -17,7 +17,7 @@ void mava_set_error(const char* fmt, ...) {
 
 extern "C" const char* mava_last_error(void) { return g_err; }
 
-extern "C" int mava_abi_version(void) { return 3; }  // 3: round-3 signatures (mava_ctx handle instead of process-wide setters)
+extern "C" int mava_abi_version(void) { return 4; }  // 4: one entry point per operation (optional outputs are trailing arguments that may be null)
 
 // ---- context handle (ctx.h) -------------------------------------------------------------------------------------------
 enum { CTX_MATMUL_MODE = 0, CTX_CRITIC_AGGREGATION = 1, CTX_GAE_VARIANT = 2, CTX_POLICY_VARIANT = 3, CTX_H2_LAUNCHES = 4, CTX_TRAIN_VARIANT = 5, CTX_W8_LAUNCHES = 6, CTX_W1_SPLIT_FRESH = 7, CTX_EXACT_TILES = 8, CTX_X16_LAUNCHES = 9, CTX_X16_W8_LAUNCHES = 10, CTX_W8_DEFER_LAUNCHES = 11, CTX_W8_AHEAD_LAUNCHES = 12 };

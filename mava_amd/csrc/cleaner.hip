@@ -28,7 +28,7 @@
 //                   span is written as scalar head + aligned float4 body + scalar tail.  Divisions are multiplications
 //                   by host-computed reciprocals with one correction step (exact below 2^24).
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
-// graph.  mava_cleaner_step_real_next (the REAL instantiation of the same body) also writes the pre-reset agents_view /
+// graph.  The REAL instantiation of the same body (real_view given) also writes the pre-reset agents_view /
 // action_mask and the `terminated` flag (won or invalid; a time-limit end alone is a truncation).
 #include "env_common.h"
 
@@ -382,24 +382,24 @@ __global__ __launch_bounds__(THREADS) void cleaner_step_real_kernel(ClnArgs a, C
 
 }  // namespace
 
-static int cleaner_step_impl(const char* fn, const ClnReal* rn, int E, int A, int R, int C, int time_limit, uint64_t seed,
-                             uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos,
-                             uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                             int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
-                             hipStream_t s) {
+extern "C" int mava_cleaner_step(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t,
+                                 const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid,
+                                 int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                 int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                 int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
+                                 int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
+                                 float* real_view, uint8_t* real_mask, uint8_t* terminated, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXA && R >= 3 && R <= MAXS && C >= 3 && C <= MAXS, 0,
-                 "%s: bad shape E=%d A=%d R=%d C=%d (1 <= A <= %d, 3 <= R, C <= %d)", fn, E, A, R, C, MAXA, MAXS);
-  MAVA_ARG_CHECK(time_limit >= 1, 1, "%s: bad scenario time_limit=%d (time_limit >= 1)", fn, time_limit);
-  MAVA_ARG_CHECK((long)E * A * R * C * NCH < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
+                 "mava_cleaner_step: bad shape E=%d A=%d R=%d C=%d (1 <= A <= %d, 3 <= R, C <= %d)", E, A, R, C, MAXA, MAXS);
+  MAVA_ARG_CHECK(time_limit >= 1, 1, "mava_cleaner_step: bad scenario time_limit=%d (time_limit >= 1)", time_limit);
+  MAVA_ARG_CHECK((long)E * A * R * C * NCH < (1L << 31), 3, "mava_cleaner_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(pos && grid && step_count && run_return && run_length && ep_return && ep_length && agents_view &&
                      global_state && action_mask && obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_cleaner_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
+                 "mava_cleaner_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_cleaner_step: a step needs the (E, A) action array");
   ClnArgs a;
   a.E = E; a.A = A; a.R = R; a.C = C; a.time_limit = time_limit;
   a.inv_c = 1.0f / (float)C; a.inv_rc = 1.0f / (float)(R * C); a.inv_a = 1.0f / (float)A;
@@ -412,43 +412,18 @@ static int cleaner_step_impl(const char* fn, const ClnReal* rn, int E, int A, in
   a.obs_step_count = obs_step_count; a.reward = reward; a.done = done; a.info_return = info_return;
   a.info_length = info_length; a.info_terminal = info_terminal; a.info_won = is_reset ? nullptr : info_won;
   a.action = action;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 0 || n_real == 3, 7,
+                 "mava_cleaner_step: real_view, real_mask and terminated go together (all three or none)");
+  if (n_real == 0) {
     hipLaunchKernelGGL(cleaner_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
-                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
-    hipLaunchKernelGGL(cleaner_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask), 8,
+                   "mava_cleaner_step: real_view / real_mask must not alias agents_view / action_mask");
+    const ClnReal rn = {real_view, real_mask, terminated};
+    hipLaunchKernelGGL(cleaner_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_cleaner_step(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t,
-                                 const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos, uint8_t* grid,
-                                 int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                 int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                 int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                                 int32_t* info_length, uint8_t* info_terminal, uint8_t* info_won, const int32_t* action,
-                                 hipStream_t s) {
-  return cleaner_step_impl("mava_cleaner_step", nullptr, E, A, R, C, time_limit, seed, t, t_base, env_offset, is_reset, pos,
-                           grid, step_count, run_return, run_length, ep_return, ep_length, agents_view, global_state,
-                           action_mask, obs_step_count, reward, done, info_return, info_length, info_terminal, info_won,
-                           action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_cleaner_step_real_next(int E, int A, int R, int C, int time_limit, uint64_t seed, uint32_t t,
-                                           const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* pos,
-                                           uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length,
-                                           float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                                           uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                           float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                                           uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
-                                           uint8_t* terminated, hipStream_t s) {
-  const ClnReal rn = {real_view, real_mask, terminated};
-  return cleaner_step_impl("mava_cleaner_step_real_next", &rn, E, A, R, C, time_limit, seed, t, t_base, env_offset,
-                           is_reset, pos, grid, step_count, run_return, run_length, ep_return, ep_length, agents_view,
-                           global_state, action_mask, obs_step_count, reward, done, info_return, info_length, info_terminal,
-                           info_won, action, s);
 }

@@ -22,7 +22,7 @@
 //                   be 16-byte aligned, so each row starts with up to three scalar stores to reach alignment and ends
 //                   with up to three.  The only divisions are by the constants 5 and 3.
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
-// graph.  mava_connector_step_real_next (the REAL instantiation of the same body) also writes the pre-reset
+// graph.  The REAL instantiation of the same body (real_view given) also writes the pre-reset
 // agents_view / action_mask and the `terminated` flag (nobody can move; a time-limit end alone is a truncation).
 #include "env_common.h"
 
@@ -396,26 +396,26 @@ __global__ __launch_bounds__(THREADS) void connector_step_real_kernel(ConArgs a,
 
 }  // namespace
 
-static int connector_step_impl(const char* fn, const ConReal* rn, int E, int A, int G, int time_limit, uint64_t seed,
-                               uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* head,
-                               int32_t* target, uint8_t* connected, uint8_t* grid, int32_t* step_count, float* run_return,
-                               int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                               float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward,
-                               uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                               const int32_t* action, hipStream_t s) {
+extern "C" int mava_connector_step(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
+                                   uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
+                                   uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length,
+                                   float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                                   uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                                   float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
+                                   float* real_view, uint8_t* real_mask, uint8_t* terminated, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXA && G >= 3 && G <= MAXG, 0,
-                 "%s: bad shape E=%d A=%d G=%d (1 <= A <= %d, 3 <= G <= %d)", fn, E, A, G, MAXA, MAXG);
+                 "mava_connector_step: bad shape E=%d A=%d G=%d (1 <= A <= %d, 3 <= G <= %d)", E, A, G, MAXA, MAXG);
   MAVA_ARG_CHECK(2 * A <= G * G - 2 && time_limit >= 1, 1,
-                 "%s: bad scenario num_agents=%d grid_size=%d time_limit=%d (2 A <= G G - 2, time_limit >= 1)", fn, A, G,
+                 "mava_connector_step: bad scenario num_agents=%d grid_size=%d time_limit=%d (2 A <= G G - 2, time_limit >= 1)", A, G,
                  time_limit);
-  MAVA_ARG_CHECK((long)E * A * G * G * NCH < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
+  MAVA_ARG_CHECK((long)E * A * G * G * NCH < (1L << 31), 3, "mava_connector_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(head && target && connected && grid && step_count && run_return && run_length && ep_return && ep_length &&
                      agents_view && global_state && action_mask && obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_connector_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
+                 "mava_connector_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_connector_step: a step needs the (E, A) action array");
   ConArgs a;
   a.E = E; a.A = A; a.G = G; a.time_limit = time_limit;
   a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.t = t; a.t_base = t_base; a.env_offset = env_offset;
@@ -427,43 +427,18 @@ static int connector_step_impl(const char* fn, const ConReal* rn, int E, int A, 
   a.info_length = info_length; a.info_terminal = info_terminal; a.action = action;
   ConTable tab;
   for (int i = 0; i <= MAXA; ++i) tab.rel[i] = i <= A ? (float)i / (float)A : 0.0f;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 0 || n_real == 3, 7,
+                 "mava_connector_step: real_view, real_mask and terminated go together (all three or none)");
+  if (n_real == 0) {
     hipLaunchKernelGGL(connector_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, tab);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
-                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
-    hipLaunchKernelGGL(connector_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, tab, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask), 8,
+                   "mava_connector_step: real_view / real_mask must not alias agents_view / action_mask");
+    const ConReal rn = {real_view, real_mask, terminated};
+    hipLaunchKernelGGL(connector_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, tab, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_connector_step(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                                   uint32_t env_offset, int is_reset, int32_t* head, int32_t* target, uint8_t* connected,
-                                   uint8_t* grid, int32_t* step_count, float* run_return, int32_t* run_length,
-                                   float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                                   uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                   float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                                   hipStream_t s) {
-  return connector_step_impl("mava_connector_step", nullptr, E, A, G, time_limit, seed, t, t_base, env_offset, is_reset,
-                             head, target, connected, grid, step_count, run_return, run_length, ep_return, ep_length,
-                             agents_view, global_state, action_mask, obs_step_count, reward, done, info_return,
-                             info_length, info_terminal, action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_connector_step_real_next(int E, int A, int G, int time_limit, uint64_t seed, uint32_t t,
-                                             const uint32_t* t_base, uint32_t env_offset, int is_reset, int32_t* head,
-                                             int32_t* target, uint8_t* connected, uint8_t* grid, int32_t* step_count,
-                                             float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length,
-                                             float* agents_view, float* global_state, uint8_t* action_mask,
-                                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                                             float* real_view, uint8_t* real_mask, uint8_t* terminated, hipStream_t s) {
-  const ConReal rn = {real_view, real_mask, terminated};
-  return connector_step_impl("mava_connector_step_real_next", &rn, E, A, G, time_limit, seed, t, t_base, env_offset,
-                             is_reset, head, target, connected, grid, step_count, run_return, run_length, ep_return,
-                             ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done, info_return,
-                             info_length, info_terminal, action, s);
 }

@@ -17,7 +17,7 @@
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
 // graph.
 //
-// mava_lbf_step_real_next (the REAL instantiation) also writes what AutoResetWrapper keeps in
+// The REAL instantiation (real_view given) also writes what AutoResetWrapper keeps in
 // extras["real_next_obs"] (mava/wrappers/auto_reset_wrapper.py:52-101): the agents_view / action_mask of the state the
 // rules produced, BEFORE the auto-reset, and a per-env `terminated` flag (every food eaten).  The reset of ending envs
 // then moves behind one more output pass over the same LDS tile; the plain kernel is the same code with those parts
@@ -430,32 +430,33 @@ __global__ __launch_bounds__(THREADS) void lbf_step_real_kernel(LbfArgs a, LbfRe
 
 }  // namespace
 
-static int lbf_step_impl(const char* fn, const LbfReal* rn, int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
+extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
                              int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
-                             int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
-                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, hipStream_t s) {
+                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level, int32_t* food_pos,
+                             int32_t* food_level, uint8_t* food_alive, float* total_food_level, int32_t* step_count,
+                             float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length,
+                             float* agents_view, float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
+                             float* reward, uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
+                             const int32_t* action, float* real_view, uint8_t* real_mask, uint8_t* terminated,
+                             hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXA && F >= 1 && F <= MAXF && G >= 3 && G <= MAXG, 0,
-                 "%s: bad shape E=%d A=%d F=%d G=%d (1 <= A <= %d, 1 <= F <= %d, 3 <= G <= %d)", fn, E, A, F, G,
+                 "mava_lbf_step: bad shape E=%d A=%d F=%d G=%d (1 <= A <= %d, 1 <= F <= %d, 3 <= G <= %d)", E, A, F, G,
                  MAXA, MAXF, MAXG);
   MAVA_ARG_CHECK(fov >= 0 && max_agent_level >= 1 && max_agent_level <= 1000 && time_limit >= 1 &&
                      (force_coop == 0 || force_coop == 1) && (individual_rewards == 0 || individual_rewards == 1),
-                 1, "%s: bad scenario fov=%d max_agent_level=%d time_limit=%d force_coop=%d individual=%d",
-                 fn, fov, max_agent_level, time_limit, force_coop, individual_rewards);
+                 1, "mava_lbf_step: bad scenario fov=%d max_agent_level=%d time_limit=%d force_coop=%d individual=%d",
+                 fov, max_agent_level, time_limit, force_coop, individual_rewards);
   MAVA_ARG_CHECK((G - 2) * (G - 2) >= 9 * (F - 1) + 1 && G * G >= F + A, 2,
-                 "%s: a %dx%d grid cannot place %d foods and %d agents", fn, G, G, F, A);
-  MAVA_ARG_CHECK((long)E * A * (A + 3 * (F + A)) < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
+                 "mava_lbf_step: a %dx%d grid cannot place %d foods and %d agents", G, G, F, A);
+  MAVA_ARG_CHECK((long)E * A * (A + 3 * (F + A)) < (1L << 31), 3, "mava_lbf_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(agent_pos && agent_level && food_pos && food_level && food_alive && total_food_level && step_count &&
                      run_return && run_length && ep_return && ep_length && agents_view && global_state && action_mask &&
                      obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_lbf_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
+                 "mava_lbf_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_lbf_step: a step needs the (E, A) action array");
   LbfArgs a;
   a.E = E; a.A = A; a.F = F; a.G = G; a.fov = fov; a.max_level = max_agent_level; a.force_coop = force_coop;
   a.individual = individual_rewards; a.time_limit = time_limit;
@@ -467,45 +468,18 @@ static int lbf_step_impl(const char* fn, const LbfReal* rn, int E, int A, int F,
   a.ep_length = ep_length; a.agents_view = agents_view; a.global_state = global_state; a.action_mask = action_mask;
   a.obs_step_count = obs_step_count; a.reward = reward; a.done = done; a.info_return = info_return;
   a.info_length = info_length; a.info_terminal = info_terminal; a.action = action;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 0 || n_real == 3, 7,
+                 "mava_lbf_step: real_view, real_mask and terminated go together (all three or none)");
+  if (n_real == 0) {
     hipLaunchKernelGGL(lbf_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
-                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
-    hipLaunchKernelGGL(lbf_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask), 8,
+                   "mava_lbf_step: real_view / real_mask must not alias agents_view / action_mask");
+    const LbfReal rn = {real_view, real_mask, terminated};
+    hipLaunchKernelGGL(lbf_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_lbf_step(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
-                             int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
-                             int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
-                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, hipStream_t s) {
-  return lbf_step_impl("mava_lbf_step", nullptr, E, A, F, G, fov, max_agent_level, force_coop, individual_rewards, time_limit, seed, t, t_base, env_offset, is_reset,
-                       agent_pos, agent_level, food_pos, food_level, food_alive, total_food_level, step_count, run_return,
-                       run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done,
-                       info_return, info_length, info_terminal, action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_lbf_step_real_next(int E, int A, int F, int G, int fov, int max_agent_level, int force_coop,
-                             int individual_rewards, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                             uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_level,
-                             int32_t* food_pos, int32_t* food_level, uint8_t* food_alive, float* total_food_level,
-                             int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                             int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                             int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return,
-                             int32_t* info_length, uint8_t* info_terminal, const int32_t* action, float* real_view, uint8_t* real_mask,
-                                       uint8_t* terminated, hipStream_t s) {
-  const LbfReal rn = {real_view, real_mask, terminated};
-  return lbf_step_impl("mava_lbf_step_real_next", &rn, E, A, F, G, fov, max_agent_level, force_coop, individual_rewards, time_limit, seed, t, t_base, env_offset, is_reset,
-                       agent_pos, agent_level, food_pos, food_level, food_alive, total_food_level, step_count, run_return,
-                       run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done,
-                       info_return, info_length, info_terminal, action, s);
 }

@@ -1031,11 +1031,14 @@ extern "C" int mava_adv_stats_batched_f64(const float* adv, const int32_t* idx, 
   return MAVA_OK;
 }
 
-static int actor_grad_impl(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
-                           const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
-                           const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base, int Rb, int A,
-                           float clip_eps, float ent_coef, float* slab, long slab_stride, int n_slab, const uint16_t* input16,
-                           const uint32_t* input16_valid, int input16_ld, hipStream_t s) {
+// input16 / input16_valid / input16_ld: the optional f16 record of agents_view, its validity word on the device and its row
+// length in halves (include/mava_hip.h); null, null, 0 = none
+extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int din, int n_actions, const float* agents_view,
+                                       const uint8_t* action_mask, const int32_t* action, const float* old_log_prob,
+                                       const float* advantages, const double* adv_stats, const int32_t* idx, long idx_base,
+                                       int Rb, int A, float clip_eps, float ent_coef, float* slab, long slab_stride,
+                                       int n_slab, const uint16_t* input16, const uint32_t* input16_valid, int input16_ld,
+                                       hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && n_actions >= 1 && n_actions <= 32, 0,
                  "mava_ppo_actor_grad_f32: din=%d n_actions=%d unsupported", din, n_actions);
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1 && n_slab >= 1 && n_slab <= 1024 && (long)Rb * A < (1L << 31), 1,
@@ -1044,6 +1047,8 @@ static int actor_grad_impl(mava_ctx* ctx, const float* params, int din, int n_ac
                  "mava_ppo_actor_grad_f32: slab_stride too small");
   MAVA_ARG_CHECK(params && agents_view && action && old_log_prob && advantages && adv_stats && slab, 3,
                  "mava_ppo_actor_grad_f32: null pointer argument");
+  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
+                 "mava_ppo_actor_grad_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
   TrainTask tk = {};
   tk.params = params; tk.x = agents_view; tk.din = din; tk.no = n_actions; tk.xshare = 1; tk.agg = 1;
   tk.xv = pick_xv(agents_view, din); tk.A = A; tk.idx = idx; tk.idx_base = idx_base; tk.Rb = Rb;
@@ -1060,32 +1065,6 @@ static int actor_grad_impl(mava_ctx* ctx, const float* params, int din, int n_ac
   if (n_actions <= 8) return dispatch_kt<8, true>(tk, n_slab, s);
   if (n_actions <= 16) return dispatch_kt<16, true>(tk, n_slab, s);
   return dispatch_kt<32, true>(tk, n_slab, s);
-}
-
-extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int din, int n_actions,
-                                       const float* agents_view, const uint8_t* action_mask,
-                                       const int32_t* action, const float* old_log_prob,
-                                       const float* advantages, const double* adv_stats,
-                                       const int32_t* idx, long idx_base, int Rb, int A,
-                                       float clip_eps, float ent_coef, float* slab, long slab_stride,
-                                       int n_slab, hipStream_t s) {
-  return actor_grad_impl(ctx, params, din, n_actions, agents_view, action_mask, action, old_log_prob, advantages, adv_stats, idx,
-                         idx_base, Rb, A, clip_eps, ent_coef, slab, slab_stride, n_slab, nullptr, nullptr, 0, s);
-}
-
-// ... with an f16 record of agents_view, its row length in halves and its validity word on the device (include/mava_hip.h)
-extern "C" int mava_ppo_actor_grad_x16_f32(mava_ctx* ctx, const float* params, int din, int n_actions,
-                                           const float* agents_view, const uint8_t* action_mask,
-                                           const int32_t* action, const float* old_log_prob,
-                                           const float* advantages, const double* adv_stats,
-                                           const int32_t* idx, long idx_base, int Rb, int A,
-                                           float clip_eps, float ent_coef, float* slab, long slab_stride,
-                                           int n_slab, const uint16_t* input16, const uint32_t* input16_valid,
-                                           int input16_ld, hipStream_t s) {
-  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
-                 "mava_ppo_actor_grad_x16_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
-  return actor_grad_impl(ctx, params, din, n_actions, agents_view, action_mask, action, old_log_prob, advantages, adv_stats, idx,
-                         idx_base, Rb, A, clip_eps, ent_coef, slab, slab_stride, n_slab, input16, input16_valid, input16_ld, s);
 }
 
 // Continuous action head (networks.py:127-169): params = [MLP(din -> 128 -> 128 -> action_dim) | log_std(action_dim)],
@@ -1120,10 +1099,12 @@ extern "C" int mava_ppo_actor_grad_continuous_f32(const float* params, int din, 
   return dispatch_kt<16, true, true>(tk, n_slab, s);
 }
 
-static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
-                            const float* old_value, const float* targets, const int32_t* idx, long idx_base, int Rb, int A,
-                            float clip_eps, float vf_coef, float* slab, long slab_stride, int n_slab, const uint16_t* input16,
-                            const uint32_t* input16_valid, int input16_ld, hipStream_t s) {
+// input16 / input16_valid / input16_ld: the optional f16 copy of critic_input, likewise
+extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input, int x_share,
+                                        const float* old_value, const float* targets, const int32_t* idx, long idx_base,
+                                        int Rb, int A, float clip_eps, float vf_coef, float* slab, long slab_stride,
+                                        int n_slab, const uint16_t* input16, const uint32_t* input16_valid, int input16_ld,
+                                        hipStream_t s) {
   MAVA_ARG_CHECK(din >= 1 && x_share >= 1, 0, "mava_ppo_critic_grad_f32: din=%d x_share=%d", din, x_share);
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1 && n_slab >= 1 && n_slab <= 1024 && (long)Rb * A < (1L << 31), 1,
                  "mava_ppo_critic_grad_f32: Rb=%d A=%d n_slab=%d", Rb, A, n_slab);
@@ -1131,6 +1112,8 @@ static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const f
                  "mava_ppo_critic_grad_f32: slab_stride too small");
   MAVA_ARG_CHECK(params && critic_input && old_value && targets && slab, 3,
                  "mava_ppo_critic_grad_f32: null pointer argument");
+  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
+                 "mava_ppo_critic_grad_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
   TrainTask tk = {};
   tk.params = params; tk.x = critic_input; tk.din = din; tk.no = 1; tk.xshare = x_share; tk.agg = 1;
   if (mava_ctx_critic_aggregation(ctx) && A > 1 && A <= 8 && x_share == A) {  // input row of index p is row p itself
@@ -1148,26 +1131,4 @@ static int critic_grad_impl(mava_ctx* ctx, const float* params, int din, const f
   if (ctx != nullptr) ctx->w1_fresh[1] = 0;  // one-shot whichever kernel takes the launch (the exact-f32 one does not read the copy)
   if (rc <= 0) return rc;
   return dispatch_kt<1, false>(tk, n_slab, s);
-}
-
-extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input,
-                                        int x_share, const float* old_value, const float* targets,
-                                        const int32_t* idx, long idx_base, int Rb, int A,
-                                        float clip_eps, float vf_coef, float* slab, long slab_stride,
-                                        int n_slab, hipStream_t s) {
-  return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
-                          slab, slab_stride, n_slab, nullptr, nullptr, 0, s);
-}
-
-// ... with an f16 copy of critic_input and its validity word on the device (include/mava_hip.h)
-extern "C" int mava_ppo_critic_grad_x16_f32(mava_ctx* ctx, const float* params, int din, const float* critic_input,
-                                            int x_share, const float* old_value, const float* targets,
-                                            const int32_t* idx, long idx_base, int Rb, int A,
-                                            float clip_eps, float vf_coef, float* slab, long slab_stride,
-                                            int n_slab, const uint16_t* input16, const uint32_t* input16_valid,
-                                            int input16_ld, hipStream_t s) {
-  MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
-                 "mava_ppo_critic_grad_x16_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
-  return critic_grad_impl(ctx, params, din, critic_input, x_share, old_value, targets, idx, idx_base, Rb, A, clip_eps, vf_coef,
-                          slab, slab_stride, n_slab, input16, input16_valid, input16_ld, s);
 }

@@ -72,12 +72,12 @@ struct RolloutArgs {
   float* info_return; int32_t* info_length; uint8_t* info_terminal;  // (T, E)
   float* adv; float* tgt;  // (T, E, A) or null: GAE of ff_mappo.py:112-139 in the kernel's tail
   float gamma, lam;
-  // mava_rollout_ff_tail_f32 (null otherwise): reward / done of the last step, (E, A), and the device step counter
+  // optional (null otherwise): reward / done of the last step, (E, A), and the device step counter
   float* last_reward; uint8_t* last_done; int32_t* step_counter;
-  // mava_rollout_ff_x16_f32 (null otherwise): the f16 copy of global_state, (T+1, E, A*O) with A*O % 8 == 0, and its validity
+  // optional (null otherwise): the f16 copy of global_state, (T+1, E, A*O) with A*O % 8 == 0, and its validity
   // word (see the prologue).  Last members: the offsets of everything above stay what they were.
   _Float16* state16; uint32_t* state16_valid;
-  // mava_rollout_ff_records16_f32 (null otherwise): the f16 record of agents_view, (T+1, E, A, RP) with RP = 8 ceil((A+O+1) / 8) -
+  // optional (null otherwise): the f16 record of agents_view, (T+1, E, A, RP) with RP = 8 ceil((A+O+1) / 8) -
   // the rows of the actor's x image as they are: the observation, 1.0 (the ones column that carries b1), zeros - and its
   // validity word, same protocol as state16_valid.
   _Float16* view16; uint32_t* view16_valid;
@@ -502,7 +502,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   const int wo_dr = 256 / wo_q, gs_dr = 256 / gs_q;
   const uint32_t wo_m = 65536u / (uint32_t)wo_q + 1u, gs_m = 65536u / (uint32_t)gs_q + 1u;
   // The global state of slot `slot` from the shared critic's image (actor group): its f32 record (f32_too; slot 0 came from
-  // memory and is left alone) and, with mava_rollout_ff_x16_f32, the halves themselves into state16.  The copy rides on the
+  // memory and is left alone) and, when state16 is given, the halves themselves into state16.  The copy rides on the
   // quad loop's cursors: the lane of an even quad k also moves the 16 bytes of quads k and k + 1 (A O % 8 == 0, the launcher's
   // check: a row is a whole number of such pairs and pair j / 2 of the block is piece j / 2 of the record) - one 16-byte LDS
   // read and one 16-byte store, consecutive even lanes on consecutive pieces; no cursor or factor of its own.
@@ -907,16 +907,18 @@ extern "C" int mava_debug_get_rollout_stamps(unsigned long long* out16) {
 // test can assert WHICH instantiation it checked (tests/test_gpu_learner.py).
 extern "C" int mava_debug_rollout_last_instance(void) { return g_rollout_last_instance; }
 
-static int rollout_ff_impl(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                           int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                           uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                           int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                           int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                           int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                           uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                           uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                           float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                           uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, hipStream_t s) {
+// The fused rollout (include/mava_hip.h).  Each optional group of outputs may be null on its own: last_reward / last_done
+// (and step_counter, only with them), state16 / state16_valid, view16 / view16_valid.
+extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                   float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                   uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 1 && A >= 1 && O >= 2 && T >= 1 && n_actions >= 1 && time_limit >= 1, 0,
                  "mava_rollout_ff_f32: bad shape E=%d A=%d O=%d T=%d nA=%d", E, A, O, T, n_actions);
   MAVA_ARG_CHECK(actor_params && critic_params && step_count && run_return && run_length && ep_return && ep_length &&
@@ -939,13 +941,15 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
   a.info_terminal = info_terminal;
   MAVA_ARG_CHECK((adv == nullptr) == (tgt == nullptr), 1, "mava_rollout_ff_f32: adv and tgt go together");
   a.adv = adv; a.tgt = tgt; a.gamma = gamma; a.lam = gae_lambda;
+  MAVA_ARG_CHECK((last_reward == nullptr) == (last_done == nullptr) && (last_reward != nullptr || step_counter == nullptr), 1,
+                 "mava_rollout_ff_f32: last_reward, last_done (and step_counter) go together");
   a.last_reward = last_reward; a.last_done = last_done; a.step_counter = step_counter;
-  MAVA_ARG_CHECK((state16 == nullptr) == (state16_valid == nullptr), 1, "mava_rollout_ff_x16_f32: state16 and state16_valid go together");
+  MAVA_ARG_CHECK((state16 == nullptr) == (state16_valid == nullptr), 1, "mava_rollout_ff_f32: state16 and state16_valid go together");
   MAVA_ARG_CHECK(state16 == nullptr || (critic_shared && (A * O) % 8 == 0 && (uintptr_t)state16 % 16 == 0), 2,
-                 "mava_rollout_ff_x16_f32: state16 needs the shared critic, A*O %% 8 == 0 (A*O=%d) and 16-byte alignment", A * O);
+                 "mava_rollout_ff_f32: state16 needs the shared critic, A*O %% 8 == 0 (A*O=%d) and 16-byte alignment", A * O);
   a.state16 = reinterpret_cast<_Float16*>(state16); a.state16_valid = state16_valid;
-  MAVA_ARG_CHECK((view16 == nullptr) == (view16_valid == nullptr), 1, "mava_rollout_ff_records16_f32: view16 and view16_valid go together");
-  MAVA_ARG_CHECK(view16 == nullptr || (uintptr_t)view16 % 16 == 0, 2, "mava_rollout_ff_records16_f32: view16 needs 16-byte alignment");
+  MAVA_ARG_CHECK((view16 == nullptr) == (view16_valid == nullptr), 1, "mava_rollout_ff_f32: view16 and view16_valid go together");
+  MAVA_ARG_CHECK(view16 == nullptr || (uintptr_t)view16 % 16 == 0, 2, "mava_rollout_ff_f32: view16 needs 16-byte alignment");
   a.view16 = reinterpret_cast<_Float16*>(view16); a.view16_valid = view16_valid;
   a.v16_nc = (A + O + 8) / 8; a.v16_nc_m = 65536u / (uint32_t)a.v16_nc + 1u;
   if (critic_shared) {
@@ -962,87 +966,6 @@ static int rollout_ff_impl(const float* actor_params, int n_actions, const float
   if (s1a <= 2) return launch_rollout<8, 2, 2, false>(a, s);
 #endif
   return 1;
-}
-
-extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                                   hipStream_t s) {
-  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
-                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
-                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
-                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, s);
-}
-
-// mava_rollout_ff_f32 that also leaves what the caller copied or added after it: last_reward / last_done (E, A) = reward /
-// done of step T - 1, and *step_counter += T when step_counter is not null (one replica of an update passes it; the
-// kernel itself counts from t0).
-extern "C" int mava_rollout_ff_tail_f32(const float* actor_params, int n_actions, const float* critic_params,
-                                        int critic_shared, int E, int A, int O, int T, int time_limit,
-                                        uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
-                                        uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
-                                        int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                                        float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
-                                        int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
-                                        float* last_val, float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                                        float* adv, float* tgt, float gamma, float gae_lambda, float* last_reward,
-                                        uint8_t* last_done, int32_t* step_counter, hipStream_t s) {
-  MAVA_ARG_CHECK(last_reward && last_done, 1, "mava_rollout_ff_tail_f32: null pointer argument");
-  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
-                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
-                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
-                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, nullptr, nullptr, nullptr, nullptr, s);
-}
-
-// ... that also writes the f16 copy of the shared global state and its validity word (include/mava_hip.h).  last_reward /
-// last_done may be null here (then step_counter is too).
-extern "C" int mava_rollout_ff_x16_f32(const float* actor_params, int n_actions, const float* critic_params,
-                                       int critic_shared, int E, int A, int O, int T, int time_limit,
-                                       uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
-                                       uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
-                                       int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                                       float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
-                                       int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
-                                       float* last_val, float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                                       float* adv, float* tgt, float gamma, float gae_lambda, float* last_reward,
-                                       uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                                       uint32_t* state16_valid, hipStream_t s) {
-  MAVA_ARG_CHECK((last_reward == nullptr) == (last_done == nullptr) && (last_reward != nullptr || step_counter == nullptr), 1,
-                 "mava_rollout_ff_x16_f32: last_reward, last_done (and step_counter) go together");
-  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
-                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
-                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
-                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, state16, state16_valid, nullptr, nullptr, s);
-}
-
-// ... and / or the f16 record of agents_view with its own validity word (include/mava_hip.h): each pair may be null on its own.
-extern "C" int mava_rollout_ff_records16_f32(const float* actor_params, int n_actions, const float* critic_params,
-                                             int critic_shared, int E, int A, int O, int T, int time_limit,
-                                             uint64_t policy_seed, uint64_t env_seed, uint32_t t0, uint32_t row_offset,
-                                             uint32_t env_offset, int reward_mode, int32_t* step_count, float* run_return,
-                                             int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                                             float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
-                                             int32_t* action, float* value, float* reward, float* log_prob, uint8_t* done,
-                                             float* last_val, float* info_return, int32_t* info_length,
-                                             uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                                             float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                                             uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid,
-                                             hipStream_t s) {
-  MAVA_ARG_CHECK((last_reward == nullptr) == (last_done == nullptr) && (last_reward != nullptr || step_counter == nullptr), 1,
-                 "mava_rollout_ff_records16_f32: last_reward, last_done (and step_counter) go together");
-  return rollout_ff_impl(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed,
-                         t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length,
-                         agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done,
-                         last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward,
-                         last_done, step_counter, state16, state16_valid, view16, view16_valid, s);
 }
 
 // The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of the four observation

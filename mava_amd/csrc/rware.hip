@@ -25,7 +25,7 @@
 //                   the consecutive features (no division by a run-time width per element), then all threads the masks
 //                   and the advanced state: every store instruction covers consecutive addresses.
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
-// graph.  mava_rware_step_real_next (the REAL instantiation of the same body) also writes the pre-reset agents_view /
+// graph.  The REAL instantiation of the same body (real_view given) also writes the pre-reset agents_view /
 // action_mask and the `terminated` flag (a collision in collision mode "terminate"; a time-limit end is a truncation).
 #include "env_common.h"
 
@@ -497,45 +497,45 @@ extern "C" int mava_debug_set_rware_stamps(unsigned long long* p) {
   return MAVA_OK;
 }
 
-static int rware_step_impl(const char* fn, const RwReal* rn, int E, int A, int S, int R, int H, int W, int sensor_range,
-                           int time_limit, int collision_terminates, const uint32_t* highway_rows,
-                           const int32_t* shelf_home, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                           uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_dir,
-                           int32_t* agent_carry, int32_t* shelf_pos, int32_t* request_queue, int32_t* step_count,
-                           float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length,
-                           float* agents_view, float* global_state, uint8_t* action_mask, int32_t* obs_step_count,
-                           float* reward, uint8_t* done, float* info_return, int32_t* info_length,
-                           uint8_t* info_terminal, const int32_t* action, hipStream_t s) {
+extern "C" int mava_rware_step(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit,
+                               int collision_terminates, const uint32_t* highway_rows, const int32_t* shelf_home,
+                               uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
+                               int32_t* agent_pos, int32_t* agent_dir, int32_t* agent_carry, int32_t* shelf_pos,
+                               int32_t* request_queue, int32_t* step_count, float* run_return, int32_t* run_length,
+                               float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                               uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                               float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
+                               float* real_view, uint8_t* real_mask, uint8_t* terminated, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXA && S >= 2 && S <= MAXS && H >= 2 && H <= MAXH && W >= 2 && W <= MAXW, 0,
-                 "%s: bad shape E=%d A=%d S=%d H=%d W=%d (1 <= A <= %d, 2 <= S <= %d, H <= %d, W <= %d)", fn, E, A, S,
+                 "mava_rware_step: bad shape E=%d A=%d S=%d H=%d W=%d (1 <= A <= %d, 2 <= S <= %d, H <= %d, W <= %d)", E, A, S,
                  H, W, MAXA, MAXS, MAXH, MAXW);
   MAVA_ARG_CHECK(R >= 1 && R <= MAXR && R < S && sensor_range >= 1 && sensor_range <= MAXSR && time_limit >= 1 &&
                      (collision_terminates == 0 || collision_terminates == 1) && A <= H * W,
-                 1, "%s: bad scenario request_queue_size=%d (1 .. min(%d, S - 1)) sensor_range=%d (1 .. %d) "
-                 "time_limit=%d collision_terminates=%d num_agents=%d", fn, R, MAXR, sensor_range, MAXSR, time_limit,
+                 1, "mava_rware_step: bad scenario request_queue_size=%d (1 .. min(%d, S - 1)) sensor_range=%d (1 .. %d) "
+                 "time_limit=%d collision_terminates=%d num_agents=%d", R, MAXR, sensor_range, MAXSR, time_limit,
                  collision_terminates, A);
-  MAVA_ARG_CHECK(highway_rows && shelf_home, 2, "%s: null layout (highway_rows, shelf_home are host arrays)", fn);
+  MAVA_ARG_CHECK(highway_rows && shelf_home, 2, "mava_rware_step: null layout (highway_rows, shelf_home are host arrays)");
   RwLayout lay;
   for (int y = 0; y < MAXH; ++y) lay.hw[y] = y < H ? highway_rows[y] : 0u;
   for (int i = 0; i < MAXS; ++i) lay.home[i] = 0;
   for (int i = 0; i < S; ++i) {
     const int c = shelf_home[i];
     MAVA_ARG_CHECK(c >= 0 && c < H * W && (i == 0 || c > shelf_home[i - 1]) && !((lay.hw[c / W] >> (c % W)) & 1u), 2,
-                   "%s: bad layout: shelf_home[%d]=%d must be an increasing non-highway cell of the %dx%d grid", fn, i,
+                   "mava_rware_step: bad layout: shelf_home[%d]=%d must be an increasing non-highway cell of the %dx%d grid", i,
                    c, H, W);
     lay.home[i] = (uint16_t)c;
   }
-  MAVA_ARG_CHECK(((lay.hw[H - 1] >> (W / 2 - 1)) & 3u) == 3u, 2, "%s: bad layout: the goal cells must be highways", fn);
+  MAVA_ARG_CHECK(((lay.hw[H - 1] >> (W / 2 - 1)) & 3u) == 3u, 2, "mava_rware_step: bad layout: the goal cells must be highways");
   const int C = (2 * sensor_range + 1) * (2 * sensor_range + 1);
   MAVA_ARG_CHECK((long)E * A * (A + HEAD + CELL * C) < (1L << 31) && (long)E * S < (1L << 31), 3,
-                 "%s: E=%d exceeds 32-bit indexing", fn, E);
+                 "mava_rware_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(agent_pos && agent_dir && agent_carry && shelf_pos && request_queue && step_count && run_return &&
                      run_length && ep_return && ep_length && agents_view && global_state && action_mask && obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_rware_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
+                 "mava_rware_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_rware_step: a step needs the (E, A) action array");
   RwArgs a;
   a.E = E; a.A = A; a.S = S; a.R = R; a.H = H; a.W = W; a.sr = sensor_range; a.time_limit = time_limit;
   a.terminate = collision_terminates;
@@ -547,50 +547,18 @@ static int rware_step_impl(const char* fn, const RwReal* rn, int E, int A, int S
   a.action_mask = action_mask; a.obs_step_count = obs_step_count; a.reward = reward; a.done = done;
   a.info_return = info_return; a.info_length = info_length; a.info_terminal = info_terminal; a.action = action;
   a.stamps = g_rware_stamps;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 0 || n_real == 3, 7,
+                 "mava_rware_step: real_view, real_mask and terminated go together (all three or none)");
+  if (n_real == 0) {
     hipLaunchKernelGGL(rware_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, lay);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
-                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
-    hipLaunchKernelGGL(rware_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, lay, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask), 8,
+                   "mava_rware_step: real_view / real_mask must not alias agents_view / action_mask");
+    const RwReal rn = {real_view, real_mask, terminated};
+    hipLaunchKernelGGL(rware_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, lay, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_rware_step(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit,
-                               int collision_terminates, const uint32_t* highway_rows, const int32_t* shelf_home,
-                               uint64_t seed, uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset,
-                               int32_t* agent_pos, int32_t* agent_dir, int32_t* agent_carry, int32_t* shelf_pos,
-                               int32_t* request_queue, int32_t* step_count, float* run_return, int32_t* run_length,
-                               float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                               uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                               float* info_return, int32_t* info_length, uint8_t* info_terminal, const int32_t* action,
-                               hipStream_t s) {
-  return rware_step_impl("mava_rware_step", nullptr, E, A, S, R, H, W, sensor_range, time_limit, collision_terminates,
-                         highway_rows, shelf_home, seed, t, t_base, env_offset, is_reset, agent_pos, agent_dir,
-                         agent_carry, shelf_pos, request_queue, step_count, run_return, run_length, ep_return, ep_length,
-                         agents_view, global_state, action_mask, obs_step_count, reward, done, info_return, info_length,
-                         info_terminal, action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_rware_step_real_next(int E, int A, int S, int R, int H, int W, int sensor_range, int time_limit,
-                                         int collision_terminates, const uint32_t* highway_rows,
-                                         const int32_t* shelf_home, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                                         uint32_t env_offset, int is_reset, int32_t* agent_pos, int32_t* agent_dir,
-                                         int32_t* agent_carry, int32_t* shelf_pos, int32_t* request_queue,
-                                         int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                         int32_t* ep_length, float* agents_view, float* global_state,
-                                         uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                         float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                                         const int32_t* action, float* real_view, uint8_t* real_mask,
-                                         uint8_t* terminated, hipStream_t s) {
-  const RwReal rn = {real_view, real_mask, terminated};
-  return rware_step_impl("mava_rware_step_real_next", &rn, E, A, S, R, H, W, sensor_range, time_limit,
-                         collision_terminates, highway_rows, shelf_home, seed, t, t_base, env_offset, is_reset, agent_pos,
-                         agent_dir, agent_carry, shelf_pos, request_queue, step_count, run_return, run_length, ep_return,
-                         ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done, info_return,
-                         info_length, info_terminal, action, s);
 }

@@ -22,7 +22,7 @@
 // -ffp-contract=fast, under which a product may be fused into a following sum, so every product that feeds a sum passes
 // through rounded(); distances stay squared and every division is a multiplication by a reciprocal from the host's table.
 // Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays from a captured
-// graph.  mava_smax_step_real_next (the REAL instantiation of the same body) also writes the pre-reset agents_view /
+// graph.  The REAL instantiation of the same body (real_view given) also writes the pre-reset agents_view /
 // action_mask and the `terminated` flag (a side wiped out; a time-limit end alone is a truncation).
 #include "env_common.h"
 
@@ -344,25 +344,27 @@ bool types_ok(uint64_t types, int n) {
 
 }  // namespace
 
-static int smax_step_impl(const char* fn, const SmaxReal* rn, int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types,
-                          int time_limit, int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t,
-                          const uint32_t* t_base, uint32_t env_offset, int is_reset, float* pos, float* health, int32_t* cd,
-                          int32_t* last_action, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                          int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                          int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
-                          uint8_t* info_terminal, uint8_t* info_won, const int32_t* action, hipStream_t s) {
+extern "C" int mava_smax_step(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit,
+                              int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t,
+                              const uint32_t* t_base, uint32_t env_offset, int is_reset, float* pos, float* health,
+                              int32_t* cd, int32_t* last_action, int32_t* step_count, float* run_return,
+                              int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
+                              float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward,
+                              uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
+                              uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
+                              uint8_t* terminated, hipStream_t s) {
   MAVA_ARG_CHECK(E >= 0 && A >= 1 && A <= MAXSIDE && Ne >= 1 && Ne <= MAXSIDE, 0,
-                 "%s: bad shape E=%d A=%d Ne=%d (1 <= A, Ne <= %d)", fn, E, A, Ne, MAXSIDE);
-  MAVA_ARG_CHECK(time_limit >= 1, 1, "%s: bad scenario time_limit=%d (time_limit >= 1)", fn, time_limit);
-  MAVA_ARG_CHECK(types_ok(ally_types, A) && types_ok(enemy_types, Ne), 2, "%s: a unit type nibble is not below %d", fn, NT);
-  MAVA_ARG_CHECK((long)E * A * (A + BLK * (A + Ne - 1) + OWN) < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
+                 "mava_smax_step: bad shape E=%d A=%d Ne=%d (1 <= A, Ne <= %d)", E, A, Ne, MAXSIDE);
+  MAVA_ARG_CHECK(time_limit >= 1, 1, "mava_smax_step: bad scenario time_limit=%d (time_limit >= 1)", time_limit);
+  MAVA_ARG_CHECK(types_ok(ally_types, A) && types_ok(enemy_types, Ne), 2, "mava_smax_step: a unit type nibble is not below %d", NT);
+  MAVA_ARG_CHECK((long)E * A * (A + BLK * (A + Ne - 1) + OWN) < (1L << 31), 3, "mava_smax_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(pos && health && cd && last_action && step_count && run_return && run_length && ep_return && ep_length &&
                      agents_view && global_state && action_mask && obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_smax_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A) action array", fn);
+                 "mava_smax_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_smax_step: a step needs the (E, A) action array");
   SmaxArgs a;
   a.E = E; a.Na = A; a.Ne = Ne; a.time_limit = time_limit;
   a.see_enemy_actions = see_enemy_actions ? 1 : 0; a.walls_cause_death = walls_cause_death ? 1 : 0;
@@ -383,44 +385,18 @@ static int smax_step_impl(const char* fn, const SmaxReal* rn, int E, int A, int 
   a.obs_step_count = obs_step_count; a.reward = reward; a.done = done; a.info_return = info_return;
   a.info_length = info_length; a.info_terminal = info_terminal; a.info_won = is_reset ? nullptr : info_won;
   a.action = action;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 0 || n_real == 3, 7,
+                 "mava_smax_step: real_view, real_mask and terminated go together (all three or none)");
+  if (n_real == 0) {
     hipLaunchKernelGGL(smax_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask), 8,
-                   "%s: real_view / real_mask must not alias agents_view / action_mask", fn);
-    hipLaunchKernelGGL(smax_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask), 8,
+                   "mava_smax_step: real_view / real_mask must not alias agents_view / action_mask");
+    const SmaxReal rn = {real_view, real_mask, terminated};
+    hipLaunchKernelGGL(smax_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_smax_step(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit,
-                              int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                              uint32_t env_offset, int is_reset, float* pos, float* health, int32_t* cd, int32_t* last_action,
-                              int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                              int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                              int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
-                              uint8_t* info_terminal, uint8_t* info_won, const int32_t* action, hipStream_t s) {
-  return smax_step_impl("mava_smax_step", nullptr, E, A, Ne, ally_types, enemy_types, time_limit, see_enemy_actions,
-                        walls_cause_death, seed, t, t_base, env_offset, is_reset, pos, health, cd, last_action, step_count,
-                        run_return, run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count,
-                        reward, done, info_return, info_length, info_terminal, info_won, action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_smax_step_real_next(int E, int A, int Ne, uint64_t ally_types, uint64_t enemy_types, int time_limit,
-                                        int see_enemy_actions, int walls_cause_death, uint64_t seed, uint32_t t,
-                                        const uint32_t* t_base, uint32_t env_offset, int is_reset, float* pos, float* health,
-                                        int32_t* cd, int32_t* last_action, int32_t* step_count, float* run_return,
-                                        int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                                        float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward,
-                                        uint8_t* done, float* info_return, int32_t* info_length, uint8_t* info_terminal,
-                                        uint8_t* info_won, const int32_t* action, float* real_view, uint8_t* real_mask,
-                                        uint8_t* terminated, hipStream_t s) {
-  const SmaxReal rn = {real_view, real_mask, terminated};
-  return smax_step_impl("mava_smax_step_real_next", &rn, E, A, Ne, ally_types, enemy_types, time_limit, see_enemy_actions,
-                        walls_cause_death, seed, t, t_base, env_offset, is_reset, pos, health, cd, last_action, step_count,
-                        run_return, run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count,
-                        reward, done, info_return, info_length, info_terminal, info_won, action, s);
 }

@@ -17,7 +17,7 @@
 // Bit-exactness against the model: every float expression is one rounded operation.  The file is built with
 // -ffp-contract=fast, under which a product may be fused into a following sum, so every product that feeds a sum passes
 // through rounded().  Everything is a pure function of the device state and (seed, t + *t_base, env id): the step replays
-// from a captured graph.  mava_spread_step_real_next (the REAL instantiation of the same body) also writes the pre-reset
+// from a captured graph.  The REAL instantiation of the same body (real_view given) also writes the pre-reset
 // agents_view / action_mask (and global_state, when asked for) and the `terminated` flag, which is always 0.
 #include "env_common.h"
 
@@ -228,22 +228,24 @@ __global__ __launch_bounds__(THREADS) void spread_step_real_kernel(SpreadArgs a,
 
 }  // namespace
 
-static int spread_step_impl(const char* fn, const SpreadReal* rn, int E, int A, int add_agent_id, int time_limit, uint64_t seed,
-                            uint32_t t, const uint32_t* t_base, uint32_t env_offset, int is_reset, float* agent_pos,
-                            float* landmark_pos, int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                            int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                            int32_t* obs_step_count, float* reward, uint8_t* done, float* info_return, int32_t* info_length,
-                            uint8_t* info_terminal, const float* action, hipStream_t s) {
-  MAVA_ARG_CHECK(E >= 0 && A >= MINA && A <= MAXA, 0, "%s: bad shape E=%d A=%d (%d <= A <= %d)", fn, E, A, MINA, MAXA);
-  MAVA_ARG_CHECK(time_limit >= 1, 1, "%s: bad scenario time_limit=%d (time_limit >= 1)", fn, time_limit);
-  MAVA_ARG_CHECK((long)E * A * 5 * A < (1L << 31), 3, "%s: E=%d exceeds 32-bit indexing", fn, E);
+extern "C" int mava_spread_step(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t,
+                                const uint32_t* t_base, uint32_t env_offset, int is_reset, float* agent_pos,
+                                float* landmark_pos, int32_t* step_count, float* run_return, int32_t* run_length,
+                                float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
+                                uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
+                                float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
+                                float* real_view, uint8_t* real_mask, uint8_t* terminated, float* real_state,
+                                hipStream_t s) {
+  MAVA_ARG_CHECK(E >= 0 && A >= MINA && A <= MAXA, 0, "mava_spread_step: bad shape E=%d A=%d (%d <= A <= %d)", E, A, MINA, MAXA);
+  MAVA_ARG_CHECK(time_limit >= 1, 1, "mava_spread_step: bad scenario time_limit=%d (time_limit >= 1)", time_limit);
+  MAVA_ARG_CHECK((long)E * A * 5 * A < (1L << 31), 3, "mava_spread_step: E=%d exceeds 32-bit indexing", E);
   if (E == 0) return MAVA_OK;
   MAVA_ARG_CHECK(agent_pos && landmark_pos && step_count && run_return && run_length && ep_return && ep_length && agents_view &&
                      global_state && action_mask && obs_step_count,
-                 4, "%s: null state/observation pointer", fn);
+                 4, "mava_spread_step: null state/observation pointer");
   MAVA_ARG_CHECK(is_reset || (reward && done && info_return && info_length && info_terminal), 5,
-                 "%s: null transition pointer", fn);
-  MAVA_ARG_CHECK(is_reset || action, 6, "%s: a step needs the (E, A, 2) f32 action array", fn);
+                 "mava_spread_step: null transition pointer");
+  MAVA_ARG_CHECK(is_reset || action, 6, "mava_spread_step: a step needs the (E, A, 2) f32 action array");
   SpreadArgs a;
   a.E = E; a.A = A; a.add_id = add_agent_id ? 1 : 0; a.time_limit = time_limit;
   a.inv_a = 1.0f / (float)A;
@@ -254,42 +256,18 @@ static int spread_step_impl(const char* fn, const SpreadReal* rn, int E, int A, 
   a.agents_view = agents_view; a.global_state = global_state; a.action_mask = action_mask;
   a.obs_step_count = obs_step_count; a.reward = reward; a.done = done; a.info_return = info_return;
   a.info_length = info_length; a.info_terminal = info_terminal; a.action = action;
-  if (rn == nullptr) {
+  // all three null: the plain instance; all three given: the REAL instance (which writes none of them on a reset)
+  const int n_real = (real_view != nullptr) + (real_mask != nullptr) + (terminated != nullptr);
+  MAVA_ARG_CHECK(n_real == 3 || (n_real == 0 && real_state == nullptr), 7,
+                 "mava_spread_step: real_view, real_mask and terminated go together (all three or none), real_state only with them");
+  if (n_real == 0) {
     hipLaunchKernelGGL(spread_step_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a);
   } else {
-    MAVA_ARG_CHECK(is_reset || (rn->view && rn->mask && rn->terminated), 7, "%s: null real_view / real_mask / terminated", fn);
-    MAVA_ARG_CHECK(is_reset || (rn->view != agents_view && rn->mask != action_mask && rn->state != global_state), 8,
-                   "%s: real_view / real_mask / real_state must not alias agents_view / action_mask / global_state", fn);
-    hipLaunchKernelGGL(spread_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, *rn);
+    MAVA_ARG_CHECK(is_reset || (real_view != agents_view && real_mask != action_mask && real_state != global_state), 8,
+                   "mava_spread_step: real_view / real_mask / real_state must not alias agents_view / action_mask / global_state");
+    const SpreadReal rn = {real_view, real_mask, terminated, real_state};
+    hipLaunchKernelGGL(spread_step_real_kernel, dim3(mava_cdiv(E, NE)), dim3(THREADS), 0, s, a, rn);
   }
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
-}
-
-extern "C" int mava_spread_step(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t, const uint32_t* t_base,
-                                uint32_t env_offset, int is_reset, float* agent_pos, float* landmark_pos, int32_t* step_count,
-                                float* run_return, int32_t* run_length, float* ep_return, int32_t* ep_length, float* agents_view,
-                                float* global_state, uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
-                                hipStream_t s) {
-  return spread_step_impl("mava_spread_step", nullptr, E, A, add_agent_id, time_limit, seed, t, t_base, env_offset, is_reset,
-                          agent_pos, landmark_pos, step_count, run_return, run_length, ep_return, ep_length, agents_view,
-                          global_state, action_mask, obs_step_count, reward, done, info_return, info_length, info_terminal,
-                          action, s);
-}
-
-// The same step plus the pre-reset observation and the termination flag (REAL instantiation; see the file header).
-extern "C" int mava_spread_step_real_next(int E, int A, int add_agent_id, int time_limit, uint64_t seed, uint32_t t,
-                                          const uint32_t* t_base, uint32_t env_offset, int is_reset, float* agent_pos,
-                                          float* landmark_pos, int32_t* step_count, float* run_return, int32_t* run_length,
-                                          float* ep_return, int32_t* ep_length, float* agents_view, float* global_state,
-                                          uint8_t* action_mask, int32_t* obs_step_count, float* reward, uint8_t* done,
-                                          float* info_return, int32_t* info_length, uint8_t* info_terminal, const float* action,
-                                          float* real_view, uint8_t* real_mask, uint8_t* terminated, float* real_state,
-                                          hipStream_t s) {
-  const SpreadReal rn = {real_view, real_mask, terminated, real_state};
-  return spread_step_impl("mava_spread_step_real_next", &rn, E, A, add_agent_id, time_limit, seed, t, t_base, env_offset,
-                          is_reset, agent_pos, landmark_pos, step_count, run_return, run_length, ep_return, ep_length,
-                          agents_view, global_state, action_mask, obs_step_count, reward, done, info_return, info_length,
-                          info_terminal, action, s);
 }

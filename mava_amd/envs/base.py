@@ -9,8 +9,9 @@ use - writes straight into trajectory slots owned by the learner.  The step kern
     ep_length, agents_view, global_state, action_mask, obs_step_count, reward, done, info_return, info_length,
     info_terminal, [info_won,] action, [*step_tail_args,] [real_view, real_mask, terminated, [*real_extra_keys,]] stream
 
-so `BatchedEnv.step_into` assembles it once.  A subclass states `State`, `action_dim`, `step_symbols`, `obs_dim`,
-`state_dim`, `alloc_own_state` and `step_args`, validates its scenario in `__init__` and reads it from the config in its
+(the real_* group only where `emits_real_next_obs`, null pointers when the caller passes no `real_obs`), so
+`BatchedEnv.step_into` assembles it once.  A subclass states `State`, `action_dim`, `step_symbol`, `obs_dim`, `state_dim`,
+`alloc_own_state` and `step_args`, validates its scenario in `__init__` and reads it from the config in its
 module's `make`.
 """
 from __future__ import annotations
@@ -48,12 +49,12 @@ class BatchedEnv:
     supports_fused_rollout = False  # True: the feed-forward learner may route the env to the one-launch rollout
     emits_real_next_obs = True  # step_into(real_obs=, terminated=): what rec_iql stores as next_obs / terminal
     implicit_agent_id = False  # True: no one-hot id in agents_view (system.add_agent_id is ignored)
-    reports_win = False  # True: the symbols take info_won after info_terminal, reset / step add extras["won_episode"]
-    step_tail_args: tuple = ()  # arguments of the plain symbol after `action`
-    real_extra_keys: tuple = ()  # keys of real_obs whose pointers follow `terminated` in the _real_next symbol (None if absent)
+    reports_win = False  # True: the symbol takes info_won after info_terminal, reset / step add extras["won_episode"]
+    step_tail_args: tuple = ()  # arguments of the symbol after `action`, before the real_* group
+    real_extra_keys: tuple = ()  # keys of real_obs whose pointers follow `terminated` (None if absent)
     State: type  # the state tuple: COMMON_STATE, then the fields of alloc_own_state in its order
     action_dim: int
-    step_symbols: Tuple[str, Optional[str]]  # (mava_X_step, mava_X_step_real_next)
+    step_symbol: str  # mava_X_step
 
     def __init__(self, ctor_kw: Dict[str, Any]):
         """`ctor_kw`: `dict(locals())` of the subclass constructor, taken as its first statement; `clone` builds from them."""
@@ -117,20 +118,27 @@ class BatchedEnv:
         transition into the given (E, A) / (E,) slots.  `t` is the replica's global step index (Philox counter); `t_base`
         (a device int32 word) is added to it on the device, for rollouts replayed from a captured graph.  `real_obs`
         ({"agents_view", "action_mask"}) and `terminated` (E,) u8, given together, receive the pre-reset observation
-        (AutoResetWrapper's extras["real_next_obs"]) and the termination flag (a time-limit end alone is a truncation) -
-        the `_real_next` symbol; they are not written on a reset.  `info_won` (E,) u8, optional and only where
-        `reports_win`, receives done & won (the learners do not pass it)."""
+        (AutoResetWrapper's extras["real_next_obs"]) and the termination flag (a time-limit end alone is a truncation);
+        they are not written on a reset.  `info_won` (E,) u8, optional and only where `reports_win`, receives done & won
+        (the learners do not pass it)."""
         act = self._action_ptr(action, is_reset)
         if (real_obs is None) != (terminated is None):
             raise ValueError(f"{type(self).__name__}.step_into: real_obs and terminated go together")
         if info_won is not None and not self.reports_win:
             raise ValueError(f"{type(self).__name__}.step_into: this environment reports no win")
         off = self.env_offset if env_offset is None else env_offset
-        real = () if real_obs is None else (ptr(real_obs["agents_view"]), ptr(real_obs["action_mask"]), ptr(terminated),
-                                            *(ptr(real_obs.get(k, None)) for k in self.real_extra_keys))
+        if not self.emits_real_next_obs:
+            if real_obs is not None:
+                raise ValueError(f"{type(self).__name__}.step_into: this environment emits no real next observation")
+            real = ()
+        elif real_obs is None:
+            real = (None,) * (3 + len(self.real_extra_keys))
+        else:
+            real = (ptr(real_obs["agents_view"]), ptr(real_obs["action_mask"]), ptr(terminated),
+                    *(ptr(real_obs.get(k, None)) for k in self.real_extra_keys))
         won = (ptr(info_won),) if self.reports_win else ()
         scenario, own = self.step_args(state)
-        self._call(self.step_symbols[1 if real else 0], (
+        self._call(self.step_symbol, (
             self.num_envs, self.num_agents, *scenario, self.seed & 0xFFFFFFFFFFFFFFFF, t & 0xFFFFFFFF, ptr(t_base),
             off & 0xFFFFFFFF, int(is_reset), *own, ptr(state.step_count), ptr(state.run_return), ptr(state.run_length),
             ptr(state.ep_return), ptr(state.ep_length), ptr(obs["agents_view"]), ptr(obs["global_state"]),

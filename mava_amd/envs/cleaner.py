@@ -40,7 +40,7 @@ class Cleaner(BatchedEnv):
     action_dim = NUM_ACTIONS
     implicit_agent_id = True
     reports_win = True  # info_won / extras["won_episode"]
-    step_symbols = ("mava_cleaner_step", "mava_cleaner_step_real_next")  # terminated: won or an invalid action
+    step_symbol = "mava_cleaner_step"  # terminated: won or an invalid action
 
     def __init__(self, num_envs: int, num_rows: int, num_cols: int, num_agents: int, time_limit: int = 25,
                  add_global_state: bool = False, seed: int = 42, env_offset: int = 0, device: Optional[torch.device] = None):

@@ -38,7 +38,7 @@ class Connector(BatchedEnv):
     State = ConnectorState
     action_dim = NUM_ACTIONS
     implicit_agent_id = True  # the channels encode the agent index relative to the viewer
-    step_symbols = ("mava_connector_step", "mava_connector_step_real_next")  # terminated: no agent has a legal move
+    step_symbol = "mava_connector_step"  # terminated: no agent has a legal move
 
     def __init__(self, num_envs: int, grid_size: int, num_agents: int, time_limit: int = 50, add_global_state: bool = False,
                  seed: int = 42, env_offset: int = 0, device: Optional[torch.device] = None):

@@ -36,7 +36,7 @@ LBFState = NamedTuple("LBFState", COMMON_STATE + [
 class LevelBasedForaging(BatchedEnv):
     State = LBFState
     action_dim = NUM_ACTIONS
-    step_symbols = ("mava_lbf_step", "mava_lbf_step_real_next")  # terminated: every food eaten
+    step_symbol = "mava_lbf_step"  # terminated: every food eaten
 
     def __init__(self, num_envs: int, grid_size: int, fov: int, num_agents: int, num_food: int, max_agent_level: int,
                  force_coop: bool, time_limit: int = 100, use_individual_rewards: bool = False,

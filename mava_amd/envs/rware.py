@@ -60,7 +60,7 @@ RwareState = NamedTuple("RwareState", COMMON_STATE + [
 class RobotWarehouse(BatchedEnv):
     State = RwareState
     action_dim = NUM_ACTIONS
-    step_symbols = ("mava_rware_step", "mava_rware_step_real_next")  # terminated: a collision in mode "terminate"
+    step_symbol = "mava_rware_step"  # terminated: a collision in mode "terminate"
 
     def __init__(self, num_envs: int, column_height: int, shelf_rows: int, shelf_columns: int, num_agents: int,
                  sensor_range: int, request_queue_size: int, time_limit: int = 500, collision_mode: str = "terminate",

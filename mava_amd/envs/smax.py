@@ -64,7 +64,7 @@ def _pack(types: Sequence[int]) -> int:
 class Smax(BatchedEnv):
     State = SmaxState
     reports_win = True  # info_won / extras["won_episode"]
-    step_symbols = ("mava_smax_step", "mava_smax_step_real_next")  # terminated: a side is wiped out
+    step_symbol = "mava_smax_step"  # terminated: a side is wiped out
 
     def __init__(self, num_envs: int, ally_types: Sequence[int], enemy_types: Sequence[int], time_limit: int = 100,
                  see_enemy_actions: bool = True, walls_cause_death: bool = True, attack_mode: str = "closest",

@@ -41,7 +41,7 @@ class Spread(BatchedEnv):
     State = SpreadState
     action_dim = ACTION_DIM
     continuous_actions = True  # the learners pass the stored f32 action, not an int32 index
-    step_symbols = ("mava_spread_step", "mava_spread_step_real_next")  # terminated: never (the time limit truncates)
+    step_symbol = "mava_spread_step"  # terminated: never (the time limit truncates)
     real_extra_keys = ("global_state",)  # real_obs["global_state"] (E, 1, 4A), optional: ff_masac stores it as next state
 
     def __init__(self, num_envs: int, num_agents: int = 3, time_limit: int = 25, add_agent_id: bool = False,

@@ -26,7 +26,7 @@ class SyntheticRware(BatchedEnv):
     # env to the one-launch rollout only when it declares so (any other MarlEnv steps through step_into per time step)
     supports_fused_rollout = True
     emits_real_next_obs = False
-    step_symbols = ("mava_synth_rware_step", None)
+    step_symbol = "mava_synth_rware_step"
 
     def __init__(self, num_envs: int, num_agents: int, obs_dim: int = 66, num_actions: int = 5, time_limit: int = 500,
                  add_global_state: bool = False, add_agent_id: bool = True, seed: int = 42, env_offset: int = 0,

@@ -5,8 +5,8 @@ epsilon-greedy acting steps that store Transitions in a device replay buffer (:2
 (:413-463): sample windows of sample_sequence_length + 1 steps, three recurrent passes from a zero hidden state (online
 Q on obs, online and target Q on next_obs), the double-Q TD loss, clip + Adam, then the target update.
 
-Kernels per act step: mava_rec_q_step_f32 (the whole Q network + epsilon-greedy), mava_lbf_step_real_next (the env with
-its pre-reset observation), mava_replay_add_f32.  Per train step: mava_replay_sample_f32, three forward_sequence chains
+Kernels per act step: mava_rec_q_step_f32 (the whole Q network + epsilon-greedy), the env's step with real_view / real_mask
+/ terminated (its pre-reset observation), mava_replay_add_f32.  Per train step: mava_replay_sample_f32, three forward_sequence chains
 (mava_amd/rec_networks.py; the padded sample batch is Rp single-agent "envs", identity idx), mava_q_td_loss_f32, the
 backward_sequence chain, mava_clip_adam and mava_target_update_f32.  The epsilon schedule, the buffer head and fill
 level and the train gate are host arithmetic on step counts: nothing synchronises the host per step or per epoch.

@@ -416,7 +416,7 @@ def ppo_actor_grad(params, agents_view, action_mask, action, old_log_prob, advan
     (None: exact f32).
     input16 / input16_valid: an f16 record of agents_view, (rows, RP >= din) float16 laid out as rollout_ff's view16, and the
     (1,) int32 device word that says whether it may be read: the eight-wave f16x2 kernel stages its input from the record when
-    the word reads 1 (mava_ppo_actor_grad_x16_f32); same bits either way, and no host read of the word."""
+    the word reads 1; same bits either way, and no host read of the word."""
     _req(agents_view, torch.float32, "agents_view")
     rows, din = agents_view.shape
     if (input16 is None) != (input16_valid is None):
@@ -451,11 +451,8 @@ def ppo_actor_grad(params, agents_view, action_mask, action, old_log_prob, advan
         raise ValueError("slab must be (n_slab, >= P+2)")
     args = (ctx_ptr(ctx), ptr(params), din, n_actions, ptr(agents_view), ptr(action_mask), ptr(action), ptr(old_log_prob),
             ptr(advantages), ptr(stats), ptr(idx), idx_base, Rb, A, clip_eps, ent_coef, ptr(slab), slab.shape[1], slab.shape[0])
-    if input16 is not None:
-        check(lib().mava_ppo_actor_grad_x16_f32(*args, ptr(input16), ptr(input16_valid), input16.shape[1], stream_ptr()),
-              "mava_ppo_actor_grad_x16_f32")
-        return
-    check(lib().mava_ppo_actor_grad_f32(*args, stream_ptr()), "mava_ppo_actor_grad_f32")
+    check(lib().mava_ppo_actor_grad_f32(*args, ptr(input16), ptr(input16_valid), 0 if input16 is None else input16.shape[1],
+                                        stream_ptr()), "mava_ppo_actor_grad_f32")
 
 
 def ppo_critic_grad(params, critic_input, x_share: int, old_value, targets, idx, idx_base: int, Rb: int, A: int,
@@ -464,9 +461,8 @@ def ppo_critic_grad(params, critic_input, x_share: int, old_value, targets, idx,
     """Fills slab (n_slab, stride) with partial [critic gradient | value_loss, 0] sums.  `ctx` selects the arithmetic and
     the aggregation of shared input rows (None: exact f32, aggregation on).
     input16 / input16_valid: an f16 copy of critic_input and the (1,) int32 device word that says whether it equals
-    critic_input (written by rollout_ff): the wide f16x2 critic kernel stages its input from the copy when the word reads 1
-    (mava_ppo_critic_grad_x16_f32); same bits either way, and no host read of the word.  With x_share == 1 the copy may also be
-    a (rows, RP > din) record laid out as rollout_ff's view16: the eight-wave kernel reads that one."""
+    critic_input (written by rollout_ff): the wide f16x2 critic kernel stages its input from the copy when the word reads 1;
+    same bits either way, and no host read of the word.  With x_share == 1 the copy may also be a (rows, RP > din) record laid out as rollout_ff's view16: the eight-wave kernel reads that one."""
     _req(critic_input, torch.float32, "critic_input")
     din = critic_input.shape[1]
     if (input16 is None) != (input16_valid is None):
@@ -496,11 +492,8 @@ def ppo_critic_grad(params, critic_input, x_share: int, old_value, targets, idx,
         raise ValueError("slab must be (n_slab, >= P+2)")
     args = (ctx_ptr(ctx), ptr(params), din, ptr(critic_input), x_share, ptr(old_value), ptr(targets), ptr(idx), idx_base, Rb, A,
             clip_eps, vf_coef, ptr(slab), slab.shape[1], slab.shape[0])
-    if input16 is not None:
-        check(lib().mava_ppo_critic_grad_x16_f32(*args, ptr(input16), ptr(input16_valid), input16.shape[1], stream_ptr()),
-              "mava_ppo_critic_grad_x16_f32")
-        return
-    check(lib().mava_ppo_critic_grad_f32(*args, stream_ptr()), "mava_ppo_critic_grad_f32")
+    check(lib().mava_ppo_critic_grad_f32(*args, ptr(input16), ptr(input16_valid), 0 if input16 is None else input16.shape[1],
+                                         stream_ptr()), "mava_ppo_critic_grad_f32")
 
 
 def slab_reduce2(slab: torch.Tensor, n_main: int, out_main: torch.Tensor, n_tail: int, out_tail: torch.Tensor,
@@ -527,11 +520,11 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
     """The whole rollout of one replica in one launch (mava_rollout_ff_f32).  Returns False when the library does not
     instantiate the shape - the caller then steps policy_step / env.step_into per time step.
     last_reward / last_done (E, A): also written by the launch (= reward[T-1], done[T-1]); step_counter (1,) int32:
-    advanced by T at the launch's end (mava_rollout_ff_tail_f32).
+    advanced by T at the launch's end.
     state16 (T + 1, E, 1, A * O) float16 / state16_valid (1,) int32 holding 0 or 1: the launch also writes the f16 copy of
-    global_state and whether it equals it (mava_rollout_ff_x16_f32); shared critic with A * O % 8 == 0 only.
+    global_state and whether it equals it; shared critic with A * O % 8 == 0 only.
     view16 (T + 1, E, A, RP) float16 with RP = 8 * ceil((A + O + 1) / 8) / view16_valid (1,) int32 holding 0 or 1: the f16 record of
-    agents_view - observation, 1.0, zeros - and its word (mava_rollout_ff_records16_f32); every instance."""
+    agents_view - observation, 1.0, zeros - and its word; every instance."""
     W = A + O
     _req(actor_params, torch.float32, "actor_params")
     _req(critic_params, torch.float32, "critic_params")
@@ -579,30 +572,14 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
     if view16 is not None:
         _req(view16, torch.float16, "view16", (T + 1, E, A, 8 * ((W + 8) // 8)))
         _req(view16_valid, torch.int32, "view16_valid", (1,))
-    if state16 is not None or view16 is not None:
-        name = "mava_rollout_ff_records16_f32" if view16 is not None else "mava_rollout_ff_x16_f32"
-        if last_reward is not None:
-            _req(last_reward, torch.float32, "last_reward", (E, A))
-            _req(last_done, torch.uint8, "last_done", (E, A))
-        if step_counter is not None:
-            _req(step_counter, torch.int32, "step_counter", (1,))
-        if view16 is not None:
-            rc = lib().mava_rollout_ff_records16_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16),
-                                                     ptr(state16_valid), ptr(view16), ptr(view16_valid), stream_ptr())
-        else:
-            rc = lib().mava_rollout_ff_x16_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16),
-                                               ptr(state16_valid), stream_ptr())
-    elif last_reward is None and last_done is None and step_counter is None:
-        name = "mava_rollout_ff_f32"
-        rc = lib().mava_rollout_ff_f32(*args, stream_ptr())
-    else:
-        name = "mava_rollout_ff_tail_f32"
+    if last_reward is not None or last_done is not None or step_counter is not None:
         _req(last_reward, torch.float32, "last_reward", (E, A))
         _req(last_done, torch.uint8, "last_done", (E, A))
         if step_counter is not None:
             _req(step_counter, torch.int32, "step_counter", (1,))
-        rc = lib().mava_rollout_ff_tail_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), stream_ptr())
+    rc = lib().mava_rollout_ff_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16), ptr(state16_valid),
+                                   ptr(view16), ptr(view16_valid), stream_ptr())
     if rc == 1:
         return False
-    check(rc, name)
+    check(rc, "mava_rollout_ff_f32")
     return True

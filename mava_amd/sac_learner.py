@@ -9,7 +9,7 @@ update_actor_and_alpha (:342-384), which repeats its update policy_update_delay 
 
 The networks run on the general layer path (mava_amd/generic_networks.py): GenericActor with ContinuousActionHead(
 independent_std=False) (:113-116) and GenericNet with a Dense(1) head for Q (mava/networks.py:210-235).  Kernels per act
-step: the actor's layer products, mava_sac_sample_f32, the env's _real_next symbol, mava_sac_replay_add_f32.  Per train
+step: the actor's layer products, mava_sac_sample_f32, the env's step with its real-next outputs, mava_sac_replay_add_f32.  Per train
 step: mava_sac_replay_sample_f32; the actor on next_obs, mava_sac_sample_f32, mava_sac_concat_f32 and the two target Q
 passes; mava_sac_concat_f32, the two online Q passes, mava_sac_q_loss_f32, two backward chains, mava_clip_adam over
 [q1 | q2] and mava_target_update_f32; and per actor update the actor pass, mava_sac_sample_f32, mava_sac_concat_f32, two Q

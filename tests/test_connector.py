@@ -218,7 +218,7 @@ def test_connector_step_argument_errors_without_a_gpu():
     lib = _lib.lib()
     ok = dict(E=4, A=3, G=5, tl=25)
 
-    def call(fn=lib.mava_connector_step, is_reset=1, ptrs=True, trans=False, action=None, extra=(), **kw):
+    def call(fn=lib.mava_connector_step, is_reset=1, ptrs=True, trans=False, action=None, extra=(None,) * 3, **kw):
         a = dict(ok, **kw)
         p = 16 if ptrs else None  # never dereferenced: every call below is rejected on the host
         return fn(a["E"], a["A"], a["G"], a["tl"], 1, 0, None, 0, is_reset, *([p] * 13), *([p if trans else None] * 5),
@@ -232,8 +232,12 @@ def test_connector_step_argument_errors_without_a_gpu():
     assert call(ptrs=False) <= -1000 and b"null state" in err()
     assert call(is_reset=0) <= -1000 and b"transition" in err()
     assert call(is_reset=0, trans=True) <= -1000 and b"action array" in err()
-    real = lib.mava_connector_step_real_next
-    assert call(real, A=33, extra=(None,) * 3) <= -1000 and b"mava_connector_step_real_next: bad shape" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(None,) * 3) <= -1000 and b"real_view" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()
+    # real_view / real_mask / terminated: none of them on a step reaches the later checks (the line above), one or two are
+    # rejected, all three must not alias the observation
+    assert b"real_view" not in err()
+    assert call(A=33, extra=(16, 16, 16)) <= -1000 and b"mava_connector_step: bad shape" in err()
+    for part in ((16, None, None), (None, 16, None), (None, None, 16), (16, 16, None), (16, None, 16), (None, 16, 16)):
+        assert call(is_reset=0, trans=True, action=16, extra=part) <= -1000 and b"real_view" in err()
+        assert call(is_reset=1, extra=part) <= -1000 and b"real_view" in err()
+    assert call(is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()
     assert call(E=0) == 0  # nothing to do, nothing launched

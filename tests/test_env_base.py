@@ -162,9 +162,7 @@ def test_step_into_argument_list(name, recorder):
     obs, tr, real, action, t_base = _buffers(env)
     won = torch.empty(E, dtype=torch.uint8)
     scenario, own = _scenario_and_state(name, env, st)
-    plain, real_next = {"lbf": ("mava_lbf_step", "mava_lbf_step_real_next"), "rware": ("mava_rware_step", "mava_rware_step_real_next"),
-                        "connector": ("mava_connector_step", "mava_connector_step_real_next"),
-                        "cleaner": ("mava_cleaner_step", "mava_cleaner_step_real_next")}[name]
+    symbol = f"mava_{name}_step"  # one entry point: the three real slots are always passed, None without real_obs
     p = torch.Tensor.data_ptr
 
     def want(t, off, is_reset, tb=None, with_tr=True, with_real=False, info_won=None, act=None):
@@ -173,29 +171,30 @@ def test_step_into_argument_list(name, recorder):
                 + [p(st.step_count), p(st.run_return), p(st.run_length), p(st.ep_return), p(st.ep_length)]
                 + [p(obs["agents_view"]), p(obs["global_state"]), p(obs["action_mask"]), p(obs["step_count"])] + trs
                 + ([info_won] if name == "cleaner" else []) + [act]
-                + ([p(real["real_obs"]["agents_view"]), p(real["real_obs"]["action_mask"]), p(real["terminated"])] if with_real else [])
+                + ([p(real["real_obs"]["agents_view"]), p(real["real_obs"]["action_mask"]), p(real["terminated"])] if with_real
+                   else [None, None, None])
                 + [STREAM])
 
     def last():
-        symbol, args = recorder.calls[-1]
-        return symbol, list(args)
+        sym, args = recorder.calls[-1]
+        return sym, list(args)
 
     # a reset passes no action (even when one is given) and no transition slots
     env.step_into(st, 0, obs, is_reset=True, action=action)
-    assert last() == (plain, want(0, 3, 1, with_tr=False))
+    assert last() == (symbol, want(0, 3, 1, with_tr=False))
     env.step_into(st, 0, obs, is_reset=True, **real)
-    assert last() == (real_next, want(0, 3, 1, with_tr=False, with_real=True))
+    assert last() == (symbol, want(0, 3, 1, with_tr=False, with_real=True))
     # a step; t is passed modulo 2^32, env_offset= overrides the object's, t_base is the device word
     env.step_into(st, (1 << 32) + 7, obs, action=action, **tr)
-    assert last() == (plain, want(7, 3, 0, act=p(action)))
+    assert last() == (symbol, want(7, 3, 0, act=p(action)))
     env.step_into(st, 8, obs, tr["reward"], tr["done"], tr["info_return"], tr["info_length"], tr["info_terminal"], False, 21,
                   t_base, action, **real)
-    assert last() == (real_next, want(8, 21, 0, tb=p(t_base), with_real=True, act=p(action)))
+    assert last() == (symbol, want(8, 21, 0, tb=p(t_base), with_real=True, act=p(action)))
     if name == "cleaner":
         env.step_into(st, 9, obs, action=action, info_won=won, **tr)
-        assert last() == (plain, want(9, 3, 0, info_won=p(won), act=p(action)))
+        assert last() == (symbol, want(9, 3, 0, info_won=p(won), act=p(action)))
         env.step_into(st, 9, obs, action=action, info_won=won, **tr, **real)
-        assert last() == (real_next, want(9, 3, 0, with_real=True, info_won=p(won), act=p(action)))
+        assert last() == (symbol, want(9, 3, 0, with_real=True, info_won=p(won), act=p(action)))
     else:
         with pytest.raises(ValueError, match="reports no win"):
             env.step_into(st, 9, obs, action=action, info_won=won, **tr)
@@ -215,26 +214,30 @@ def test_step_into_argument_list(name, recorder):
 
     # the allocating API goes through the same call: reset at t = 0, a step at state.t + 1 with the action as int32
     st2, ts = env.reset()
-    assert recorder.calls[-1][0] == plain and recorder.calls[-1][1][-2] is None
+    assert recorder.calls[-1][0] == symbol and recorder.calls[-1][1][-5:-1] == (None, None, None, None)
     assert ("won_episode" in ts.extras) == (name == "cleaner")
     st3, ts = env.step(st2, action.long())
-    symbol, args = recorder.calls[-1]
+    sym, args = recorder.calls[-1]
     i_t = 2 + len(scenario) + 1
-    assert symbol == plain and args[i_t] == 1 and args[i_t + 3] == 0 and int(st3.t) == 1 and int(st2.t) == 0
-    assert isinstance(args[-2], int) and args[-2] != p(action)
+    assert sym == symbol and args[i_t] == 1 and args[i_t + 3] == 0 and int(st3.t) == 1 and int(st2.t) == 0
+    assert args[-4:-1] == (None, None, None) and isinstance(args[-5], int) and args[-5] != p(action)
     assert ("won_episode" in ts.extras) == (name == "cleaner") and set(ts.extras["episode_metrics"]) == {
         "episode_return", "episode_length", "is_terminal_step"}
     if name == "cleaner":
-        assert args[-3] is not None and ts.extras["won_episode"].dtype == torch.bool
+        assert args[-6] is not None and ts.extras["won_episode"].dtype == torch.bool
 
 
 @pytest.mark.parametrize("mode", ["random", "match"])
 def test_synthetic_step_arguments(mode, recorder):
     env = _make("synthetic", reward_mode=mode)
     st = env.alloc_state()
-    obs, tr, _, action, _ = _buffers(env)
+    obs, tr, real, action, _ = _buffers(env)
     p = torch.Tensor.data_ptr
     match = int(mode == "match")
+    # no real-next outputs here: asked for, the call is refused before the library is reached
+    with pytest.raises(ValueError, match="SyntheticRware.step_into: this environment emits no real next observation"):
+        env.step_into(st, 5, obs, action=action, **tr, **real)
+    assert recorder.calls == []
 
     def want(t, is_reset, act):
         trs = [None if is_reset else p(tr[k]) for k in ("reward", "done", "info_return", "info_length", "info_terminal")]

@@ -1,6 +1,6 @@
 """The one-launch rollout's tail (csrc/rollout_h2.hip): GAE by the whole workgroup from LDS, last_reward / last_done and
-the device step counter written by the launch itself (mava_rollout_ff_tail_f32), and the slot T -> slot 0 carry launch
-(mava_rollout_carry)."""
+the device step counter written by the launch itself (mava_rollout_ff_f32's optional tail outputs), and the slot T ->
+slot 0 carry launch (mava_rollout_carry)."""
 import numpy as np
 import pytest
 import torch

@@ -204,6 +204,64 @@ def test_rollout_word_is_zero_for_an_inexact_initial_state(dev, rollout_runs):
     assert float(out["global_state"][0, 19, 0, 137]) == pytest.approx(0.1), "slot 0 of the f32 state belongs to the caller"
 
 
+# ------------------------------------------------------------------------------------------------ optional argument groups
+E_C, T_C = 32, 8  # the learner test's shape below: 32 envs x 4 agents, T = 8
+COMBOS = {"none": (False, False, False), "tail": (True, False, False), "tail+state16": (True, True, False),
+          "tail+state16+view16": (True, True, True)}
+
+
+def _run_combo(dev, pa, pc, init, tail, s16, v16):
+    from mava_amd import ops
+
+    av0, gs0, mask0 = init
+    W, AO, T, E = A + O_R, A * O_R, T_C, E_C
+    z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+    b = dict(agents_view=z((T + 1, E, A, W)), global_state=z((T + 1, E, 1, AO)), action_mask=z((T + 1, E, A, NA_R), torch.uint8),
+             obs_step_count=z((T + 1, E, A), torch.int32), action=z((T, E, A), torch.int32), value=z((T, E, A)), reward=z((T, E, A)),
+             log_prob=z((T, E, A)), done=z((T, E, A), torch.uint8), last_val=z((E, A)), info_return=z((T, E)),
+             info_length=z((T, E), torch.int32), info_terminal=z((T, E), torch.uint8), adv=z((T, E, A)), tgt=z((T, E, A)))
+    b["agents_view"][0], b["global_state"][0], b["action_mask"][0] = _t(av0, dev), _t(gs0, dev), _t(mask0, dev)
+    st = SimpleNamespace(step_count=z((E, A), torch.int32), run_return=z((E,)), run_length=z((E,), torch.int32), ep_return=z((E,)),
+                         ep_length=z((E,), torch.int32))
+    opt = {}
+    if tail:
+        opt.update(last_reward=z((E, A)), last_done=z((E, A), torch.uint8), step_counter=z((1,), torch.int32))
+    if s16:
+        opt.update(state16=z((T + 1, E, 1, AO), torch.float16), state16_valid=z((1,), torch.int32))
+    if v16:
+        opt.update(view16=z((T + 1, E, A, 8 * ((W + 8) // 8)), torch.float16), view16_valid=z((1,), torch.int32))
+    ok = ops.rollout_ff(pa, pc, n_actions=NA_R, critic_shared=True, E=E, A=A, O=O_R, T=T, time_limit=4, policy_seed=42, env_seed=7,
+                        t0=3, row_offset=0, env_offset=0, reward_mode=0, env_state=st, gamma=0.99, gae_lambda=0.95, **opt, **b)
+    torch.cuda.synchronize()
+    assert ok, "the fused rollout does not instantiate this shape"
+    return dict(b, **opt, **{f"state.{k}": v for k, v in vars(st).items()})
+
+
+@pytest.fixture(scope="module")
+def combo_runs(dev):
+    rng = np.random.default_rng(13)
+    pa = _t(po.mlp_flatten(po.init_mlp(rng, A + O_R, NA_R, 1.0)).astype(np.float32), dev)
+    pc = _t(po.mlp_flatten(po.init_mlp(rng, A * O_R, 1, 1.0)).astype(np.float32), dev)
+    raw = (rng.random((E_C, A, O_R)) < 0.2).astype(np.float32)
+    raw[:, :, :2] = rng.integers(0, 10, (E_C, A, 2)).astype(np.float32)
+    av = np.concatenate([np.broadcast_to(np.eye(A, dtype=np.float32), (E_C, A, A)), raw], axis=2)
+    init = (av, raw.reshape(E_C, 1, A * O_R), np.ones((E_C, A, NA_R), np.uint8))
+    return {name: _run_combo(dev, pa, pc, init, *flags) for name, flags in COMBOS.items()}
+
+
+@pytest.mark.parametrize("name", [n for n in COMBOS if n != "tail+state16+view16"])
+def test_rollout_optional_groups_change_no_common_output(combo_runs, name):
+    """mava_rollout_ff_f32 with each subset of its optional output groups that a caller passes - none, the tail outputs, the tail
+    and state16 - against the launch with all of them: every output both launches write is the same bit for bit."""
+    full, out = combo_runs["tail+state16+view16"], combo_runs[name]
+    assert int(full["step_counter"].item()) == T_C and int(full["state16_valid"].item()) == int(full["view16_valid"].item()) == 1
+    assert full["reward"].abs().sum().item() > 0 and full["done"].sum().item() > 0 and full["agents_view"][1:].abs().sum().item() > 0
+    assert torch.equal(full["last_reward"], full["reward"][T_C - 1]) and torch.equal(full["last_done"], full["done"][T_C - 1])
+    assert len(out) == 20 + 3 * COMBOS[name][0] + 2 * COMBOS[name][1]
+    for k, v in out.items():
+        assert torch.equal(v, full[k]), f"{k} differs from the launch with every optional group"
+
+
 # ------------------------------------------------------------------------------------------------ one learner update
 def _update_once(dev, monkeypatch, x16, U):
     from mava_amd import envs

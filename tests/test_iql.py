@@ -57,9 +57,14 @@ def test_new_entry_points_report_argument_errors():
     L = _lib.lib()
     err = lambda: L.mava_last_error()
     n = [None] * 24
-    # mava_lbf_step_real_next: the shape checks of mava_lbf_step, then the three new pointers
-    assert L.mava_lbf_step_real_next(4, 0, 1, 5, 1, 2, 0, 0, 10, 1, 0, None, 0, 0, *n, None) <= -1000
-    assert b"mava_lbf_step_real_next: bad shape" in err()
+    # mava_lbf_step: the shape checks, then the three real-next pointers - all of them or none
+    assert L.mava_lbf_step(4, 0, 1, 5, 1, 2, 0, 0, 10, 1, 0, None, 0, 0, *n, None) <= -1000
+    assert b"mava_lbf_step: bad shape" in err()
+    step = lambda action, *real: L.mava_lbf_step(4, 2, 1, 5, 1, 2, 0, 0, 10, 1, 0, None, 0, 0, *[16] * 20, action, *real, None)
+    assert step(None, None, None, None) <= -1000 and b"action array" in err()  # none of the three: the later checks are reached
+    for part in ((16, None, None), (None, 16, None), (None, None, 16), (16, 16, None), (16, None, 16), (None, 16, 16)):
+        assert step(16, *part) <= -1000 and b"real_view" in err()
+    assert step(16, 16, 16, 16) <= -1000 and b"alias" in err()
     assert L.mava_rec_q_step_f32(None, 21, 6, None, None, None, None, None, 33, 0.1, 1, 0, 0, None, None, None) <= -1000
     assert b"multiple of 32" in err()
     assert L.mava_rec_q_step_f32(None, 21, 17, None, None, None, None, None, 32, 0.1, 1, 0, 0, None, None, None) <= -1000

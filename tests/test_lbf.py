@@ -129,7 +129,8 @@ def test_lbf_step_argument_errors_without_a_gpu():
         a = dict(ok, **kw)
         p = 16 if ptrs else None  # never dereferenced: every call below is rejected on the host
         return lib.mava_lbf_step(a["E"], a["A"], a["F"], a["G"], a["fov"], a["lvl"], a["coop"], a["ind"], a["tl"], 1, 0,
-                                 None, 0, is_reset, *([p] * 15), *([p if trans else None] * 5), action, None)
+                                 None, 0, is_reset, *([p] * 15), *([p if trans else None] * 5), action, None, None, None,
+                                 None)  # no real_view / real_mask / terminated (tests/test_iql.py has them)
 
     assert call(A=17) <= -1000 and b"bad shape" in lib.mava_last_error()
     assert call(G=33) <= -1000 and call(F=0) <= -1000 and call(E=-1) <= -1000

@@ -119,7 +119,7 @@ def test_symbols_are_declared():
     names = [n for n in _lib.declared_symbols() if n.startswith("mava_mat_")]
     assert len(names) == 9
     lib = _lib.lib()
-    assert lib.mava_abi_version() == 3 and all(hasattr(lib, n) for n in names)
+    assert lib.mava_abi_version() == 4 and all(hasattr(lib, n) for n in names)
 
 
 def test_kernel_argument_refusals_need_no_gpu():

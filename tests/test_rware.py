@@ -184,7 +184,7 @@ def test_rware_step_argument_errors_without_a_gpu():
     ok = dict(E=4, A=2, S=32, R=2, H=11, W=10, sr=1, tl=500, coll=1)
 
     def call(fn=lib.mava_rware_step, is_reset=1, ptrs=True, trans=False, action=None, rows=lay.highway_rows,
-             home=lay.shelf_home, extra=(), **kw):
+             home=lay.shelf_home, extra=(None,) * 3, **kw):
         a = dict(ok, **kw)
         p = 16 if ptrs else None  # never dereferenced: every call below is rejected on the host
         hr = (C.c_uint32 * len(rows))(*rows) if rows is not None else None
@@ -205,8 +205,12 @@ def test_rware_step_argument_errors_without_a_gpu():
     assert call(ptrs=False) <= -1000 and b"null state" in err()
     assert call(is_reset=0) <= -1000 and b"transition" in err()
     assert call(is_reset=0, trans=True) <= -1000 and b"action array" in err()
-    real = lib.mava_rware_step_real_next
-    assert call(real, A=17, extra=(None,) * 3) <= -1000 and b"mava_rware_step_real_next: bad shape" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(None,) * 3) <= -1000 and b"real_view" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()
+    # real_view / real_mask / terminated: none of them on a step reaches the later checks (the line above), one or two are
+    # rejected, all three must not alias the observation
+    assert b"real_view" not in err()
+    assert call(A=17, extra=(16, 16, 16)) <= -1000 and b"mava_rware_step: bad shape" in err()
+    for part in ((16, None, None), (None, 16, None), (None, None, 16), (16, 16, None), (16, None, 16), (None, 16, 16)):
+        assert call(is_reset=0, trans=True, action=16, extra=part) <= -1000 and b"real_view" in err()
+        assert call(is_reset=1, extra=part) <= -1000 and b"real_view" in err()
+    assert call(is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()
     assert call(E=0) == 0  # nothing to do, nothing launched

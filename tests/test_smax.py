@@ -341,28 +341,29 @@ def test_step_into_argument_list(monkeypatch):
                 + [p(st.step_count), p(st.run_return), p(st.run_length), p(st.ep_return), p(st.ep_length)]
                 + [p(obs["agents_view"]), p(obs["global_state"]), p(obs["action_mask"]), p(obs["step_count"])] + trs
                 + [info_won, act]
-                + ([p(real["real_obs"]["agents_view"]), p(real["real_obs"]["action_mask"]), p(real["terminated"])] if with_real else [])
+                + ([p(real["real_obs"]["agents_view"]), p(real["real_obs"]["action_mask"]), p(real["terminated"])] if with_real
+                   else [None, None, None])
                 + [STREAM])
 
     def last():
         symbol, args = rec.calls[-1]
         return symbol, list(args)
 
-    plain, real_next = "mava_smax_step", "mava_smax_step_real_next"
+    name = "mava_smax_step"  # one entry point: the three real slots are always passed, None without real_obs
     env.step_into(st, 0, obs, is_reset=True, action=action)
-    assert last() == (plain, want(0, 3, 1, with_tr=False))
+    assert last() == (name, want(0, 3, 1, with_tr=False))
     env.step_into(st, 0, obs, is_reset=True, **real)
-    assert last() == (real_next, want(0, 3, 1, with_tr=False, with_real=True))
+    assert last() == (name, want(0, 3, 1, with_tr=False, with_real=True))
     env.step_into(st, (1 << 32) + 7, obs, action=action, **tr)
-    assert last() == (plain, want(7, 3, 0, act=p(action)))
+    assert last() == (name, want(7, 3, 0, act=p(action)))
     env.step_into(st, 8, obs, tr["reward"], tr["done"], tr["info_return"], tr["info_length"], tr["info_terminal"], False, 21,
                   t_base, action, **real)
-    assert last() == (real_next, want(8, 21, 0, tb=p(t_base), with_real=True, act=p(action)))
+    assert last() == (name, want(8, 21, 0, tb=p(t_base), with_real=True, act=p(action)))
     env.step_into(st, 9, obs, action=action, info_won=won, **tr)
-    assert last() == (plain, want(9, 3, 0, info_won=p(won), act=p(action)))
+    assert last() == (name, want(9, 3, 0, info_won=p(won), act=p(action)))
     env.step_into(st, 9, obs, action=action, info_won=won, **tr, **real)
-    assert last() == (real_next, want(9, 3, 0, with_real=True, info_won=p(won), act=p(action)))
-    assert len(last()[1]) == len(__import__("mava_amd._lib", fromlist=["_SIGNATURES"])._SIGNATURES[real_next])
+    assert last() == (name, want(9, 3, 0, with_real=True, info_won=p(won), act=p(action)))
+    assert len(last()[1]) == len(__import__("mava_amd._lib", fromlist=["_SIGNATURES"])._SIGNATURES[name])
     ptrs = [a for a in last()[1] if isinstance(a, int) and a > (1 << 16)]
     assert len(set(ptrs)) == len(ptrs) >= 22  # every pointer of a call is a different one
     n = len(rec.calls)
@@ -371,11 +372,12 @@ def test_step_into_argument_list(monkeypatch):
     assert len(rec.calls) == n
     # the allocating API goes through the same call and carries won_episode
     st2, ts = env.reset()
-    assert rec.calls[-1][0] == plain and rec.calls[-1][1][-2] is None and ts.extras["won_episode"].dtype == torch.bool
+    assert rec.calls[-1][0] == name and rec.calls[-1][1][-5:-1] == (None,) * 4 and ts.extras["won_episode"].dtype == torch.bool
     st3, ts = env.step(st2, action.long())
     symbol, args = rec.calls[-1]
     i_t = 2 + len(scenario) + 1
-    assert symbol == plain and args[i_t] == 1 and args[i_t + 3] == 0 and int(st3.t) == 1 and args[-3] is not None
+    assert symbol == name and args[i_t] == 1 and args[i_t + 3] == 0 and int(st3.t) == 1 and args[-6] is not None
+    assert args[-4:-1] == (None, None, None)
     assert ts.extras["won_episode"].dtype == torch.bool
 
 
@@ -385,7 +387,7 @@ def test_smax_step_argument_errors_without_a_gpu():
     lib = _lib.lib()
     ok = dict(E=4, A=3, Ne=4, at=0x000, et=0x3332, tl=100)
 
-    def call(fn=lib.mava_smax_step, is_reset=1, ptrs=True, trans=False, action=None, extra=(), **kw):
+    def call(fn=lib.mava_smax_step, is_reset=1, ptrs=True, trans=False, action=None, extra=(None,) * 3, **kw):
         a = dict(ok, **kw)
         p = 16 if ptrs else None  # never dereferenced: every call below is rejected on the host
         return fn(a["E"], a["A"], a["Ne"], a["at"], a["et"], a["tl"], 1, 1, 1, 0, None, 0, is_reset, *([p] * 13),
@@ -401,7 +403,11 @@ def test_smax_step_argument_errors_without_a_gpu():
     assert call(ptrs=False) <= -1000 and b"null state" in err()
     assert call(is_reset=0) <= -1000 and b"transition" in err()
     assert call(is_reset=0, trans=True) <= -1000 and b"action array" in err()
-    real = lib.mava_smax_step_real_next
-    assert call(real, A=17, extra=(None,) * 3) <= -1000 and b"mava_smax_step_real_next: bad shape" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(None,) * 3) <= -1000 and b"real_view" in err()
-    assert call(real, is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()
+    # real_view / real_mask / terminated: none of them on a step reaches the later checks (the line above), one or two are
+    # rejected, all three must not alias the observation
+    assert b"real_view" not in err()
+    assert call(A=17, extra=(16, 16, 16)) <= -1000 and b"mava_smax_step: bad shape" in err()
+    for part in ((16, None, None), (None, 16, None), (None, None, 16), (16, 16, None), (16, None, 16), (None, 16, 16)):
+        assert call(is_reset=0, trans=True, action=16, extra=part) <= -1000 and b"real_view" in err()
+        assert call(is_reset=1, extra=part) <= -1000 and b"real_view" in err()
+    assert call(is_reset=0, trans=True, action=16, extra=(16, 16, 16)) <= -1000 and b"alias" in err()

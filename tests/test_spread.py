@@ -204,3 +204,35 @@ def test_make_refuses_a_discrete_head_and_bad_shapes():
     with pytest.raises(ValueError, match="float32"):
         env._action_ptr(torch.zeros((4, 2, 3)), False)
     assert env._action_ptr(None, True) is None and env._action_ptr(torch.zeros((4, 2, 2)), False) is not None
+
+
+def test_spread_step_argument_errors_without_a_gpu():
+    from mava_amd import _lib
+
+    lib = _lib.lib()
+
+    def call(is_reset=1, ptrs=True, trans=False, action=None, real=(None,) * 4, E=4, A=3, tl=25):
+        p = 16 if ptrs else None  # never dereferenced: every call below is rejected on the host
+        return lib.mava_spread_step(E, A, 1, tl, 1, 0, None, 0, is_reset, *([p] * 11), *([p if trans else None] * 5), action,
+                                    *real, None)
+
+    err = lib.mava_last_error
+    assert call(A=9) <= -1000 and b"mava_spread_step: bad shape" in err()
+    assert call(A=1) <= -1000 and call(E=-1) <= -1000
+    assert call(tl=0) <= -1000 and b"time_limit" in err()
+    assert call(E=2**24, A=8) <= -1000 and b"32-bit" in err()
+    assert call(ptrs=False) <= -1000 and b"null state" in err()
+    assert call(is_reset=0) <= -1000 and b"transition" in err()
+    # real_view / real_mask / terminated: none of them on a step reaches the later checks, one or two are rejected (on a
+    # reset too), real_state comes only with them, and none of the four may alias the observation
+    assert call(is_reset=0, trans=True) <= -1000 and b"action array" in err() and b"real_view" not in err()
+    assert call(A=9, real=(16, 16, 16, 16)) <= -1000 and b"mava_spread_step: bad shape" in err()
+    for part in ((16, None, None), (None, 16, None), (None, None, 16), (16, 16, None), (16, None, 16), (None, 16, 16)):
+        for state in (None, 16):
+            assert call(is_reset=0, trans=True, action=16, real=(*part, state)) <= -1000 and b"real_view" in err()
+            assert call(is_reset=1, real=(*part, state)) <= -1000 and b"real_view" in err()
+    assert call(is_reset=0, trans=True, action=16, real=(None, None, None, 16)) <= -1000 and b"real_state only with them" in err()
+    assert call(is_reset=1, real=(None, None, None, 16)) <= -1000 and b"real_state only with them" in err()
+    assert call(is_reset=0, trans=True, action=16, real=(16, 16, 16, None)) <= -1000 and b"alias" in err()
+    assert call(is_reset=0, trans=True, action=16, real=(32, 48, 64, 16)) <= -1000 and b"alias" in err()
+    assert call(E=0) == 0  # nothing to do, nothing launched

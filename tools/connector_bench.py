@@ -5,7 +5,7 @@
     python tools/connector_bench.py --curve [--calls N --lr X --envs E --rollout T] [--out profiles/connector_learning_curve.json]
 
 Default mode: the device time of one env step launch, graph-replayed (20 launches per graph, warm-up, median of 5), for
-mava_connector_step and mava_connector_step_real_next at 4096 envs x con-5x5x3a and 1024 envs x con-10x10x10a, with the
+mava_connector_step without and with its real_view / real_mask / terminated outputs at 4096 envs x con-5x5x3a and 1024 envs x con-10x10x10a, with the
 compulsory bytes per launch and the GB/s they give; in the same run mava_rware_step at 4096 envs x tiny-4ag and a
 device-to-device copy of the same number of bytes as each Connector step moves.  Then env-steps/s through learn() of
 ff_mappo (network=mlp and network=cnn) and rec_mappo on con-5x5x3a.
@@ -147,6 +147,7 @@ def step_device_times(dev) -> dict:
     for scenario, E in (("con-5x5x3a", 4096), ("con-10x10x10a", 1024)):
         env, _ = envs.make(_compose("ff_mappo", scenario, "mlp", [f"arch.num_envs={E}"]), add_global_state=True, device=dev)
         G, A = env.grid_size, env.num_agents
+        # (row names, not symbols: "_real_next" = mava_connector_step with its real-next outputs; the committed profiles keep them)
         for name, real in (("connector_step", False), ("connector_step_real_next", True)):
             us = _time_step(env, real, dev)
             b = env_step_bytes(G, A, real)["total"] * E

@@ -120,6 +120,7 @@ def step_device_times(scenario: str, E: int, dev) -> dict:
                            add_global_state=True, device=dev)
     syn = envs.SyntheticRware(E, A, obs_dim=66, num_actions=5, add_global_state=True, device=dev)
     out = {}
+    # (row names, not symbols: "_real_next" = mava_rware_step with its real-next outputs; the committed profiles keep these keys)
     for name, env, real in (("rware_step", rw, False), ("rware_step_real_next", rw, True), ("lbf_step", lbf_env, False),
                             ("synth_rware_step", syn, False)):
         A = env.num_agents
