@@ -283,7 +283,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   // The env phase below writes only the HIGH plane of the x images (its observations are exact in f16): when the slot-0
   // observations loaded above are exact too, the low plane is zero for the whole rollout, and layer 1 runs two MFMAs per
   // product instead of three without reading that plane (the skipped product is exactly 0: same bits).
-  const bool x_lo = __builtin_amdgcn_readfirstlane((int)*XLF) != 0;
+  // Slot-0 observations that are NOT exact leave their low terms in the low plane, where no later observation overwrites them:
+  // only the first pass of the rollout, the one that reads slot 0, may take the low plane (the step loop clears x_lo behind it).
+  int x_lo = __builtin_amdgcn_readfirstlane((int)*XLF) != 0;
   // The validity word of an f16 record, one per launch: 1 when no block loaded a slot-0 value of the recorded array with a low
   // term - then the f32 record of slot 0 is the conversion of the halves in the image, like every later slot's.  The word holds
   // 0 or 1 on entry.  One thread per block counts itself in bits 1 .. 30, a block with a low term sets bit 31 first; the block
@@ -607,6 +609,8 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   for (int t = 0; t < T_steps; ++t) {
     const uint32_t step = t0 + (uint32_t)t;
     forward(true, true, step);
+    x_lo = 0;  // the images hold the environment's own observations from here on: high plane only (see x_lo)
+    asm volatile("" : "+s"(x_lo));  // (opaque: the loop is not peeled for it)
     const auto& a = args_here();  // (shadows the parameter for the sample phase: see args_here)
     // ---------------------------------------------------------------- S: sample, log-prob, value -> slot t
     // (the sample and observation-generation code runs on the actor group: the critic group's registers are full of
