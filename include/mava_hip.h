@@ -913,6 +913,25 @@ int mava_mat_loss_f32(int Bm, int A, int n_actions, long rows, const int32_t* id
                       float ent_coef, float vf_coef, float grad_scale, float* dlogits, float* dvalues, float* loss_partials,
                       int n_blocks, mava_stream_t s);
 
+/* ---- ff_mat, fused acting (csrc/mat_act.hip): one env step of the autoregressive decode in ONE launch, with a per-sample
+ *      key/value cache.  Equal to mava_rec_gather_t32_f32 + the encoder + A x (mava_mat_shift_onehot_f32 + the decoder +
+ *      mava_mat_sample_f32) up to the summation order of the dense products, which are plain f32 FMAs here whatever the
+ *      context's matmul mode; same masking and same Philox counters as mava_mat_sample_f32. */
+/* length of the flat vector [encoder | decoder] (mat_learner.param_spec); the kernel derives every leaf's offset from these
+ * four numbers */
+long mava_transformer_param_count(int O, int n_actions, int D, int n_block);
+/* bytes of the caller's device workspace (the decoder's key/value cache of every block of the grid) */
+size_t mava_transformer_act_workspace_bytes(int B, int A, int D, int n_block, int n_blocks);
+/* agents_view (B, A, O) row-major; mask (B, A, n_actions) u8 or NULL; action, log_prob (B, A); value (B, A) or NULL.
+ * 1 <= A <= 32, D a multiple of 32 up to 128 and of n_head, 1 <= n_actions <= 64, 1 <= O <= 1024.  workspace: at least
+ * mava_transformer_act_workspace_bytes(B, A, D, n_block, n_blocks) bytes, 16-byte aligned, never read before it is
+ * written in the same launch.  Outputs are bit-identical for any n_blocks.  Returns 1 ("not instantiated", nothing
+ * launched) when n_block > 4. */
+int mava_transformer_act_f32(const float* params, const float* agents_view, const uint8_t* mask, int B, int A, int O,
+                             int n_actions, int D, int n_head, int n_block, uint64_t seed, uint32_t step, uint32_t row_offset,
+                             int greedy, int32_t* action, float* log_prob, float* value, void* workspace,
+                             size_t workspace_bytes, int n_blocks, mava_stream_t s);
+
 /* ---- exchange step: replaces the jax.lax.pmean calls of mava/systems/ppo/ff_mappo.py:224-238
  *      (actor and critic (grads, loss_info) over the "batch" and "device" axes) for a host without torch.distributed.
  *      One process per GPU: rank 0 obtains a 128-byte id (mava_comm_unique_id) and hands it to the other ranks by any

@@ -45,6 +45,7 @@ HIP_SOURCES = [
     "rec_out_h2.hip",
     "generic_layers.hip",
     "mat.hip",
+    "mat_act.hip",
 ]
 CPP_SOURCES = ["api.cpp", "comm.cpp"]
 

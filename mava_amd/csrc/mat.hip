@@ -34,6 +34,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "mat_rows.h"
 
 namespace {
 
@@ -332,32 +333,6 @@ __global__ __launch_bounds__(256) void shift_onehot_kernel(const int32_t* __rest
   }
 }
 
-// masked logits as every Categorical of this library sees them (mlp_core.h): illegal -> -FLT_MAX; a row without a legal
-// action is uniform over its n real slots.  No per-action arrays: up to 64 actions are walked from memory again.
-struct RowLogits {
-  const float* y;       // T32 logits, already offset to (tile, lane): feature o at y[o * 32]
-  const uint8_t* mask;  // the row's n flags or null
-  int n;
-  __device__ __forceinline__ bool legal(int o) const { return mask == nullptr || mask[o] != 0; }
-  __device__ __forceinline__ float z(int o) const { return legal(o) ? y[(long)o * 32] : -FLT_MAX; }
-};
-
-struct RowStats {
-  float lse;
-  bool none;
-};
-
-__device__ __forceinline__ RowStats row_stats(const RowLogits& rl) {
-  float mx = -FLT_MAX;
-  for (int o = 0; o < rl.n; ++o) mx = fmaxf(mx, rl.z(o));
-  float se = 0.0f;
-  for (int o = 0; o < rl.n; ++o) se += expf(rl.z(o) - mx);
-  RowStats st;
-  st.none = (mx == -FLT_MAX);
-  st.lse = st.none ? logf((float)rl.n) : mx + logf(se);
-  return st;
-}
-
 struct SampleTask {
   int B, A, agent, n;
   const float* logits;
@@ -376,29 +351,9 @@ __global__ __launch_bounds__(256) void mat_sample_kernel(SampleTask tk) {
   const long row = (long)b * tk.A + tk.agent;
   RowLogits rl = {tk.logits + (row >> 5) * tk.n * 32 + (row & 31), tk.mask ? tk.mask + row * tk.n : nullptr, tk.n};
   const RowStats st = row_stats(rl);
-  int a = 0;
-  float best = -FLT_MAX;
-  if (tk.greedy) {
-    for (int o = 0; o < tk.n; ++o) {
-      const float z = rl.z(o);
-      if (z > best) { best = z; a = o; }
-    }
-  } else {
-    const uint32_t gid = tk.row_offset + (uint32_t)row;
-    for (int c = 0; c < (tk.n + 3) / 4; ++c) {
-      const Philox4 rnd = philox4x32_10(gid, tk.step, (uint32_t)c, 0x504f4c49u, tk.seed_lo, tk.seed_hi);
-      for (int k = 0; k < 4; ++k) {
-        const int o = 4 * c + k;
-        if (o < tk.n) {
-          const uint32_t w = k == 0 ? rnd.x : (k == 1 ? rnd.y : (k == 2 ? rnd.z : rnd.w));
-          const float sc = rl.z(o) - logf(-logf(u01_open(w)));
-          if (sc > best) { best = sc; a = o; }
-        }
-      }
-    }
-  }
+  const int a = row_draw(rl, tk.greedy, tk.row_offset + (uint32_t)row, tk.step, tk.seed_lo, tk.seed_hi);
   tk.action[row] = a;
-  tk.log_prob[row] = (st.none ? 0.0f : rl.z(a)) - st.lse;
+  tk.log_prob[row] = row_log_prob(rl, st, a);
 }
 
 struct LossTask {

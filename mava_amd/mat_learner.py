@@ -9,7 +9,9 @@ Network (discrete actions).  One sample is one (t, env) pair with its A agents i
   decoder:  x = LN(GELU(Dense_nobias(shifted one-hot)));  n_block x { x = LN(x + Attn(x, x, causal));
             x = LN(rep + Attn(q = rep, kv = x, causal));  x = LN(x + MLP(x)) };  logits = Dense(nA)(LN(GELU(Dense(x))))
 Acting is autoregressive: A decoder passes per env step, pass i samples agent i (mava_mat_sample_f32) and the next pass
-sees its action in the shifted one-hot.  Training is one teacher-forced pass.
+sees its action in the shifted one-hot.  Training is one teacher-forced pass.  With network.acting=fused an env step is one
+launch instead (mava_transformer_act_f32, csrc/mat_act.hip: the same network with a key/value cache, f32 dense products
+whatever system.matmul_mode); the bootstrap value and training stay on the layer-wise tapes.
 
 Every matrix is T32 with the E * A (acting) or Bm * A (minibatch) agent rows padded to a multiple of 32; the dense products
 are GenericNet._dense / _xty (mava_rec_dense_f32 / mava_rec_xty_f32: system.matmul_mode, grad_scale), everything between
@@ -39,6 +41,7 @@ from .ppo_learner import PPOLearner
 from .types import LearnerState, TimeStep
 
 MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
+ACTING = ("layerwise", "fused")  # network.acting: MATPass.act launches layer by layer, or csrc/mat_act.hip once per env step
 
 
 def check_supported(*, num_agents: int, n_actions: int, n_embd: int, n_head: int, continuous: bool, world: int,
@@ -294,9 +297,17 @@ class _Graph:
 class MATPass(_Graph):
     """Encoder and decoder tapes for B samples, with the gathered observations and the shifted one-hot as inputs."""
 
-    def __init__(self, net: MATNet, B: int, device, training: bool, ctx):
+    def __init__(self, net: MATNet, B: int, device, training: bool, ctx, acting: str = "layerwise"):
         super().__init__(net, B, device, training, ctx)
         O, nA, D = net.O, net.nA, net.D
+        if acting not in ACTING:
+            raise MavaHipError(f"ff_mat: network.acting must be one of {ACTING}, got {acting!r}")
+        self.acting = acting
+        self._act_ws: Optional[torch.Tensor] = None  # the fused step's workspace (its key/value cache), once per pass shape
+        if acting == "fused":
+            self._act_blocks = max(1, min(256, -(-self.B // max(1, 32 // net.A))))  # one block per group of samples
+            need = int(lib().mava_transformer_act_workspace_bytes(self.B, net.A, D, net.n_block, self._act_blocks))
+            self._act_ws = torch.zeros(max(need, 16), dtype=torch.uint8, device=device)
         self.Np = pad32(nA + 1)
         self.obs = self.buf(O)
         self.onehot = self.buf(nA + 1, ld=self.Np)
@@ -351,7 +362,11 @@ class MATPass(_Graph):
     def act(self, flat: torch.Tensor, agents_view: torch.Tensor, mask: torch.Tensor, action: torch.Tensor, log_prob: torch.Tensor,
             seed: int, step: int, row_offset: int, greedy: bool, value_out: Optional[torch.Tensor] = None) -> None:
         """One env step for the B samples of (B, A, O) agents_view: encoder, then A decoder passes; pass i samples agent i.
-        Launches: 1 + len(enc) + A * (2 + len(dec)) (+ 1 copy of the values)."""
+        Launches: 1 + len(enc) + A * (2 + len(dec)) (+ 1 copy of the values); one when the pass was built with
+        acting="fused" and the kernel takes the network's depth."""
+        if self.acting == "fused" and self._act_fused(flat, agents_view, mask, action, log_prob, seed, step, row_offset, greedy,
+                                                      value_out):
+            return
         self.gather_obs(agents_view, self.B)
         self.encode(flat)
         if value_out is not None:
@@ -361,6 +376,15 @@ class MATPass(_Graph):
             self.decode(flat)
             launch("mat_sample", lib().mava_mat_sample_f32, self.B, self.A, i, self.net.nA, ptr(self.logits.t), ptr(mask),
                    seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action), ptr(log_prob), stream_ptr())
+
+
+    def _act_fused(self, flat, agents_view, mask, action, log_prob, seed, step, row_offset, greedy, value_out) -> bool:
+        """The env step as one launch; False when the kernel has no instance for this depth (the caller runs layer by layer)."""
+        net, L = self.net, lib()
+        rc = launch("mat_act", L.mava_transformer_act_f32, ptr(flat), ptr(agents_view), ptr(mask), self.B, net.A, net.O, net.nA, net.D,
+                    net.H, net.n_block, seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action),
+                    ptr(log_prob), ptr(value_out), ptr(self._act_ws), self._act_ws.numel(), self._act_blocks, stream_ptr(), ok=(0, 1))
+        return rc == 0
 
 
 class _MATPolicy:
@@ -384,15 +408,15 @@ class _MATPolicy:
 class MATActor:
     """actor_network of the system: apply(params, observation) -> a policy over the joint action (E, A)."""
 
-    def __init__(self, net: MATNet, ctx, device):
-        self.net, self.ctx, self.device = net, ctx, device
+    def __init__(self, net: MATNet, ctx, device, acting: str = "layerwise"):
+        self.net, self.ctx, self.device, self.acting = net, ctx, device, acting
         self._passes: Dict[int, MATPass] = {}
         self._flat = torch.zeros(net.num_params, device=device)
         self._calls = 0
 
     def pass_for(self, B: int) -> MATPass:
         if B not in self._passes:
-            p = MATPass(self.net, B, self.device, False, self.ctx)
+            p = MATPass(self.net, B, self.device, False, self.ctx, self.acting)
             p.idx[:B].copy_(torch.arange(B, dtype=torch.int32))
             self._passes[B] = p
         return self._passes[B]
@@ -417,6 +441,7 @@ class MATLearner(PPOLearner):
     def __init__(self, env, config, device: Optional[torch.device] = None):
         net = config.network
         self.D, self.H, self.n_block = int(net.get("n_embd", 64)), int(net.get("n_head", 1)), int(net.get("n_block", 1))
+        self.acting = str(net.get("acting", "layerwise"))
         super().__init__(env, config, False, device)
         s, self.rep = config.system, self.reps[0]
         self.O = self.Oa  # (image observations: their flat row)
@@ -428,7 +453,7 @@ class MATLearner(PPOLearner):
         self._alloc_params([(self.net, s.actor_lr)])
         d = self.device
         self.Bm = self.T * self.E // self.M  # (t, env) samples per minibatch
-        self.actor_network = MATActor(self.net, self.ctx, d)
+        self.actor_network = MATActor(self.net, self.ctx, d, self.acting)
         self.roll = self.actor_network.pass_for(self.E)
         self.train = MATPass(self.net, self.Bm, d, True, self.ctx)
         rows = self.train.rows
@@ -446,6 +471,8 @@ class MATLearner(PPOLearner):
                         update_batch_size=self.U)
         if self.n_block < 1:
             raise ValueError(f"network.n_block must be >= 1, got {self.n_block}")
+        if self.acting not in ACTING:
+            raise MavaHipError(f"ff_mat: network.acting must be one of {ACTING}, got {self.acting!r}")
         if (self.T * self.E) % self.M:
             raise ValueError("rollout_length * num_envs must be divisible by num_minibatches")
 

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """ff_mat measurements (bench.py's headline is not involved).
 
-    python tools/mat_bench.py [--envs 1024] [--out profiles/mat_bench.json]
-    python tools/mat_bench.py --curve [--out profiles/mat_learning_curve.json]
+    python tools/mat_bench.py [--envs 1024] [--acting layerwise|fused] [--out profiles/mat_bench_fused.json]
+    python tools/mat_bench.py --curve [--acting fused] [--out profiles/mat_learning_curve_fused.json]
 
 Default mode: ms per update and library calls per update of ff_mat at its defaults on env=rware tiny-4ag, ff_mappo
 (update_batch_size 1) in the same run for scale, and the per-launch HIP-event times of the attention and LayerNorm kernels at
-rows = envs * 4 next to the bytes each launch moves.
+rows = envs * 4 next to the bytes each launch moves.  Without --acting both settings of network.acting run in the same
+process (the layer-wise path is the yardstick of the fused one), with the fused step's per-launch time, the library calls per
+update the code implies and the fused step's maximum differences from the float64 model on the shapes of
+tests/test_gpu_mat_fused_act.py; with --acting only that setting runs.
 --curve: the learning run of tests/test_gpu_mat_learning.py - ff_mat and ff_mappo (network=mlp) for the same number of
 env-steps and the same seed - with the bar the test holds ff_mat to.
 """
@@ -39,7 +42,8 @@ def _setup(system: str, dev, c=CURVE):
     cfg = compose(f"default_{system}", [f"env={c['env']}", f"env/scenario={c['scenario']}", f"arch.num_envs={c['envs']}",
                                         f"system.rollout_length={c['rollout']}", "system.update_batch_size=1", f"system.seed={c['seed']}",
                                         f"system.actor_lr={c['lr']}", f"system.critic_lr={c['lr']}",
-                                        f"arch.num_eval_episodes={c['eval_envs']}"])
+                                        f"arch.num_eval_episodes={c['eval_envs']}"]
+                  + ([f"network.acting={c['acting']}"] if system == "ff_mat" and c.get("acting") else []))
     cfg.system.num_updates_per_eval = c["updates_per_call"]
     env, eval_env = envs.make(cfg, add_global_state=system == "ff_mappo", device=dev)
     learn, actor_network, state = mod.learner_setup(env, (c["seed"], c["seed"] + 2, c["seed"] + 3), cfg, device=dev)
@@ -69,11 +73,12 @@ def learning_curve(system: str, dev, log=None, c=CURVE) -> dict:
     return {"curve": curve, "final_sem": sem}
 
 
-def learning_run(dev, log=None) -> dict:
+def learning_run(dev, log=None, acting=None) -> dict:
     """Both systems on CURVE, and the bar: ff_mat's gain must reach BAR_FACTOR of ff_mappo's."""
-    out = {"config": CURVE, "bar_factor": BAR_FACTOR}
+    c = CURVE if acting is None else dict(CURVE, acting=acting)
+    out = {"config": c, "bar_factor": BAR_FACTOR}
     for system in ("ff_mappo", "ff_mat"):
-        out[system] = learning_curve(system, dev, log)
+        out[system] = learning_curve(system, dev, log, c)
         cv = out[system]["curve"]
         out[system]["gain"] = cv[-1][2] - cv[0][2]
     out["bar"] = BAR_FACTOR * out["ff_mappo"]["gain"]
@@ -103,8 +108,10 @@ class _CallCounter:
             setattr(self.lib, k, fn)
 
 
-def update_cost(system: str, envs_: int, dev, steps: int = 3) -> dict:
+def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None) -> dict:
     c = dict(CURVE, env="rware", scenario="tiny-4ag", envs=envs_, rollout=128, updates_per_call=1, lr=2.5e-4, eval_envs=32)
+    if acting is not None:
+        c["acting"] = acting
     cfg, learn, state, _ = _setup(system, dev, c)
     state = learn(state).learner_state  # warm-up (and ff_mappo's graph capture needs two calls)
     state = learn(state).learner_state
@@ -119,9 +126,52 @@ def update_cost(system: str, envs_: int, dev, steps: int = 3) -> dict:
         learn(state)
         torch.cuda.synchronize()
     L = learn.learner
-    return {"system": system, "envs": envs_, "agents": L.A, "rollout_length": L.T, "ms_per_update": round(1e3 * sorted(times)[len(times) // 2], 3),
+    extra = {}
+    if system == "ff_mat":
+        extra["acting"] = L.acting
+        # what MATPass.act launches layer by layer (its docstring), and what an update must then cost with the fused step:
+        # T x (1 act + 1 env step) + the bootstrap's gather and encoder + the training calls
+        per_act = 1 + len(L.roll.enc) + L.A * (2 + len(L.roll.dec))
+        by = cc.by
+        rollout_calls = by.get("mava_transformer_act_f32", 0) + by.get(L.rep.env.step_symbol, 0) if L.acting == "fused" else L.T * (per_act + 1)
+        extra["layerwise_calls_per_act"] = per_act
+        extra["library_calls_outside_rollout"] = cc.n - rollout_calls
+        if L.acting == "fused":
+            extra["fused_act_us_per_launch"] = _fused_step_us(L)
+    return {"system": system, "envs": envs_, **extra, "agents": L.A, "rollout_length": L.T, "ms_per_update": round(1e3 * sorted(times)[len(times) // 2], 3),
             "ms_per_update_all": [round(1e3 * t, 3) for t in times], "env_steps_per_s": round(L.T * L.E / sorted(times)[len(times) // 2]),
             "library_calls_per_update": cc.n, "library_calls_by_symbol": dict(sorted(cc.by.items(), key=lambda kv: -kv[1]))}
+
+
+def _fused_step_us(L, reps: int = 30) -> float:
+    """Median HIP-event time (us, includes the Python launch cost) of one fused acting step of the learner's rollout pass."""
+    rep = L.rep
+    act = lambda: L.roll.act(L.p, rep.agents_view[0], rep.action_mask[0], rep.action[0], rep.log_prob[0], L.seed, 0, 0, False,
+                             value_out=rep.value[0])
+    act()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record()
+        act()
+        b.record()
+    torch.cuda.synchronize()
+    return round(sorted(1e3 * a.elapsed_time(b) for a, b in ev)[reps // 2], 2)
+
+
+def fused_accuracy(dev) -> dict:
+    """The fused step against the float64 model on the shapes of tests/test_gpu_mat_fused_act.py (that module's cases and
+    comparison): rows compared and the maximum log-prob and value differences over the sampled and the greedy run."""
+    from tests import test_gpu_mat_fused_act as t
+
+    cases, worst_lp, worst_v = [], 0.0, 0.0
+    for shape in t.SHAPES + [t.MANY_GROUPS]:
+        for greedy in (False, True):
+            n, rows, e, v = t.measure(dev, shape, greedy)
+            cases.append({"shape": list(shape), "greedy": greedy, "rows_compared": n, "rows": rows, "max_log_prob_error": e,
+                          "max_value_error": v})
+            worst_lp, worst_v = max(worst_lp, e), max(worst_v, v)
+    return {"bound": 1e-5, "max_log_prob_error": worst_lp, "max_value_error": worst_v, "cases": cases}
 
 
 def kernel_times(rows: int, dev, A: int = 4, D: int = 64, H: int = 1, reps: int = 30) -> dict:
@@ -164,6 +214,8 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--curve", action="store_true")
+    ap.add_argument("--acting", choices=("layerwise", "fused"), default=None, help="network.acting of ff_mat (default: the "
+                    "config's in --curve mode, both settings otherwise)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -171,11 +223,22 @@ def main() -> None:
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     if args.curve:
-        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True))
+        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True), acting=args.acting)
     else:
+        settings = [args.acting] if args.acting else ["layerwise", "fused"]
+        results = [update_cost("ff_mat", args.envs, dev, acting=a) for a in settings] + [update_cost("ff_mappo", args.envs, dev)]
         out = {"device": torch.cuda.get_device_name(0), "workload": f"env=rware tiny-4ag x {args.envs} envs, defaults",
-               "results": [update_cost("ff_mat", args.envs, dev), update_cost("ff_mappo", args.envs, dev)],
-               "kernel_times": kernel_times(args.envs * 4, dev)}
+               "results": results, "kernel_times": kernel_times(args.envs * 4, dev)}
+        by = {r.get("acting"): r for r in results if r["system"] == "ff_mat"}
+        if "fused" in by:
+            f = by["fused"]
+            # T x (1 act + 1 env step) + everything the layer-wise update calls outside its rollout (bootstrap + training)
+            outside = by["layerwise"]["library_calls_outside_rollout"] if "layerwise" in by else f["library_calls_outside_rollout"]
+            f["library_calls_implied"] = 2 * f["rollout_length"] + outside
+            f["library_calls_as_implied"] = f["library_calls_per_update"] == f["library_calls_implied"]
+            out["fused_accuracy"] = fused_accuracy(dev)
+        if len(by) == 2:
+            out["fused_speedup_per_update"] = round(by["layerwise"]["ms_per_update"] / by["fused"]["ms_per_update"], 2)
     print(json.dumps(out))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
