@@ -932,6 +932,44 @@ int mava_transformer_act_f32(const float* params, const float* agents_view, cons
                              int greedy, int32_t* action, float* log_prob, float* value, void* workspace,
                              size_t workspace_bytes, int n_blocks, mava_stream_t s);
 
+/* ---- ff_mat, continuous action head (csrc/mat.hip, csrc/mat_act.hip): the decoder reads the previous agents' action
+ *      vectors instead of one-hots and emits the means of Independent(TanhTransformed(Normal(mean, softplus(log_std) +
+ *      min_scale))) with one log_std vector (csrc/tanh_normal.h); 1 <= action_dim <= 16, A <= 32, no action mask. */
+/* The decoder's input, T32 (rows x n_pad), n_pad = ceil32(action_dim): row (b, 0) = 0, row (b, i) = action[sample, i - 1]
+ * for 1 <= i <= known, zero rows after that, zero features past action_dim.  action: (samples, A, action_dim) f32;
+ * sample = idx[b], or b when idx is NULL. */
+int mava_transformer_shift_action_f32(const float* action, const int32_t* idx, int B, int A, int action_dim, int known,
+                                      long rows, int n_pad, float* out, mava_stream_t s);
+/* One step of the autoregressive decode: agent `agent` of each of the B samples draws a = tanh(mean + scale * eps) from its
+ * T32 means row (rows x action_dim), eps from the Philox counter (row_offset + b * A + agent, step, dim / 2, "TNSA") as
+ * mava_seq_sample_continuous_f32 has it, eps = 0 when greedy; writes action[b, agent, :] and log_prob[b, agent] (the
+ * log-prob of the action written, summed over dimensions) and nothing else. */
+int mava_transformer_sample_continuous_f32(int B, int A, int agent, int action_dim, float min_scale, const float* mean,
+                                           const float* log_std, uint64_t seed, uint32_t step, uint32_t row_offset, int greedy,
+                                           float* action, float* log_prob, mava_stream_t s);
+/* mava_mat_loss_f32 with the actor part of mava_seq_actor_loss_continuous_f32: row b * A + j reads the (samples, A[,
+ * action_dim]) trajectory arrays at agent row er = idx[b] * A + j; the entropy sample of that row uses the Philox counter
+ * (row_offset + er, ent_step, dim / 2, "TNEN").  Writes dmean (T32, times grad_scale), dvalues (rows, times grad_scale,
+ * includes vf_coef), zero on padding rows, loss_partials (n_blocks, 3) = [actor_loss, entropy, value_loss] partial means and
+ * dlog_std_partials (n_blocks, action_dim): the log_std gradient's per-block sums, already times sigmoid(log_std) and
+ * without grad_scale. */
+int mava_transformer_loss_continuous_f32(int Bm, int A, int action_dim, float min_scale, long rows, const int32_t* idx,
+                                         const float* mean, const float* log_std, const float* values, const float* action,
+                                         const float* old_log_prob, const float* advantages, const float* old_value,
+                                         const float* targets, const double* adv_stats, int n_stats, float clip_eps,
+                                         float ent_coef, float vf_coef, uint64_t seed, uint32_t ent_step, uint32_t row_offset,
+                                         float grad_scale, float* dmean, float* dvalues, float* loss_partials,
+                                         float* dlog_std_partials, int n_blocks, mava_stream_t s);
+/* length of the continuous network's flat vector: mava_transformer_param_count at n_actions = action_dim (act_dense has a
+ * bias row where the discrete network has the start token's) plus the action_dim entries of decoder/log_std at the end */
+long mava_transformer_param_count_continuous(int O, int action_dim, int D, int n_block);
+/* mava_transformer_act_f32 for the continuous head: action (B, A, action_dim) f32; the same Philox counters as
+ * mava_transformer_sample_continuous_f32; the workspace is mava_transformer_act_workspace_bytes'. */
+int mava_transformer_act_continuous_f32(const float* params, const float* agents_view, int B, int A, int O, int action_dim,
+                                        int D, int n_head, int n_block, float min_scale, uint64_t seed, uint32_t step,
+                                        uint32_t row_offset, int greedy, float* action, float* log_prob, float* value,
+                                        void* workspace, size_t workspace_bytes, int n_blocks, mava_stream_t s);
+
 /* ---- exchange step: replaces the jax.lax.pmean calls of mava/systems/ppo/ff_mappo.py:224-238
  *      (actor and critic (grads, loss_info) over the "batch" and "device" axes) for a host without torch.distributed.
  *      One process per GPU: rank 0 obtains a 128-byte id (mava_comm_unique_id) and hands it to the other ranks by any

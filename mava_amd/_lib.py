@@ -127,9 +127,17 @@ _SIGNATURES = {
     "mava_transformer_param_count": [i32, i32, i32, i32],
     "mava_transformer_act_workspace_bytes": [i32, i32, i32, i32, i32],
     "mava_transformer_act_f32": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, u32, u32, i32, vp, vp, vp, vp, C.c_size_t, i32, vp],
+    "mava_transformer_shift_action_f32": [vp, vp, i32, i32, i32, i32, lng, i32, vp, vp],
+    "mava_transformer_sample_continuous_f32": [i32, i32, i32, i32, f32, vp, vp, u64, u32, u32, i32, vp, vp, vp],
+    "mava_transformer_loss_continuous_f32": [i32, i32, i32, f32, lng, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u32,
+                                             u32, f32, vp, vp, vp, vp, i32, vp],
+    "mava_transformer_param_count_continuous": [i32, i32, i32, i32],
+    "mava_transformer_act_continuous_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, u64, u32, u32, i32, vp, vp, vp, vp, C.c_size_t,
+                                            i32, vp],
 }
 _RESTYPES = {"mava_last_error": C.c_char_p, "mava_rec_step_pack_bytes": C.c_long, "mava_ppo_finish_workspace_bytes": C.c_size_t,
-             "mava_transformer_param_count": C.c_long, "mava_transformer_act_workspace_bytes": C.c_size_t}
+             "mava_transformer_param_count": C.c_long, "mava_transformer_act_workspace_bytes": C.c_size_t,
+             "mava_transformer_param_count_continuous": C.c_long}
 
 
 def declared_symbols():

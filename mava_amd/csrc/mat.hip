@@ -2,7 +2,8 @@
 // the decoder.  The products themselves (q / k / v / output projections, the MLPs, the heads) are mava_rec_dense_f32 /
 // mava_rec_xty_f32 launches; this file adds attention over the A agents of a sample, LayerNorm with a learned scale and a
 // residual input, GELU, the decoder's shifted one-hot input, the per-agent sampling step of the autoregressive decode and
-// the PPO loss over agent rows.
+// the PPO loss over agent rows; for the continuous head (tanh-normal, tanh_normal.h) the shifted action vectors, the
+// per-agent sampling step and the loss (mava_transformer_*_f32 at the end of this file).
 //
 // Rows.  Every matrix is T32 (generic_layers.hip): element (row, f) of a (rows x N) matrix at
 // ((row / 32) * N + f) * 32 + row % 32, `rows` a multiple of 32.  Agent row b * A + j belongs to sample b; rows past B * A
@@ -35,6 +36,7 @@
 
 #include "common.h"
 #include "mat_rows.h"
+#include "tanh_normal.h"
 
 namespace {
 
@@ -44,6 +46,7 @@ constexpr int MAX_D = 128;
 constexpr int LDQ = MAX_D + 1;   // LDS row stride of a staged (rows x hd) tile: rows fall on different banks
 constexpr int LDP = MAX_A + 1;   // LDS row stride of the (rows x A) score tile
 constexpr int MAX_ACT = 64;
+constexpr int MAX_DIM = 16;       // action dimensions of the continuous head (the limit of the other continuous kernels)
 constexpr double LN_EPS = 1e-6;  // flax.linen.LayerNorm default epsilon
 
 __device__ __forceinline__ long t32(long row, long f, long N) { return ((row >> 5) * N + f) * 32 + (row & 31); }
@@ -454,6 +457,176 @@ __global__ __launch_bounds__(256) void mat_loss_kernel(LossTask tk) {
         ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
 }
 
+// ---- continuous head ------------------------------------------------------------------------------------------------------
+// s[b, 0] = 0; s[b, i] = action[b, i - 1] (d features) for 1 <= i <= known; zero rows after that, zero features past d
+__global__ __launch_bounds__(256) void shift_action_kernel(const float* __restrict__ action, const int32_t* __restrict__ idx, int B,
+                                                           int A, int d, int known, long rows, int Np, float* __restrict__ out) {
+  const long total = rows * Np, valid = (long)B * A;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long tile = e / ((long)Np * 32);
+    const int rem = (int)(e - tile * Np * 32);
+    const int f = rem >> 5;
+    const long row = tile * 32 + (rem & 31);
+    float v = 0.0f;
+    if (row < valid && f < d) {
+      const long b = row / A;
+      const int i = (int)(row - b * A);
+      if (i >= 1 && i - 1 < known) {
+        const long sb = idx != nullptr ? idx[b] : b;
+        v = action[(sb * A + (i - 1)) * d + f];
+      }
+    }
+    out[e] = v;
+  }
+}
+
+struct SampleContTask {
+  int B, A, agent, d;
+  float min_scale;
+  const float *mean, *log_std;
+  uint32_t seed_lo, seed_hi, step, row_offset;
+  int greedy;
+  float *action, *log_prob;
+};
+
+// agent `agent` of every sample: a = tanh(mean + scale * eps), eps on the Philox stream of mava_seq_sample_continuous_f32
+// (counter (row_offset + row, step, dim / 2, "TNSA")), 0 when greedy; the log-prob is that of the action written
+__global__ __launch_bounds__(256) void mat_sample_cont_kernel(SampleContTask tk) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= tk.B) return;
+  const long row = (long)b * tk.A + tk.agent;
+  const float* mp = tk.mean + (row >> 5) * tk.d * 32 + (row & 31);
+  const uint32_t gid = tk.row_offset + (uint32_t)row;
+  float lp = 0.0f;
+  for (int o = 0; o < tk.d; ++o) {
+    const float mean = mp[(long)o * 32];
+    const float sc = tn::scale_of(tk.log_std[o], tk.min_scale);
+    const float eps = tk.greedy ? 0.0f : tn::noise(gid, tk.step, o, tn::STREAM_SAMPLE, tk.seed_lo, tk.seed_hi);
+    const float a = tanhf(fmaf(sc, eps, mean));
+    lp += tn::log_prob(a, mean, sc).lp;
+    tk.action[row * tk.d + o] = a;
+  }
+  tk.log_prob[row] = lp;
+}
+
+struct LossContTask {
+  int Bm, A, d;
+  float min_scale;
+  long rows;
+  const int32_t* idx;
+  const float *mean, *log_std, *values, *action;
+  const float *old_log_prob, *adv, *old_value, *targets;
+  const double* stats;
+  int n_stats;
+  float clip_eps, ent_coef, vf_coef, grad_scale;
+  uint32_t seed_lo, seed_hi, ent_step, row_offset;
+  float *dmean, *dvalues, *partials, *dls_partials;
+};
+
+// mat_loss_kernel's row walk, value loss and padding handling with the actor part of mava_seq_actor_loss_continuous_f32
+// (rec_gru.hip): a thread owns all d action dimensions of its agent row
+template <int NO>
+__global__ __launch_bounds__(256) void mat_loss_cont_kernel(LossContTask tk) {
+  __shared__ float red[3 + NO][4];
+  __shared__ float st[2];
+  const long R = (long)tk.Bm * tk.A;
+  const float invR = 1.0f / (float)R, gs = tk.grad_scale;
+  if (threadIdx.x == 0) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < tk.n_stats; ++i) { s1 += tk.stats[2 * i]; s2 += tk.stats[2 * i + 1]; }
+    const double mean = s1 / (double)R;
+    double var = s2 / (double)R - mean * mean;
+    if (var < 0.0) var = 0.0;
+    st[0] = (float)mean;
+    st[1] = 1.0f / ((float)sqrt(var) + 1e-8f);
+  }
+  __syncthreads();
+  float sc[NO], ds[NO];
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    sc[o] = tn::scale_of(tk.log_std[o < tk.d ? o : 0], tk.min_scale);
+    ds[o] = 0.0f;
+  }
+  float la = 0.0f, lb = 0.0f, lc = 0.0f;
+  const float lo = 1.0f - tk.clip_eps, hi = 1.0f + tk.clip_eps;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < tk.rows; q += (long)gridDim.x * 256) {
+    const long tb = (q >> 5) * tk.d * 32 + (q & 31);
+    if (q >= R) {  // padding
+      for (int o = 0; o < tk.d; ++o) tk.dmean[tb + (long)o * 32] = 0.0f;
+      tk.dvalues[q] = 0.0f;
+      continue;
+    }
+    const long b = q / tk.A;
+    const long er = (long)tk.idx[b] * tk.A + (q - b * tk.A);
+    float dm[NO], dsl[NO], th[NO], ep[NO];
+    float lp = 0.0f, ent = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      dm[o] = dsl[o] = th[o] = ep[o] = 0.0f;
+      if (o < tk.d) {
+        const float mean = tk.mean[tb + (long)o * 32];
+        const tn::LogProb l = tn::log_prob(tk.action[er * tk.d + o], mean, sc[o]);
+        lp += l.lp;
+        dm[o] = l.dmean;
+        dsl[o] = l.dscale;
+        ep[o] = tn::noise(tk.row_offset + (uint32_t)er, tk.ent_step, o, tn::STREAM_ENTROPY, tk.seed_lo, tk.seed_hi);
+        const float x = fmaf(sc[o], ep[o], mean);
+        th[o] = tanhf(x);
+        ent += 0.5f + tn::HALF_LOG_2PI + logf(sc[o]) + tn::tanh_fldj(x);
+      }
+    }
+    const float gae = (tk.adv[er] - st[0]) * st[1];
+    const float ratio = expf(lp - tk.old_log_prob[er]);
+    const float rc = fminf(fmaxf(ratio, lo), hi);
+    const float l1 = ratio * gae, l2 = rc * gae;
+    const bool inside = (ratio >= lo) && (ratio <= hi);
+    const float g1 = (l1 < l2) ? 1.0f : ((l1 == l2) ? 0.5f : 0.0f);
+    const float g2 = inside ? (1.0f - g1) : 0.0f;
+    const float dlp = -(g1 + g2) * gae * ratio * invR;
+    const float ec = tk.ent_coef * invR;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      if (o < tk.d) {
+        tk.dmean[tb + (long)o * 32] = (dlp * dm[o] + ec * 2.0f * th[o]) * gs;
+        ds[o] += dlp * dsl[o] - ec * (1.0f / sc[o] - 2.0f * th[o] * ep[o]);
+      }
+    }
+    la += -fminf(l1, l2) * invR;
+    lb += ent * invR;
+    // value: as mat_loss_kernel
+    const float v = tk.values[q];
+    const float ov = tk.old_value[er], tg = tk.targets[er];
+    const float diff = v - ov;
+    const float vclip = ov + fminf(fmaxf(diff, -tk.clip_eps), tk.clip_eps);
+    const float e1 = v - tg, e2 = vclip - tg;
+    const float v1 = e1 * e1, v2 = e2 * e2;
+    const bool vin = (diff >= -tk.clip_eps) && (diff <= tk.clip_eps);
+    const float h1 = (v1 > v2) ? 1.0f : ((v1 == v2) ? 0.5f : 0.0f);
+    const float h2 = vin ? (1.0f - h1) : 0.0f;
+    tk.dvalues[q] = tk.vf_coef * (h1 * e1 + h2 * e2) * invR * gs;
+    lc += 0.5f * fmaxf(v1, v2) * invR;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    la += __shfl_down(la, o, 64);
+    lb += __shfl_down(lb, o, 64);
+    lc += __shfl_down(lc, o, 64);
+#pragma unroll
+    for (int k = 0; k < NO; ++k) ds[k] += __shfl_down(ds[k], o, 64);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][w] = la; red[1][w] = lb; red[2][w] = lc;
+#pragma unroll
+    for (int k = 0; k < NO; ++k) red[3 + k][w] = ds[k];
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < 3) tk.partials[3 * blockIdx.x + k] = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+  if (k < tk.d)  // d scale / d log_std = sigmoid(log_std)
+    tk.dls_partials[(long)blockIdx.x * tk.d + k] =
+        (((red[3 + k][0] + red[3 + k][1]) + red[3 + k][2]) + red[3 + k][3]) * tn::sigmoid(tk.log_std[k]);
+}
+
 int blocks_for(long total, int cap) {
   long b = (total + 255) / 256;
   return (int)(b > cap ? cap : (b < 1 ? 1 : b));
@@ -585,6 +758,66 @@ extern "C" int mava_mat_loss_f32(int Bm, int A, int n_actions, long rows, const 
   tk.stats = adv_stats; tk.n_stats = n_stats; tk.clip_eps = clip_eps; tk.ent_coef = ent_coef; tk.vf_coef = vf_coef;
   tk.grad_scale = grad_scale; tk.dlogits = dlogits; tk.dvalues = dvalues; tk.partials = loss_partials;
   hipLaunchKernelGGL(mat_loss_kernel, dim3(n_blocks), dim3(256), 0, s, tk);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
+}
+
+extern "C" int mava_transformer_shift_action_f32(const float* action, const int32_t* idx, int B, int A, int action_dim, int known,
+                                                 long rows, int n_pad, float* out, hipStream_t s) {
+  const char* who = "mava_transformer_shift_action_f32";
+  MAVA_ARG_CHECK(B >= 1 && A >= 1 && A <= MAX_A && rows >= 32 && rows % 32 == 0 && (long)B * A <= rows, 0,
+                 "%s: B=%d A=%d rows=%ld (A <= %d, rows a multiple of 32 holding B * A rows)", who, B, A, rows, MAX_A);
+  MAVA_ARG_CHECK(action_dim >= 1 && action_dim <= MAX_DIM && n_pad >= action_dim && n_pad % 32 == 0 && known >= 0 && known <= A - 1, 1,
+                 "%s: action_dim=%d n_pad=%d known=%d (1 <= action_dim <= %d, n_pad a multiple of 32 holding it, known <= A - 1)", who,
+                 action_dim, n_pad, known, MAX_DIM);
+  MAVA_ARG_CHECK(out && (action || known == 0), 2, "%s: null pointer argument", who);
+  hipLaunchKernelGGL(shift_action_kernel, dim3(blocks_for(rows * n_pad, 4096)), dim3(256), 0, s, action, idx, B, A, action_dim, known,
+                     rows, n_pad, out);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
+}
+
+extern "C" int mava_transformer_sample_continuous_f32(int B, int A, int agent, int action_dim, float min_scale, const float* mean,
+                                                      const float* log_std, uint64_t seed, uint32_t step, uint32_t row_offset,
+                                                      int greedy, float* action, float* log_prob, hipStream_t s) {
+  const char* who = "mava_transformer_sample_continuous_f32";
+  MAVA_ARG_CHECK(B >= 1 && A >= 1 && A <= MAX_A && agent >= 0 && agent < A && action_dim >= 1 && action_dim <= MAX_DIM, 0,
+                 "%s: B=%d A=%d agent=%d action_dim=%d (A <= %d, agent < A, 1 <= action_dim <= %d)", who, B, A, agent, action_dim, MAX_A,
+                 MAX_DIM);
+  MAVA_ARG_CHECK(min_scale >= 0.0f, 1, "%s: min_scale=%g", who, (double)min_scale);
+  MAVA_ARG_CHECK(mean && log_std && action && log_prob, 2, "%s: null pointer argument", who);
+  SampleContTask tk = {};
+  tk.B = B; tk.A = A; tk.agent = agent; tk.d = action_dim; tk.min_scale = min_scale; tk.mean = mean; tk.log_std = log_std;
+  tk.seed_lo = (uint32_t)seed; tk.seed_hi = (uint32_t)(seed >> 32); tk.step = step; tk.row_offset = row_offset;
+  tk.greedy = greedy != 0; tk.action = action; tk.log_prob = log_prob;
+  hipLaunchKernelGGL(mat_sample_cont_kernel, dim3(mava_cdiv(B, 256)), dim3(256), 0, s, tk);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
+}
+
+extern "C" int mava_transformer_loss_continuous_f32(int Bm, int A, int action_dim, float min_scale, long rows, const int32_t* idx,
+                                                    const float* mean, const float* log_std, const float* values, const float* action,
+                                                    const float* old_log_prob, const float* advantages, const float* old_value,
+                                                    const float* targets, const double* adv_stats, int n_stats, float clip_eps,
+                                                    float ent_coef, float vf_coef, uint64_t seed, uint32_t ent_step, uint32_t row_offset,
+                                                    float grad_scale, float* dmean, float* dvalues, float* loss_partials,
+                                                    float* dlog_std_partials, int n_blocks, hipStream_t s) {
+  const char* who = "mava_transformer_loss_continuous_f32";
+  MAVA_ARG_CHECK(Bm >= 1 && A >= 1 && A <= MAX_A && rows >= 32 && rows % 32 == 0 && (long)Bm * A <= rows && n_blocks >= 1 &&
+                 n_blocks <= 65536 && n_stats >= 1, 0, "%s: Bm=%d A=%d rows=%ld n_blocks=%d (A <= %d, rows a multiple of 32 holding Bm * A)",
+                 who, Bm, A, rows, n_blocks, MAX_A);
+  MAVA_ARG_CHECK(action_dim >= 1 && action_dim <= MAX_DIM && min_scale >= 0.0f, 1, "%s: action_dim=%d min_scale=%g (1 <= action_dim <= %d)",
+                 who, action_dim, (double)min_scale, MAX_DIM);
+  MAVA_ARG_CHECK(idx && mean && log_std && values && action && old_log_prob && advantages && old_value && targets && adv_stats && dmean &&
+                 dvalues && loss_partials && dlog_std_partials, 2, "%s: null pointer argument", who);
+  LossContTask tk = {};
+  tk.Bm = Bm; tk.A = A; tk.d = action_dim; tk.min_scale = min_scale; tk.rows = rows; tk.idx = idx; tk.mean = mean; tk.log_std = log_std;
+  tk.values = values; tk.action = action; tk.old_log_prob = old_log_prob; tk.adv = advantages; tk.old_value = old_value;
+  tk.targets = targets; tk.stats = adv_stats; tk.n_stats = n_stats; tk.clip_eps = clip_eps; tk.ent_coef = ent_coef; tk.vf_coef = vf_coef;
+  tk.grad_scale = grad_scale; tk.seed_lo = (uint32_t)seed; tk.seed_hi = (uint32_t)(seed >> 32); tk.ent_step = ent_step;
+  tk.row_offset = row_offset; tk.dmean = dmean; tk.dvalues = dvalues; tk.partials = loss_partials; tk.dls_partials = dlog_std_partials;
+  if (action_dim <= 8) hipLaunchKernelGGL((mat_loss_cont_kernel<8>), dim3(n_blocks), dim3(256), 0, s, tk);
+  else hipLaunchKernelGGL((mat_loss_cont_kernel<16>), dim3(n_blocks), dim3(256), 0, s, tk);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }

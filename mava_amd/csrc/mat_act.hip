@@ -38,6 +38,7 @@
 
 #include "common.h"
 #include "mat_rows.h"
+#include "tanh_normal.h"
 
 namespace {
 
@@ -45,6 +46,7 @@ constexpr int ROWS = 32;
 constexpr int MAX_A = 32;
 constexpr int MAX_D = 128;
 constexpr int MAX_ACT = 64;
+constexpr int MAX_DIM = 16;    // action dimensions of the continuous head
 constexpr int MAX_O = 1024;
 constexpr int MAX_NBLOCK = 4;  // decoder blocks the kernel takes; beyond that the caller runs layer by layer
 constexpr int LDP = MAX_A + 1;
@@ -61,6 +63,8 @@ struct ActTask {
   float* log_prob;
   float* value;
   float* cache;
+  float* action_f;  // continuous head: (B, A, nA) f32 actions, nA = the action dimension
+  float min_scale;
 };
 
 __host__ __device__ inline long enc_block_size(long D) { return 6 * D * D + 10 * D; }
@@ -251,7 +255,11 @@ constexpr size_t lds_bytes(int D) {
          ROWS * sizeof(int);
 }
 
-template <int D>
+// CONT: the continuous head (tanh-normal, tanh_normal.h).  Three places differ, each under `if constexpr`: the decoder's input
+// row is GELU(bias + sum_k previous action[k] * W[k][:]) (GELU(bias) for agent 0), the head writes nA = action_dim means, and
+// the sampling step is mava_transformer_sample_continuous_f32's.  The logits tile holds the step's means ([32][16]) and, from
+// float 512 on, the group's actions so far ([32 rows][16]).
+template <int D, bool CONT>
 __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int LD = D + 1, NS = 256 / D, RPT = ROWS / NS;
@@ -265,6 +273,7 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
   float* const T = V + ROWS * LD;
   float* const s_log = T + ROWS * LD;                    // [32][64] logits of the step's rows
   int* const s_act = reinterpret_cast<int*>(s_log + ROWS * MAX_ACT);  // [R] the group's actions so far
+  float* const s_prev = s_log + ROWS * MAX_DIM;          // CONT: [R][16] the group's action vectors so far
   const int tid = threadIdx.x;
   const int A = a.A, O = a.O, nA = a.nA, nb = a.nb, S = a.S;
 
@@ -380,10 +389,23 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
     float* const QR = Q;  // q / attention output / hidden
     float* const TR = T;  // branch output
     for (int i = 0; i < A; ++i) {
-      for (int e = tid; e < ns * D; e += 256) {
-        const int s = e / D, d = e - s * D;
-        const int tok = (i == 0) ? 0 : 1 + s_act[s * A + i - 1];
-        QR[s * LD + d] = gelu_f(dec[(long)tok * D + d]);
+      if constexpr (CONT) {
+        const float* const ab = dec + (long)nA * D;  // act_dense's bias follows its (nA x D) kernel
+        for (int e = tid; e < ns * D; e += 256) {
+          const int s = e / D, d = e - s * D;
+          float acc = 0.0f;
+          if (i > 0) {
+            const float* pa = s_prev + (s * A + i - 1) * MAX_DIM;
+            for (int k = 0; k < nA; ++k) acc = fmaf(pa[k], dec[(long)k * D + d], acc);
+          }
+          QR[s * LD + d] = gelu_f(acc + ab[d]);
+        }
+      } else {
+        for (int e = tid; e < ns * D; e += 256) {
+          const int s = e / D, d = e - s * D;
+          const int tok = (i == 0) ? 0 : 1 + s_act[s * A + i - 1];
+          QR[s * LD + d] = gelu_f(dec[(long)tok * D + d]);
+        }
       }
       __syncthreads();
       ln_rows<D>(QR, 0, 1, nullptr, 0, 0, XR, d_ln, d_ln + D, ns);
@@ -429,11 +451,28 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
           const int s = e / nA, o = e - s * nA;
           float acc = 0.0f;
           for (int k = 0; k < D; ++k) acc = fmaf(TR[s * LD + k], hw[k * nA + o], acc);
-          s_log[s * MAX_ACT + o] = acc + hb[o];
+          s_log[s * (CONT ? MAX_DIM : MAX_ACT) + o] = acc + hb[o];
         }
       }
       __syncthreads();
-      if (tid < ns) {
+      if constexpr (CONT) {
+        if (tid < ns) {
+          const long row = (b0 + tid) * A + i;
+          const float* const ls = d_head + DD + 3 * D + (long)D * nA + nA;  // decoder/log_std: the last leaf
+          const uint32_t gid = a.row_offset + (uint32_t)row;
+          float lp = 0.0f;
+          for (int o = 0; o < nA; ++o) {
+            const float mean = s_log[tid * MAX_DIM + o];
+            const float sc = tn::scale_of(ls[o], a.min_scale);
+            const float eps = a.greedy ? 0.0f : tn::noise(gid, a.step, o, tn::STREAM_SAMPLE, a.seed_lo, a.seed_hi);
+            const float act = tanhf(fmaf(sc, eps, mean));
+            lp += tn::log_prob(act, mean, sc).lp;
+            a.action_f[row * nA + o] = act;
+            s_prev[(tid * A + i) * MAX_DIM + o] = act;
+          }
+          a.log_prob[row] = lp;
+        }
+      } else if (tid < ns) {
         const long row = (b0 + tid) * A + i;
         const RowLogitsT<1> rl = {s_log + tid * MAX_ACT, a.mask != nullptr ? a.mask + row * nA : nullptr, nA};
         const RowStats st = row_stats(rl);
@@ -447,15 +486,15 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
   }
 }
 
-template <int D>
+template <int D, bool CONT = false>
 int launch_act(const ActTask& a, int n_blocks, hipStream_t s) {
   static bool attr_set = false;
   constexpr size_t lb = lds_bytes(D);
   if (!attr_set) {
-    MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)mat_act_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+    MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)mat_act_kernel<D, CONT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     attr_set = true;
   }
-  hipLaunchKernelGGL(mat_act_kernel<D>, dim3(n_blocks), dim3(256), lb, s, a);
+  hipLaunchKernelGGL((mat_act_kernel<D, CONT>), dim3(n_blocks), dim3(256), lb, s, a);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }
@@ -504,5 +543,44 @@ extern "C" int mava_transformer_act_f32(const float* params, const float* agents
     case 64: return launch_act<64>(a, n_blocks, s);
     case 96: return launch_act<96>(a, n_blocks, s);
     default: return launch_act<128>(a, n_blocks, s);
+  }
+}
+
+extern "C" long mava_transformer_param_count_continuous(int O, int action_dim, int D, int n_block) {
+  if (O < 1 || action_dim < 1 || D < 1 || n_block < 0) return -1;
+  return enc_size(O, D, n_block) + dec_size(action_dim, D, n_block) + action_dim;
+}
+
+extern "C" int mava_transformer_act_continuous_f32(const float* params, const float* agents_view, int B, int A, int O, int action_dim,
+                                                   int D, int n_head, int n_block, float min_scale, uint64_t seed, uint32_t step,
+                                                   uint32_t row_offset, int greedy, float* action, float* log_prob, float* value,
+                                                   void* workspace, size_t workspace_bytes, int n_blocks, hipStream_t s) {
+  const char* who = "mava_transformer_act_continuous_f32";
+  MAVA_ARG_CHECK(B >= 1 && (long)B * MAX_A < (1L << 31), 0, "%s: B=%d (at least one sample, B * 32 below 2^31)", who, B);
+  MAVA_ARG_CHECK(A >= 1 && A <= MAX_A, 1, "%s: A=%d (1..%d agents)", who, A, MAX_A);
+  MAVA_ARG_CHECK(D >= 32 && D % 32 == 0 && D <= MAX_D, 2, "%s: D=%d (a multiple of 32 up to %d)", who, D, MAX_D);
+  MAVA_ARG_CHECK(n_head >= 1 && D % n_head == 0, 3, "%s: D=%d n_head=%d (D a multiple of n_head)", who, D, n_head);
+  MAVA_ARG_CHECK(action_dim >= 1 && action_dim <= MAX_DIM && min_scale >= 0.0f, 4, "%s: action_dim=%d min_scale=%g (1..%d dimensions)", who,
+                 action_dim, (double)min_scale, MAX_DIM);
+  MAVA_ARG_CHECK(O >= 1 && O <= MAX_O, 5, "%s: O=%d (1..%d observation features)", who, O, MAX_O);
+  MAVA_ARG_CHECK(n_block >= 1, 6, "%s: n_block=%d", who, n_block);
+  MAVA_ARG_CHECK(n_blocks >= 1 && n_blocks <= 65536, 7, "%s: n_blocks=%d", who, n_blocks);
+  MAVA_ARG_CHECK(params && agents_view && action && log_prob, 8, "%s: null pointer argument", who);
+  if (n_block > MAX_NBLOCK) return 1;  // not instantiated: the caller runs the layer-wise path
+  const size_t need = mava_transformer_act_workspace_bytes(B, A, D, n_block, n_blocks);
+  MAVA_ARG_CHECK(workspace != nullptr && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, 9,
+                 "%s: workspace of %zu bytes (16-byte aligned) required, got %zu", who, need, workspace_bytes);
+  ActTask a = {};
+  a.params = params; a.obs = agents_view;
+  a.B = B; a.A = A; a.O = O; a.nA = action_dim; a.H = n_head; a.hd = D / n_head; a.nb = n_block;
+  a.S = A >= ROWS ? 1 : ROWS / A;
+  a.greedy = greedy != 0; a.min_scale = min_scale;
+  a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step = step; a.row_offset = row_offset;
+  a.action_f = action; a.log_prob = log_prob; a.value = value; a.cache = static_cast<float*>(workspace);
+  switch (D) {
+    case 32: return launch_act<32, true>(a, n_blocks, s);
+    case 64: return launch_act<64, true>(a, n_blocks, s);
+    case 96: return launch_act<96, true>(a, n_blocks, s);
+    default: return launch_act<128, true>(a, n_blocks, s);
   }
 }

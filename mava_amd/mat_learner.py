@@ -12,6 +12,11 @@ Acting is autoregressive: A decoder passes per env step, pass i samples agent i 
 sees its action in the shifted one-hot.  Training is one teacher-forced pass.  With network.acting=fused an env step is one
 launch instead (mava_transformer_act_f32, csrc/mat_act.hip: the same network with a key/value cache, f32 dense products
 whatever system.matmul_mode); the bootstrap value and training stay on the layer-wise tapes.
+With a ContinuousActionHead (network=continuous_transformer; float64 model tests/mat_continuous_model.py) the decoder's input is
+the shifted ACTION VECTOR (row 0 zero, no start token; act_dense has a bias and runs in exact f32), head_out gives the d means of
+Independent(TanhTransformed(Normal(mean, softplus(log_std) + min_scale))) and decoder/log_std is the flat vector's last leaf;
+the three kernels are mava_transformer_shift_action_f32 / _sample_continuous_f32 / _loss_continuous_f32, the fused step
+mava_transformer_act_continuous_f32.
 
 Every matrix is T32 with the E * A (acting) or Bm * A (minibatch) agent rows padded to a multiple of 32; the dense products
 are GenericNet._dense / _xty (mava_rec_dense_f32 / mava_rec_xty_f32: system.matmul_mode, grad_scale), everything between
@@ -33,7 +38,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 
 from . import ops, ppo_learner
-from ._lib import MavaHipError, launch, lib, ptr, stream_ptr
+from ._lib import Ctx, MavaHipError, launch, lib, ptr, stream_ptr
 from .generic_networks import GenericMLPTorso, GenericNet
 from .learner_common import pad32
 from .networks import _orthogonal_
@@ -41,6 +46,7 @@ from .ppo_learner import PPOLearner
 from .types import LearnerState, TimeStep
 
 MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
+MAX_ACTION_DIM = 16  # ... and of its continuous head (csrc/tanh_normal.h's users)
 ACTING = ("layerwise", "fused")  # network.acting: MATPass.act launches layer by layer, or csrc/mat_act.hip once per env step
 
 
@@ -63,6 +69,17 @@ def check_supported(*, num_agents: int, n_actions: int, n_embd: int, n_head: int
         raise MavaHipError(f"ff_mat: system.update_batch_size must be 1, got {update_batch_size}")
 
 
+def check_supported_continuous(*, num_agents: int, action_dim: int, n_embd: int, n_head: int, independent_std: bool, world: int,
+                               update_batch_size: int) -> None:
+    """ff_mat's refusals with a ContinuousActionHead (check_supported stays the discrete network's)."""
+    if not 1 <= action_dim <= MAX_ACTION_DIM:
+        raise MavaHipError(f"ff_mat: continuous actions of 1..{MAX_ACTION_DIM} dimensions, the environment has {action_dim}")
+    if not independent_std:
+        raise MavaHipError("ff_mat: ContinuousActionHead.independent_std=False is not implemented (one log_std vector only)")
+    check_supported(num_agents=num_agents, n_actions=action_dim, n_embd=n_embd, n_head=n_head, continuous=False, world=world,
+                    update_batch_size=update_batch_size)
+
+
 def _attn_leaves(D: int) -> List[Tuple[Tuple[str, ...], Tuple[int, ...], Any]]:
     out = []
     for name in ("query", "key", "value", "proj"):
@@ -79,8 +96,10 @@ def _dense_leaves(name: str, K: int, N: int, scale: float, bias: bool = True):
     return out + ([((name, "bias"), (N,), 0.0)] if bias else [])
 
 
-def param_spec(O: int, nA: int, D: int, n_block: int):
-    """[(tree path, shape, init)] of the flat vector [encoder | decoder]; init: an orthogonal scale, 0.0 or "ones"."""
+def param_spec(O: int, nA: int, D: int, n_block: int, continuous: bool = False):
+    """[(tree path, shape, init)] of the flat vector [encoder | decoder]; init: an orthogonal scale, 0.0 or "ones".
+    continuous (nA = the action dimension): act_dense reads the nA-wide action vector and has a bias, head_out gives the nA
+    means, and decoder/log_std (nA zeros) is the last leaf."""
     r2 = math.sqrt(2.0)
     enc = _ln_leaves("obs_ln", O) + _dense_leaves("obs_dense", O, D, r2) + _ln_leaves("ln", D)
     for i in range(n_block):
@@ -89,7 +108,7 @@ def param_spec(O: int, nA: int, D: int, n_block: int):
         blk += _dense_leaves("mlp_0", D, D, r2) + _dense_leaves("mlp_1", D, D, r2) + _ln_leaves("ln2", D)
         enc += [((b,) + p, s, k) for p, s, k in blk]
     enc += _dense_leaves("head_dense", D, D, r2) + _ln_leaves("head_ln", D) + _dense_leaves("head_out", D, 1, 0.01)
-    dec = _dense_leaves("act_dense", nA + 1, D, r2, bias=False) + _ln_leaves("ln", D)
+    dec = (_dense_leaves("act_dense", nA, D, r2) if continuous else _dense_leaves("act_dense", nA + 1, D, r2, bias=False)) + _ln_leaves("ln", D)
     for i in range(n_block):
         b = f"block_{i}"
         blk = [(("attn1",) + p, s, k) for p, s, k in _attn_leaves(D)] + _ln_leaves("ln1", D)
@@ -97,6 +116,8 @@ def param_spec(O: int, nA: int, D: int, n_block: int):
         blk += _dense_leaves("mlp_0", D, D, r2) + _dense_leaves("mlp_1", D, D, r2) + _ln_leaves("ln3", D)
         dec += [((b,) + p, s, k) for p, s, k in blk]
     dec += _dense_leaves("head_dense", D, D, r2) + _ln_leaves("head_ln", D) + _dense_leaves("head_out", D, nA, 0.01)
+    if continuous:
+        dec += [(("log_std",), (nA,), 0.0)]
     return [(("encoder",) + p, s, k) for p, s, k in enc] + [(("decoder",) + p, s, k) for p, s, k in dec]
 
 
@@ -112,9 +133,12 @@ class MATParams(dict):
 class MATNet:
     """Shapes, flat layout and trees of the network."""
 
-    def __init__(self, O: int, nA: int, A: int, D: int, n_head: int, n_block: int):
+    def __init__(self, O: int, nA: int, A: int, D: int, n_head: int, n_block: int, *, continuous: bool = False,
+                 min_scale: float = 1e-3):
+        """continuous: nA is the action dimension of a ContinuousActionHead with scale = softplus(log_std) + min_scale."""
         self.O, self.nA, self.A, self.D, self.H, self.n_block = int(O), int(nA), int(A), int(D), int(n_head), int(n_block)
-        self.spec = param_spec(self.O, self.nA, self.D, self.n_block)
+        self.continuous, self.min_scale = bool(continuous), float(min_scale)
+        self.spec = param_spec(self.O, self.nA, self.D, self.n_block, self.continuous)
         self.off: Dict[Tuple[str, ...], int] = {}
         off = 0
         for path, shape, _ in self.spec:
@@ -182,6 +206,7 @@ class _Graph:
         self.nblk = max(1, min(256, self.rows // 32))
         self.prod = GenericNet(GenericMLPTorso([net.D]), net.D, [])  # the product launches of the general layer path
         self.prod.ctx = ctx
+        self._prod32: Optional[GenericNet] = None
         self.bufs: List[_Buf] = []
         if training:
             self.slabs = torch.zeros((self.nblk, 128 * 128 + 128 + 8), device=device)
@@ -196,17 +221,26 @@ class _Graph:
         o = self.net.off[path]
         return flat[o : o + n]
 
+    def _exact(self) -> GenericNet:
+        """The product launches in exact f32 whatever system.matmul_mode (a context of their own)."""
+        if self._prod32 is None:
+            self._prod32 = GenericNet(GenericMLPTorso([self.net.D]), self.net.D, [])
+            self._prod32.ctx = Ctx("f32")
+        return self._prod32
+
     # ---- layers: (forward closure, backward closure) pairs appended to a tape
-    def dense(self, tape, x: _Buf, path: Tuple[str, ...], K: int, N: int, bias: bool = True, x_grad: bool = True) -> _Buf:
+    def dense(self, tape, x: _Buf, path: Tuple[str, ...], K: int, N: int, bias: bool = True, x_grad: bool = True,
+              exact: bool = False) -> _Buf:
         y = self.buf(N)
         wp, bp = path + ("kernel",), path + ("bias",)
+        prod = self._exact() if exact else self.prod
 
         def fwd(flat):
-            self.prod._dense(x.t.data_ptr(), x.ld, K, self._p(flat, wp, K * N), self._p(flat, bp, N) if bias else None, y.t, N,
+            prod._dense(x.t.data_ptr(), x.ld, K, self._p(flat, wp, K * N), self._p(flat, bp, N) if bias else None, y.t, N,
                              self.rows, what="mat_dense")
 
         def bwd(flat, g, inv):
-            self.prod._xty(x.t.data_ptr(), x.ld, K, y.grad, N, self.rows, self.slabs, self._p(g, wp, K * N),
+            prod._xty(x.t.data_ptr(), x.ld, K, y.grad, N, self.rows, self.slabs, self._p(g, wp, K * N),
                            self._p(g, bp, N) if bias else None, inv, False)
             if not x_grad:
                 return
@@ -214,7 +248,7 @@ class _Graph:
             first = x.grad is None
             if first:
                 x.grad = x.own()
-            self.prod._dense(y.grad.data_ptr(), N, N, wt, None, x.grad, K, self.rows, accumulate=not first, what="mat_dense_bwd")
+            prod._dense(y.grad.data_ptr(), N, N, wt, None, x.grad, K, self.rows, accumulate=not first, what="mat_dense_bwd")
 
         tape.append((fwd, bwd))
         return y
@@ -308,9 +342,10 @@ class MATPass(_Graph):
             self._act_blocks = max(1, min(256, -(-self.B // max(1, 32 // net.A))))  # one block per group of samples
             need = int(lib().mava_transformer_act_workspace_bytes(self.B, net.A, D, net.n_block, self._act_blocks))
             self._act_ws = torch.zeros(max(need, 16), dtype=torch.uint8, device=device)
-        self.Np = pad32(nA + 1)
+        n_in = nA if net.continuous else nA + 1  # the decoder's input: the previous action vector, or [start | one-hot]
+        self.Np = pad32(n_in)
         self.obs = self.buf(O)
-        self.onehot = self.buf(nA + 1, ld=self.Np)
+        self.onehot = self.buf(n_in, ld=self.Np)
         # sample ids of the rows, padded with sample 0 so that the gather of the padding rows stays inside the source
         self.idx = torch.zeros(-(-self.rows // self.A) + 1, dtype=torch.int32, device=device)
         enc: list = []
@@ -323,8 +358,8 @@ class MATPass(_Graph):
         self.rep = x
         self.value = self.head(enc, x, ("encoder",), 1)
         dec: list = []
-        x = self.ln(dec, self.gelu(dec, self.dense(dec, self.onehot, ("decoder", "act_dense"), nA + 1, D, bias=False, x_grad=False)), None,
-                    ("decoder", "ln"), D)
+        x = self.ln(dec, self.gelu(dec, self.dense(dec, self.onehot, ("decoder", "act_dense"), n_in, D, bias=net.continuous, x_grad=False,
+                                                   exact=net.continuous)), None, ("decoder", "ln"), D)
         for i in range(net.n_block):
             b = ("decoder", f"block_{i}")
             x = self.ln(dec, self.attention(dec, x, x, b + ("attn1",), True), x, b + ("ln1",), D)
@@ -340,6 +375,11 @@ class MATPass(_Graph):
                self.rows, net.O, ptr(self.obs.t), stream_ptr())
 
     def shift_onehot(self, action: torch.Tensor, known: int, use_idx: bool) -> None:
+        """The decoder's input from the first `known` agents' actions: shifted one-hots, or the shifted action vectors."""
+        if self.net.continuous:
+            launch("mat_shift_action", lib().mava_transformer_shift_action_f32, ptr(action), ptr(self.idx) if use_idx else None, self.B,
+                   self.A, self.net.nA, known, self.rows, self.Np, ptr(self.onehot.t), stream_ptr())
+            return
         launch("mat_onehot", lib().mava_mat_shift_onehot_f32, ptr(action), ptr(self.idx) if use_idx else None, self.B, self.A,
                self.net.nA, known, self.rows, self.Np, ptr(self.onehot.t), stream_ptr())
 
@@ -371,16 +411,30 @@ class MATPass(_Graph):
         self.encode(flat)
         if value_out is not None:
             value_out.view(-1).copy_(self.value.t[: self.valid])
+        net = self.net
         for i in range(self.A):
             self.shift_onehot(action, i, False)
             self.decode(flat)
-            launch("mat_sample", lib().mava_mat_sample_f32, self.B, self.A, i, self.net.nA, ptr(self.logits.t), ptr(mask),
-                   seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action), ptr(log_prob), stream_ptr())
+            if net.continuous:  # the logits buffer holds the means; the mask is not read
+                launch("mat_sample_cont", lib().mava_transformer_sample_continuous_f32, self.B, self.A, i, net.nA, net.min_scale,
+                       ptr(self.logits.t), ptr(self.log_std(flat)), seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF,
+                       int(greedy), ptr(action), ptr(log_prob), stream_ptr())
+            else:
+                launch("mat_sample", lib().mava_mat_sample_f32, self.B, self.A, i, net.nA, ptr(self.logits.t), ptr(mask),
+                       seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action), ptr(log_prob), stream_ptr())
 
+    def log_std(self, flat: torch.Tensor) -> torch.Tensor:
+        return self._p(flat, ("decoder", "log_std"), self.net.nA)
 
     def _act_fused(self, flat, agents_view, mask, action, log_prob, seed, step, row_offset, greedy, value_out) -> bool:
         """The env step as one launch; False when the kernel has no instance for this depth (the caller runs layer by layer)."""
         net, L = self.net, lib()
+        if net.continuous:
+            rc = launch("mat_act", L.mava_transformer_act_continuous_f32, ptr(flat), ptr(agents_view), self.B, net.A, net.O, net.nA, net.D,
+                        net.H, net.n_block, net.min_scale, seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy),
+                        ptr(action), ptr(log_prob), ptr(value_out), ptr(self._act_ws), self._act_ws.numel(), self._act_blocks,
+                        stream_ptr(), ok=(0, 1))
+            return rc == 0
         rc = launch("mat_act", L.mava_transformer_act_f32, ptr(flat), ptr(agents_view), ptr(mask), self.B, net.A, net.O, net.nA, net.D,
                     net.H, net.n_block, seed & (2**64 - 1), step & 0xFFFFFFFF, row_offset & 0xFFFFFFFF, int(greedy), ptr(action),
                     ptr(log_prob), ptr(value_out), ptr(self._act_ws), self._act_ws.numel(), self._act_blocks, stream_ptr(), ok=(0, 1))
@@ -430,7 +484,10 @@ class MATActor:
         B = int(av.shape[0])
         av = av.reshape(B, self.net.A, self.net.O).float().contiguous()
         mask = observation.action_mask.reshape(B, self.net.A, self.net.nA).to(torch.uint8).contiguous()
-        action = torch.zeros((B, self.net.A), dtype=torch.int32, device=av.device)
+        if self.net.continuous:  # the (B, A, action_dim) f32 action vectors; the (all-ones) mask is not read
+            action = torch.zeros((B, self.net.A, self.net.nA), device=av.device)
+        else:
+            action = torch.zeros((B, self.net.A), dtype=torch.int32, device=av.device)
         log_prob = torch.zeros((B, self.net.A), device=av.device)
         self.pass_for(B).act(flat, av, mask, action, log_prob, seed, self._calls, 0, greedy)
         self._calls += 1
@@ -447,7 +504,7 @@ class MATLearner(PPOLearner):
         self.O = self.Oa  # (image observations: their flat row)
         if self.O > 1024:
             raise MavaHipError(f"ff_mat: observations of up to 1024 features (mava_rec_gather_t32_f32), got {self.O}")
-        self.net = MATNet(self.O, self.nA, self.A, self.D, self.H, self.n_block)
+        self.net = MATNet(self.O, self.nA, self.A, self.D, self.H, self.n_block, continuous=self.continuous, min_scale=self.min_scale)
         # actor_lr is the single learning rate of the one Adam; critic_lr is accepted and unused (encoder and decoder
         # share one optimiser, as upstream MAT does)
         self._alloc_params([(self.net, s.actor_lr)])
@@ -462,13 +519,21 @@ class MATLearner(PPOLearner):
         self.dvalues = torch.zeros(rows, device=d)
         self.loss_blocks = max(1, min(256, -(-rows // 256)))
         self.partials = torch.zeros((self.loss_blocks, 3), device=d)
+        self.dls_partials = torch.zeros((self.loss_blocks, self.nA), device=d) if self.continuous else None  # d loss / d log_std per block
         self.debug: Optional[Dict[str, list]] = None  # tests: {"grads": [], "perms": [], "state": []} records every minibatch (and "slot0")
 
     def _refuse(self, env, config) -> None:
-        head = config.network.get("action_head", None) or {}
-        check_supported(num_agents=int(env.num_agents), n_actions=int(env.action_dim), n_embd=self.D, n_head=self.H,
-                        continuous="ContinuousActionHead" in str(dict(head).get("_target_", "")), world=self.world,
-                        update_batch_size=self.U)
+        head = dict(config.network.get("action_head", None) or {})
+        if "ContinuousActionHead" in str(head.get("_target_", "")):
+            if not getattr(env, "continuous_actions", False):  # its step kernel would read the f32 action vectors as int32 indices
+                raise MavaHipError("ff_mat: a continuous action head is not implemented for an environment with discrete actions "
+                                   "(the environment does not set continuous_actions; env=spread does)")
+            check_supported_continuous(num_agents=int(env.num_agents), action_dim=int(env.action_dim), n_embd=self.D, n_head=self.H,
+                                       independent_std=bool(head.get("independent_std", True)), world=self.world,
+                                       update_batch_size=self.U)
+        else:
+            check_supported(num_agents=int(env.num_agents), n_actions=int(env.action_dim), n_embd=self.D, n_head=self.H, continuous=False,
+                            world=self.world, update_batch_size=self.U)
         if self.n_block < 1:
             raise ValueError(f"network.n_block must be >= 1, got {self.n_block}")
         if self.acting not in ACTING:
@@ -525,15 +590,34 @@ class MATLearner(PPOLearner):
         tr.encode(self.p)
         tr.decode(self.p)
         ops.adv_stats(rep.adv.view(-1), tr.idx, 0, Bm, self.A, out=self.stats)
+        if self.continuous:
+            self._continuous_loss_and_backward()
+        else:
+            self._discrete_loss_and_backward()
+        if self.debug is not None:
+            self.debug["grads"].append(self.g.clone())
+        self._clip_adam(n, k, mb)
+
+    def _continuous_loss_and_backward(self) -> None:
+        """tr.logits holds the means; the log_std gradient comes from the loss kernel's per-block sums, not from the tape."""
+        s, rep, tr, T, nA = self.config.system, self.rep, self.train, self.T, self.nA
+        launch("mat_loss_cont", lib().mava_transformer_loss_continuous_f32, self.Bm, self.A, nA, self.min_scale, tr.rows, ptr(tr.idx),
+               ptr(tr.logits.t), ptr(tr.log_std(self.p)), ptr(tr.value.t), ptr(rep.action), ptr(rep.log_prob), ptr(rep.adv), ptr(rep.value),
+               ptr(rep.tgt), ptr(self.stats), self.stats.shape[0], float(s.clip_eps), float(s.ent_coef), float(s.vf_coef),
+               self.seed & (2**64 - 1), self.ent_step & 0xFFFFFFFF, 0, self.grad_scale, ptr(self.dlogits), ptr(self.dvalues),
+               ptr(self.partials), ptr(self.dls_partials), self.loss_blocks, stream_ptr())
+        ops.slab_reduce(self.partials, 3, self.g[self.P : self.P + 3])
+        tr.backward(self.p, self.g, self.dlogits, self.dvalues, self.grad_scale)
+        ops.slab_reduce(self.dls_partials, nA, tr.log_std(self.g))
+
+    def _discrete_loss_and_backward(self) -> None:
+        s, rep, tr, T, Bm = self.config.system, self.rep, self.train, self.T, self.Bm
         launch("mat_loss", lib().mava_mat_loss_f32, Bm, self.A, self.nA, tr.rows, ptr(tr.idx), ptr(tr.logits.t), ptr(tr.value.t),
                ptr(rep.action_mask[:T]), ptr(rep.action), ptr(rep.log_prob), ptr(rep.adv), ptr(rep.value), ptr(rep.tgt), ptr(self.stats),
                self.stats.shape[0], float(s.clip_eps), float(s.ent_coef), float(s.vf_coef), self.grad_scale, ptr(self.dlogits),
                ptr(self.dvalues), ptr(self.partials), self.loss_blocks, stream_ptr())
         ops.slab_reduce(self.partials, 3, self.g[self.P : self.P + 3])
         tr.backward(self.p, self.g, self.dlogits, self.dvalues, self.grad_scale)
-        if self.debug is not None:
-            self.debug["grads"].append(self.g.clone())
-        self._clip_adam(n, k, mb)
 
     def _carry_observation(self) -> None:
         if self.debug is not None:  # slot 0 of the trajectory is about to become the next rollout's first observation

@@ -234,8 +234,8 @@ class PPOLearner:
                       **self._adam_kwargs(n, k, mb))
 
     def _epoch(self, n: int, k: int, perm) -> None:
-        """The M minibatches of epoch k.  ent_step counts them for the continuous head's entropy draw; MATLearner's
-        kernels (discrete head, closed-form entropy) never read it, so advancing it there is harmless."""
+        """The M minibatches of epoch k.  ent_step counts them for the continuous head's entropy draw; the kernels of a
+        discrete head (closed-form entropy) never read it, so advancing it there is harmless."""
         for mb in range(self.M):
             self._minibatch(n, k, mb, perm)
             self.ent_step += 1

@@ -3,6 +3,8 @@
 
     python tools/mat_bench.py [--envs 1024] [--acting layerwise|fused] [--out profiles/mat_bench_fused.json]
     python tools/mat_bench.py --curve [--acting fused] [--out profiles/mat_learning_curve_fused.json]
+    python tools/mat_bench.py --continuous [--envs 1024] [--out profiles/mat_continuous_bench.json]
+    python tools/mat_bench.py --continuous --curve [--out profiles/mat_continuous_learning_curve.json]
 
 Default mode: ms per update and library calls per update of ff_mat at its defaults on env=rware tiny-4ag, ff_mappo
 (update_batch_size 1) in the same run for scale, and the per-launch HIP-event times of the attention and LayerNorm kernels at
@@ -12,6 +14,8 @@ update the code implies and the fused step's maximum differences from the float6
 tests/test_gpu_mat_fused_act.py; with --acting only that setting runs.
 --curve: the learning run of tests/test_gpu_mat_learning.py - ff_mat and ff_mappo (network=mlp) for the same number of
 env-steps and the same seed - with the bar the test holds ff_mat to.
+--continuous: the same two measurements for the continuous action head on env=spread (CONT_CURVE): ff_mat
+network=continuous_transformer against ff_mappo network=continuous_mlp, update cost layer-wise against fused.
 """
 from __future__ import annotations
 
@@ -29,6 +33,13 @@ import torch  # noqa: E402
 # tests/test_gpu_mat_learning.py runs exactly this configuration
 CURVE = dict(env="lbf", scenario="2s-8x8-2p-2f-coop", envs=256, rollout=32, updates_per_call=10, calls=8, seed=42, lr=1e-3,
              eval_envs=256)
+# a curve may carry extra config overrides per system ("overrides": {system: [...]}); none by default
+# tests/test_gpu_mat_continuous_learning.py runs exactly CONT_CURVE: spread-2a, the smaller of the two scenarios at which ff_mappo's
+# gain stands clear of its noise at CURVE's budget.  --continuous --curve also records spread-3a (CONT_CURVE_3A), where ff_mat at its
+# default hyper-parameters misses the bar: see DESIGN.md 3.25.
+CONT_CURVE = dict(CURVE, env="spread", scenario="spread-2a",
+                  overrides={"ff_mappo": ["network=continuous_mlp"], "ff_mat": ["network=continuous_transformer"]})
+CONT_CURVE_3A = dict(CONT_CURVE, scenario="spread-3a")
 BAR_FACTOR = 0.4  # of ff_mappo's eval-return gain in the same run: the factor rec_qmix was held to against rec_iql
 
 
@@ -43,6 +54,7 @@ def _setup(system: str, dev, c=CURVE):
                                         f"system.rollout_length={c['rollout']}", "system.update_batch_size=1", f"system.seed={c['seed']}",
                                         f"system.actor_lr={c['lr']}", f"system.critic_lr={c['lr']}",
                                         f"arch.num_eval_episodes={c['eval_envs']}"]
+                  + list(c.get("overrides", {}).get(system, []))
                   + ([f"network.acting={c['acting']}"] if system == "ff_mat" and c.get("acting") else []))
     cfg.system.num_updates_per_eval = c["updates_per_call"]
     env, eval_env = envs.make(cfg, add_global_state=system == "ff_mappo", device=dev)
@@ -73,12 +85,14 @@ def learning_curve(system: str, dev, log=None, c=CURVE) -> dict:
     return {"curve": curve, "final_sem": sem}
 
 
-def learning_run(dev, log=None, acting=None) -> dict:
-    """Both systems on CURVE, and the bar: ff_mat's gain must reach BAR_FACTOR of ff_mappo's."""
-    c = CURVE if acting is None else dict(CURVE, acting=acting)
-    out = {"config": c, "bar_factor": BAR_FACTOR}
+def learning_run(dev, log=None, acting=None, curve=CURVE) -> dict:
+    """Both systems on `curve`, and the bar: ff_mat's gain must reach BAR_FACTOR of ff_mappo's."""
+    c = curve if acting is None else dict(curve, acting=acting)
+    out = {"config": c, "bar_factor": BAR_FACTOR, "env_steps": c["calls"] * c["updates_per_call"] * c["rollout"] * c["envs"]}
     for system in ("ff_mappo", "ff_mat"):
+        t0 = time.perf_counter()
         out[system] = learning_curve(system, dev, log, c)
+        out[system]["wall_s"] = round(time.perf_counter() - t0, 2)
         cv = out[system]["curve"]
         out[system]["gain"] = cv[-1][2] - cv[0][2]
     out["bar"] = BAR_FACTOR * out["ff_mappo"]["gain"]
@@ -108,8 +122,12 @@ class _CallCounter:
             setattr(self.lib, k, fn)
 
 
-def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None) -> dict:
-    c = dict(CURVE, env="rware", scenario="tiny-4ag", envs=envs_, rollout=128, updates_per_call=1, lr=2.5e-4, eval_envs=32)
+ACT_SYMBOLS = ("mava_transformer_act_f32", "mava_transformer_act_continuous_f32")
+
+
+def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None, continuous: bool = False) -> dict:
+    base = dict(CONT_CURVE_3A) if continuous else dict(CURVE, env="rware", scenario="tiny-4ag")
+    c = dict(base, envs=envs_, rollout=128, updates_per_call=1, lr=2.5e-4, eval_envs=32)
     if acting is not None:
         c["acting"] = acting
     cfg, learn, state, _ = _setup(system, dev, c)
@@ -133,7 +151,7 @@ def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None) -> di
         # T x (1 act + 1 env step) + the bootstrap's gather and encoder + the training calls
         per_act = 1 + len(L.roll.enc) + L.A * (2 + len(L.roll.dec))
         by = cc.by
-        rollout_calls = by.get("mava_transformer_act_f32", 0) + by.get(L.rep.env.step_symbol, 0) if L.acting == "fused" else L.T * (per_act + 1)
+        rollout_calls = sum(by.get(k, 0) for k in ACT_SYMBOLS) + by.get(L.rep.env.step_symbol, 0) if L.acting == "fused" else L.T * (per_act + 1)
         extra["layerwise_calls_per_act"] = per_act
         extra["library_calls_outside_rollout"] = cc.n - rollout_calls
         if L.acting == "fused":
@@ -214,6 +232,8 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--curve", action="store_true")
+    ap.add_argument("--continuous", action="store_true", help="the continuous action head on env=spread (CONT_CURVE)")
+    ap.add_argument("--calls", type=int, default=None, help="--curve: learn() calls (the budget), default the curve's")
     ap.add_argument("--acting", choices=("layerwise", "fused"), default=None, help="network.acting of ff_mat (default: the "
                     "config's in --curve mode, both settings otherwise)")
     ap.add_argument("--out", default=None)
@@ -222,8 +242,29 @@ def main() -> None:
         raise SystemExit("mat_bench.py measures on the GPU; no GPU found")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
+    if args.continuous and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mat_continuous_learning_curve.json" if args.curve else "mat_continuous_bench.json")
     if args.curve:
-        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True), acting=args.acting)
+        curve = CONT_CURVE if args.continuous else CURVE
+        if args.calls:
+            curve = dict(curve, calls=args.calls)
+        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True), acting=args.acting, curve=curve)
+        out["device"] = torch.cuda.get_device_name(0)
+        if args.continuous:
+            log = lambda m: print(m, file=sys.stderr, flush=True)
+            out["spread-3a"] = learning_run(dev, log=log, acting=args.acting, curve=dict(CONT_CURVE_3A, calls=curve["calls"]))
+            vf = dict(CONT_CURVE_3A, calls=curve["calls"])
+            vf["overrides"] = dict(vf["overrides"], ff_mat=vf["overrides"]["ff_mat"] + ["system.vf_coef=0.05"])
+            out["spread-3a, ff_mat at system.vf_coef=0.05"] = learning_curve("ff_mat", dev, log, vf)
+    elif args.continuous:
+        settings = [args.acting] if args.acting else ["layerwise", "fused"]
+        results = [update_cost("ff_mat", args.envs, dev, acting=a, continuous=True) for a in settings]
+        results.append(update_cost("ff_mappo", args.envs, dev, continuous=True))
+        out = {"device": torch.cuda.get_device_name(0), "workload": f"env=spread spread-3a x {args.envs} envs, continuous head, defaults",
+               "results": results}
+        by = {r.get("acting"): r for r in results if r["system"] == "ff_mat"}
+        if len(by) == 2:
+            out["fused_speedup_per_update"] = round(by["layerwise"]["ms_per_update"] / by["fused"]["ms_per_update"], 2)
     else:
         settings = [args.acting] if args.acting else ["layerwise", "fused"]
         results = [update_cost("ff_mat", args.envs, dev, acting=a) for a in settings] + [update_cost("ff_mappo", args.envs, dev)]
