@@ -256,6 +256,16 @@ int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int din, const 
 
 /* Both gradient kernels read MAVA_CTX_MATMUL_MODE, the critic also MAVA_CTX_CRITIC_AGGREGATION, from their handle. */
 
+/* Host only, no launch: 1 when a mava_ppo_actor_grad_f32 / mava_ppo_critic_grad_f32 call with this handle, input and record
+ * would stage its input from input16 whenever input16_valid reads 1; 0 when it would read the f32 input whatever the word
+ * says (another kernel takes the launch, alignment, input16_ld, MAVA_CTX_TRAIN_VARIANT, sharing / aggregation, a NULL
+ * record); negative on an argument error.  The launchers answer with the expression they launch by: the rule is stated once,
+ * in the library.  A caller that leaves the f32 input unwritten (mava_rollout_ff_flags_f32) asks here first. */
+int mava_ppo_actor_grad_reads_input16(const mava_ctx* ctx, int din, int n_actions, const float* agents_view, int A,
+                                      const uint16_t* input16, int input16_ld);
+int mava_ppo_critic_grad_reads_input16(const mava_ctx* ctx, int din, const float* critic_input, int x_share, int A,
+                                       const uint16_t* input16, int input16_ld);
+
 /* ---- synthetic RWARE-shaped environment (measurement stand-in for the third-party Jumanji
  *      RobotWarehouse stepped at mava/systems/ppo/ff_mappo.py:88).  Wrapper semantics follow
  *      mava/wrappers/observation.py:41-53, jumanji.py:53-59,128-143, auto_reset_wrapper.py:88-101
@@ -539,6 +549,39 @@ int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* c
                         uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
                         float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
                         uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, mava_stream_t s);
+/* mava_rollout_ff_f32 with flags (mava_rollout_ff_f32 is this entry point with flags 0; the twin is to be folded into one
+ * entry point at the next ABI bump).  A set bit leaves the f32 record of slots 1 .. T-1 of one array UNWRITTEN - the launch
+ * does not touch those bytes - where the f16 record of the same array holds the same values:
+ *   MAVA_ROLLOUT_SKIP_AGENTS_VIEW (bit 0): agents_view; needs view16 / view16_valid.
+ *   MAVA_ROLLOUT_SKIP_GLOBAL_STATE (bit 1): global_state; needs state16 / state16_valid.
+ * A bit without its record, or an unknown bit, is an argument error: nothing is launched.  Slot T is always written in f32,
+ * slot 0 stays the caller's, and every other output - both records and both words included - has the bits it has with
+ * flags 0.  The skipped slots are float(record) by the records' contract whatever the words say; the words say whether
+ * the gradient kernels may read the records INSTEAD of the f32 arrays.  A caller that skips therefore runs
+ * mava_rollout_expand_f32 (force 0) behind the launch - it rebuilds the slots only when a word is not 1 - and skips an
+ * array only when every gradient launch that follows would read its record (mava_ppo_actor_grad_reads_input16,
+ * mava_ppo_critic_grad_reads_input16). */
+#define MAVA_ROLLOUT_SKIP_AGENTS_VIEW 1u
+#define MAVA_ROLLOUT_SKIP_GLOBAL_STATE 2u
+int mava_rollout_ff_flags_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                              int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                              uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                              int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                              int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                              int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                              uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                              uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                              float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                              uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, uint32_t flags,
+                              mava_stream_t s);
+/* Slots 1 .. T-1 of the f32 arrays rebuilt from the f16 records of a fused rollout, in one launch: agents_view[t] = the
+ * conversion of halves [0, A+O) of every view16 row, global_state[t] = the conversion of state16[t] - exact, by the records'
+ * contract.  Each group (agents_view, view16, view16_valid) / (global_state, state16, state16_valid) is given whole or NULL
+ * whole.  force 0: an array is rebuilt only when its word is not 1 (read on the device, once per block: with 1 the launch
+ * does nothing); force != 0: always.  Slots 0 and T are not touched. */
+int mava_rollout_expand_f32(int T, int E, int A, int O, float* agents_view, const uint16_t* view16,
+                            const uint32_t* view16_valid, float* global_state, const uint16_t* state16,
+                            const uint32_t* state16_valid, int force, mava_stream_t s);
 /* The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of agents_view
  * (T+1, E, A, obs_dim) f32, global_state (T+1, E, gs_dim) f32 (NULL with gs_dim 0: none), action_mask (T+1, E, A,
  * n_actions) u8 and step_count (T+1, E, A) i32, in one launch.  Slots 1..T are not touched. */

@@ -84,6 +84,11 @@ _SIGNATURES = {
     "mava_sac_alpha_loss_f32": [i32, i32, vp, vp, f32, vp, vp, vp],
     "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
                            + [vp, vp, f32, f32] + [vp] * 7 + [vp],
+    "mava_rollout_ff_flags_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
+                                 + [vp, vp, f32, f32] + [vp] * 7 + [u32, vp],
+    "mava_rollout_expand_f32": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+    "mava_ppo_actor_grad_reads_input16": [vp, i32, i32, vp, i32, vp, i32],
+    "mava_ppo_critic_grad_reads_input16": [vp, i32, vp, i32, i32, vp, i32],
     "mava_rollout_carry": [i32, i32, i32, i32, lng, i32, vp, vp, vp, vp, vp],
     "mava_rec_dense_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mava_rec_xty_f32": [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, lng, i32, vp],

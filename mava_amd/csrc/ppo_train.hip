@@ -1007,6 +1007,47 @@ extern "C" int mava_adv_stats_blocks(void) { return STATS_BLOCKS; }
 int g_train_last_instance = 0;
 extern "C" int mava_debug_train_last_instance(void) { return g_train_last_instance; }
 
+thread_local int* g_x16_query = nullptr;  // (ppo_train_task.h)
+
+// What decides which kernel takes a gradient launch and whether it reads the f16 record, for a launch and for the question
+// "would it" alike (mava_ppo_actor_grad_reads_input16 / mava_ppo_critic_grad_reads_input16): the input, its width and
+// sharing, the head, the record.
+static TrainTask actor_task(const float* agents_view, int din, int n_actions, int A, const uint16_t* input16,
+                            const uint32_t* input16_valid, int input16_ld) {
+  TrainTask tk = {};
+  tk.x = agents_view; tk.din = din; tk.no = n_actions; tk.xshare = 1; tk.agg = 1;
+  tk.xv = pick_xv(agents_view, din); tk.A = A;
+  // (the f16 record of the input: only the eight-wave f16x2 kernel reads it, see ppo_train_task.h)
+  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
+  return tk;
+}
+static TrainTask critic_task(const mava_ctx* ctx, const float* critic_input, int din, int x_share, int A, const uint16_t* input16,
+                             const uint32_t* input16_valid, int input16_ld) {
+  TrainTask tk = {};
+  tk.x = critic_input; tk.din = din; tk.no = 1; tk.xshare = x_share; tk.agg = 1;
+  if (mava_ctx_critic_aggregation(ctx) && A > 1 && A <= 8 && x_share == A) {  // input row of index p is row p itself
+    tk.agg = A;
+    tk.xshare = 1;
+  }
+  tk.xv = pick_xv(critic_input, din); tk.A = A;
+  // (the f16 copy of the input: only the wide and the eight-wave f16x2 kernels read it, see ppo_train_task.h)
+  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
+  return tk;
+}
+// The answer for a task: the f16x2 launchers run their dispatch with g_x16_query set, and the one that would take the launch
+// answers with its own rule; the exact-f32 kernels (another arithmetic mode, a shape the f16x2 kernels do not instantiate)
+// never read a record.
+static int reads_x16(const mava_ctx* ctx, const TrainTask& tk, bool actor) {
+  int ans = 0;
+  if (mava_ctx_matmul_mode(ctx) == 1) {
+    g_x16_query = &ans;
+    const int rc = mava_train_h2_launch(const_cast<mava_ctx*>(ctx), tk, 1, actor, nullptr);  // (nothing of *ctx is written)
+    g_x16_query = nullptr;
+    if (rc < 0) return rc;
+  }
+  return ans;
+}
+
 extern "C" int mava_adv_stats_f64(const float* adv, const int32_t* idx, long idx_base, int Rb, int A,
                                   double* partials, hipStream_t s) {
   MAVA_ARG_CHECK(Rb >= 1 && A >= 1, 0, "mava_adv_stats_f64: Rb=%d A=%d", Rb, A);
@@ -1049,15 +1090,12 @@ extern "C" int mava_ppo_actor_grad_f32(mava_ctx* ctx, const float* params, int d
                  "mava_ppo_actor_grad_f32: null pointer argument");
   MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
                  "mava_ppo_actor_grad_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
-  TrainTask tk = {};
-  tk.params = params; tk.x = agents_view; tk.din = din; tk.no = n_actions; tk.xshare = 1; tk.agg = 1;
-  tk.xv = pick_xv(agents_view, din); tk.A = A; tk.idx = idx; tk.idx_base = idx_base; tk.Rb = Rb;
+  TrainTask tk = actor_task(agents_view, din, n_actions, A, input16, input16_valid, input16_ld);
+  tk.params = params; tk.idx = idx; tk.idx_base = idx_base; tk.Rb = Rb;
   tk.mask = action_mask; tk.action = action; tk.old_logp = old_log_prob; tk.adv = advantages;
   tk.stats = adv_stats; tk.clip_eps = clip_eps; tk.ent_coef = ent_coef; tk.slab = slab;
   tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
-  // (the f16 record of the input: only the eight-wave f16x2 kernel reads it, see ppo_train_task.h)
-  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
   if (mava_ctx_matmul_mode(ctx) == 1) {
     const int rc = mava_train_h2_launch(ctx, tk, n_slab, true, s);
     if (rc <= 0) return rc;  // launched (0) or failed (< 0); 1: shape not instantiated there
@@ -1114,21 +1152,35 @@ extern "C" int mava_ppo_critic_grad_f32(mava_ctx* ctx, const float* params, int 
                  "mava_ppo_critic_grad_f32: null pointer argument");
   MAVA_ARG_CHECK((input16 == nullptr) == (input16_valid == nullptr) && input16_ld >= 0, 3,
                  "mava_ppo_critic_grad_f32: input16 and input16_valid go together, input16_ld=%d", input16_ld);
-  TrainTask tk = {};
-  tk.params = params; tk.x = critic_input; tk.din = din; tk.no = 1; tk.xshare = x_share; tk.agg = 1;
-  if (mava_ctx_critic_aggregation(ctx) && A > 1 && A <= 8 && x_share == A) {  // input row of index p is row p itself
-    tk.agg = A;
-    tk.xshare = 1;
-  }
-  tk.xv = pick_xv(critic_input, din); tk.A = A; tk.idx = idx; tk.idx_base = idx_base; tk.Rb = Rb;
+  TrainTask tk = critic_task(ctx, critic_input, din, x_share, A, input16, input16_valid, input16_ld);
+  tk.params = params; tk.idx = idx; tk.idx_base = idx_base; tk.Rb = Rb;
   tk.old_value = old_value; tk.targets = targets; tk.clip_eps = clip_eps; tk.vf_coef = vf_coef;
   tk.slab = slab; tk.slab_stride = slab_stride;
   tk.stamps = g_stamps;
-  // (the f16 copy of the input: only the wide and the eight-wave f16x2 kernels read it, see ppo_train_task.h)
-  tk.x16 = reinterpret_cast<const _Float16*>(input16); tk.x16_valid = input16_valid; tk.x16_ld = input16_ld;
   int rc = 1;
   if (mava_ctx_matmul_mode(ctx) == 1) rc = mava_train_h2_launch(ctx, tk, n_slab, false, s);
   if (ctx != nullptr) ctx->w1_fresh[1] = 0;  // one-shot whichever kernel takes the launch (the exact-f32 one does not read the copy)
   if (rc <= 0) return rc;
   return dispatch_kt<1, false>(tk, n_slab, s);
+}
+
+// Host only: 1 when a mava_ppo_actor_grad_f32 / mava_ppo_critic_grad_f32 launch with this handle, this input and this record
+// would stage its input from input16 whenever the record's validity word reads 1, else 0 (include/mava_hip.h).  The word is
+// not an argument: whoever asks holds one.
+extern "C" int mava_ppo_actor_grad_reads_input16(const mava_ctx* ctx, int din, int n_actions, const float* agents_view, int A,
+                                                 const uint16_t* input16, int input16_ld) {
+  MAVA_ARG_CHECK(din >= 1 && n_actions >= 1 && n_actions <= 32 && A >= 1 && input16_ld >= 0, 0,
+                 "mava_ppo_actor_grad_reads_input16: din=%d n_actions=%d A=%d input16_ld=%d", din, n_actions, A, input16_ld);
+  if (input16 == nullptr) return 0;
+  static const uint32_t word = 0;  // (a launch needs both pointers; the rule never reads through this one)
+  return reads_x16(ctx, actor_task(agents_view, din, n_actions, A, input16, &word, input16_ld), true);
+}
+
+extern "C" int mava_ppo_critic_grad_reads_input16(const mava_ctx* ctx, int din, const float* critic_input, int x_share, int A,
+                                                  const uint16_t* input16, int input16_ld) {
+  MAVA_ARG_CHECK(din >= 1 && x_share >= 1 && A >= 1 && input16_ld >= 0, 0,
+                 "mava_ppo_critic_grad_reads_input16: din=%d x_share=%d A=%d input16_ld=%d", din, x_share, A, input16_ld);
+  if (input16 == nullptr) return 0;
+  static const uint32_t word = 0;
+  return reads_x16(ctx, critic_task(ctx, critic_input, din, x_share, A, input16, &word, input16_ld), false);
 }

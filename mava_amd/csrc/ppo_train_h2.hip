@@ -1340,6 +1340,14 @@ int ctx_counters(mava_ctx* ctx, hipStream_t s) {
 
 template <int NO, int S1, bool ACTOR, bool WIDE, int XV>
 int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
+  // the f16 copy of x: handed to the kernel only where it has the second staging form and the copy fits it (16-byte pieces of
+  // 16-byte aligned rows, no forced x_lo products); whether the copy is VALID is the kernel's own look at the device word
+  const bool x16_ok = WIDE && !ACTOR && XV == 4 && tk.x16 != nullptr && tk.x16_valid != nullptr && tk.din % 8 == 0 &&
+                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && (tk.x16_ld == 0 || tk.x16_ld == tk.din);
+  if (g_x16_query != nullptr) {  // (the rule asked, not a launch: ppo_train_task.h)
+    *g_x16_query = x16_ok ? 1 : 0;
+    return MAVA_OK;
+  }
   const H2Layout L = make_h2_layout<NO, S1, WIDE>(ACTOR);
   MAVA_ARG_CHECK(L.end <= 163840, 8, "ppo_train_h2: %d bytes of LDS exceed the 160 KiB of a CU", L.end);
   static bool attr_set = false;
@@ -1368,10 +1376,6 @@ int launch_h2(mava_ctx* ctx, const TrainTask& tk, int n_slab, hipStream_t s) {
   }
   TrainTask tkl = tk;
   tkl.exact_tiles = WIDE ? ctx->exact_tiles : nullptr;
-  // the f16 copy of x: handed to the kernel only where it has the second staging form and the copy fits it (16-byte pieces of
-  // 16-byte aligned rows, no forced x_lo products); whether the copy is VALID is the kernel's own look at the device word
-  const bool x16_ok = WIDE && !ACTOR && XV == 4 && tk.x16 != nullptr && tk.x16_valid != nullptr && tk.din % 8 == 0 &&
-                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && (tk.x16_ld == 0 || tk.x16_ld == tk.din);
   if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; }
   tkl.x16_launches = x16_ok ? ctx->exact_tiles + 1 : nullptr;  // (the second word of the handle's counter allocation)
   g_train_last_instance = train_instance_id(2, ACTOR, false, WIDE, NO, S1, XV);
@@ -1436,7 +1440,7 @@ int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk_in, int n_slab, bool
   tk.no_defer = (ctx->train_variant & 4) != 0;
   tk.no_ahead = (ctx->train_variant & 8) != 0;
   if ((ctx->train_variant & 1) == 0) {  // the eight-wave kernel: the discrete actor and the value network on narrow inputs
-    if (tk.x16 != nullptr && tk.x16_valid != nullptr) {  // (its launches on the f16 record are counted in the third word)
+    if (tk.x16 != nullptr && tk.x16_valid != nullptr && g_x16_query == nullptr) {  // (its launches on the f16 record are counted in the third word)
       const int rcc = ctx_counters(ctx, s);
       if (rcc != MAVA_OK) return rcc;
       tk.x16_launches = ctx->exact_tiles + 2;
@@ -1445,11 +1449,11 @@ int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk_in, int n_slab, bool
     }
     const int rc8 = mava_train_w8_launch(tk, n_slab, actor, s);
     if (rc8 <= 0) {
-      if (rc8 == 0) { ++ctx->h2_launches; ++ctx->w8_launches; }
+      if (rc8 == 0 && g_x16_query == nullptr) { ++ctx->h2_launches; ++ctx->w8_launches; }
       return rc8;
     }
   }
   const int rc = h2_dispatch(ctx, tk, n_slab, actor, s);
-  if (rc == 0) ++ctx->h2_launches;
+  if (rc == 0 && g_x16_query == nullptr) ++ctx->h2_launches;
   return rc;
 }

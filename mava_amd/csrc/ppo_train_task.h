@@ -62,6 +62,12 @@ struct mava_ctx;
 int mava_train_w8_launch(const TrainTask& tk, int n_slab, bool actor, hipStream_t s);
 int mava_train_h2_launch(mava_ctx* ctx, const TrainTask& tk, int n_slab, bool actor, hipStream_t s);
 
+// The launch rule of the f16 record, asked without launching (mava_ppo_*_grad_reads_input16): while this thread's pointer is
+// set, the launchers above go through their dispatch as for a launch, and the launcher that would take the task stores ITS OWN
+// x16_ok - would this launch read x16 if the word is 1 - there and returns MAVA_OK with no launch, allocation or counter touched.
+// One rule: the expression the launch itself hands the record to the kernel by.
+extern thread_local int* g_x16_query;
+
 // Diagnostic (ppo_train.hip: mava_debug_train_last_instance): the template instance the last gradient launch of this
 // process used, as FAMILY * 1000000 + ROLE * 100000 + NO * 1000 + K * 10 + XV - FAMILY 1: ppo_train_kernel (exact f32, K = KT1),
 // 2: ppo_train_h2_kernel (K = S1), 3: ppo_train_w8_kernel (K = S1); ROLE = ACTOR + 2 * CONT + 4 * WIDE.

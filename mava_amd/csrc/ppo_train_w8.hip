@@ -1031,6 +1031,16 @@ __global__ __launch_bounds__(512, 2) void ppo_train_w8_kernel(TrainTask tk, W8La
 
 template <int NO, int S1, int XV, bool ACTOR>
 int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
+  // the f16 record of x: handed to the kernel only where it has the second staging form and the record fits it (rows of whole
+  // 16-byte chunks on a 16-byte aligned base that hold at least the din values, one input row per agent row, no forced x_lo
+  // products); whether the record is VALID is the kernel's own look at the device word
+  const int ld16 = tk.x16_ld != 0 ? tk.x16_ld : tk.din;
+  const bool x16_ok = XV == 2 && tk.x16 != nullptr && tk.x16_valid != nullptr && ld16 % 8 == 0 && ld16 >= tk.din &&
+                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && tk.xshare == 1 && tk.agg <= 1;
+  if (g_x16_query != nullptr) {  // (the rule asked, not a launch: ppo_train_task.h)
+    *g_x16_query = x16_ok ? 1 : 0;
+    return MAVA_OK;
+  }
   const W8Layout L = make_w8_layout();
   MAVA_ARG_CHECK(L.end <= 163840, 8, "ppo_train_w8: %d bytes of LDS exceed the 160 KiB of a CU", L.end);
   static bool attr_set = false;
@@ -1039,13 +1049,7 @@ int launch_w8(const TrainTask& tk, int n_slab, hipStream_t s) {
                                        L.end));
     attr_set = true;
   }
-  // the f16 record of x: handed to the kernel only where it has the second staging form and the record fits it (rows of whole
-  // 16-byte chunks on a 16-byte aligned base that hold at least the din values, one input row per agent row, no forced x_lo
-  // products); whether the record is VALID is the kernel's own look at the device word
   TrainTask tkl = tk;
-  const int ld16 = tk.x16_ld != 0 ? tk.x16_ld : tk.din;
-  const bool x16_ok = XV == 2 && tk.x16 != nullptr && tk.x16_valid != nullptr && ld16 % 8 == 0 && ld16 >= tk.din &&
-                      (uintptr_t)tk.x16 % 16 == 0 && tk.force_xlo == 0 && tk.xshare == 1 && tk.agg <= 1;
   tkl.x16_ld = ld16;
   if (!x16_ok) { tkl.x16 = nullptr; tkl.x16_valid = nullptr; tkl.x16_launches = nullptr; tkl.defer_launches = nullptr; tkl.ahead_launches = nullptr; }
   g_train_last_instance = train_instance_id(3, ACTOR, false, false, NO, S1, XV);

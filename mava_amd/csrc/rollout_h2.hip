@@ -82,7 +82,12 @@ struct RolloutArgs {
   // validity word, same protocol as state16_valid.
   _Float16* view16; uint32_t* view16_valid;
   int v16_nc; uint32_t v16_nc_m;  // RP / 8 and its div_small factor (64 rows x v16_nc chunks: 64 * 16 * 16 < 65536)
+  // MAVA_ROLLOUT_SKIP_*: the f32 records of slots 1 .. T - 1 this launch leaves unwritten (their f16 records hold the same
+  // values); and A O / 8 with its div_small factor, for the state16 copy's own loop
+  uint32_t flags;
+  int s16_nc; uint32_t s16_nc_m;
 };
+constexpr uint32_t SKIP_VIEW = 1u, SKIP_STATE = 2u;  // MAVA_ROLLOUT_SKIP_AGENTS_VIEW / _GLOBAL_STATE (include/mava_hip.h)
 
 // The kernel's arguments read again from the argument segment AT THE POINT OF USE.  The ~40 pointers and seeds of
 // RolloutArgs are loaded at the kernel's entry when they are used through the by-value parameter, and whatever the step
@@ -508,11 +513,20 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
   // quad loop's cursors: the lane of an even quad k also moves the 16 bytes of quads k and k + 1 (A O % 8 == 0, the launcher's
   // check: a row is a whole number of such pairs and pair j / 2 of the block is piece j / 2 of the record) - one 16-byte LDS
   // read and one 16-byte store, consecutive even lanes on consecutive pieces; no cursor or factor of its own.
-  auto write_gs = [&](long slot, bool f32_too) {
+  // (lean: a slot whose f32 record the launch skips - the halves alone, in a loop of their own over the record's 16-byte chunks
+  // like write_view16's: half the iterations of the quad loop's even lanes)
+  auto write_gs = [&](long slot, bool f32_too, bool lean) {
     const auto& a = args_here();  // (shadows the parameter: see args_here)
     int tid = tid_w;
     asm volatile("" : "+v"(tid));
-    if (SHARED && a.global_state != nullptr) {
+    if (SHARED && lean) {
+      const int NC = a.s16_nc;
+      uint4* const dst16 = reinterpret_cast<uint4*>(a.state16 + (slot * E + e0) * (long)AO);
+      for (int j = tid; j < envs_ok * NC; j += 256) {
+        const int le = (int)div_small((uint32_t)j, a.s16_nc_m), c = j - le * NC;
+        dst16[j] = *reinterpret_cast<const uint4*>(lds + L.xc + le * xc_row + 16 * c);
+      }
+    } else if (SHARED && a.global_state != nullptr) {
       float* dst = a.global_state + (slot * E + e0) * (long)AO;
       if ((AO & 3) == 0) {  // quads: 8-byte LDS reads, 16-byte stores
         const bool h16 = a.state16 != nullptr;
@@ -558,13 +572,16 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
       }
     }
   };
-  auto write_out = [&](long slot, bool part_gs) {  // part_gs: the global state (actor group, after sampling); else the rest
+  // (last: slot T, the bootstrap observation - always recorded in f32 too; the f32 record of an earlier slot only when the
+  // launch's flags do not skip that array: wave-uniform branches on a word fetched here)
+  auto write_out = [&](long slot, bool part_gs, bool last) {  // part_gs: the global state (actor group, after sampling); else the rest
     const auto& a = args_here();  // (shadows the parameter: see args_here)
+    const uint32_t skip = last ? 0u : a.flags;
     // The cursors' start values depend on the thread alone.  Computed from a thread id the compiler cannot see through,
     // they are two instructions here (div_small) instead of registers held, and on the critic waves spilled, over the loop.
     int tid = tid_w;
     asm volatile("" : "+v"(tid));
-    if (!part_gs) {
+    if (!part_gs && (skip & SKIP_VIEW) == 0) {
       float* dst = a.agents_view + (slot * EA + (long)e0 * A) * W;
       if ((W & 1) == 0) {  // pairs: 4-byte LDS reads, 8-byte stores (row bases are multiples of 8 bytes)
         const int W2 = W >> 1, d_r = wo_dr, d_f = 256 - d_r * W2;
@@ -592,7 +609,11 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
       }
     }
     if (!part_gs) write_view16(slot);
-    if (part_gs) write_gs(slot, true);
+    // the global state: with its f32 record the actor group's, after sampling; the halves alone are the critic group's, here in
+    // the sample phase, where it has little else left to do (before barrier 3 the shared critic's image is as stable as the
+    // actor's): measured against the actor group's place, 5.856 -> 5.819 ms per update (profiles/README.md, lean_*)
+    if (part_gs && (skip & SKIP_STATE) == 0) write_gs(slot, true, false);
+    if (!part_gs && (skip & SKIP_STATE) != 0) write_gs(slot, true, true);
     if (!part_gs) {
       uint8_t* dst = a.action_mask + (slot * EA + (long)e0 * A) * no;
       for (int j = tid; j < rows_ok * no; j += 256) {
@@ -604,7 +625,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
 
   const int T_steps = a.T;
   const uint32_t t0 = a.t0;
-  if (SHARED && ACT_ROLE && a.state16 != nullptr) write_gs(0L, false);  // slot 0 of the f16 copy: the image the prologue filled from memory
+  if (SHARED && ACT_ROLE && a.state16 != nullptr) write_gs(0L, false, false);  // slot 0 of the f16 copy: the image the prologue filled from memory
   if (!ACT_ROLE) write_view16(0L);  // slot 0 of view16, likewise (the group that writes its other slots)
   for (int t = 0; t < T_steps; ++t) {
     const uint32_t step = t0 + (uint32_t)t;
@@ -659,9 +680,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
       if (tid < 64 && (e0 + (tid >> lgA)) < E) {
         a.value[(long)t * EA + (long)e0 * A + tid] = value_of(SHARED ? (tid >> lgA) : tid);
       }
-      if (t > 0) write_out((long)t, false);  // slot t = what the env phase of step t - 1 produced (slot 0 came from memory)
+      if (t > 0) write_out((long)t, false, false);  // slot t = what the env phase of step t - 1 produced (slot 0 came from memory)
     }
-    if (ACT_ROLE && t > 0) write_out((long)t, true);
+    if (ACT_ROLE && t > 0) write_out((long)t, true, false);
     RSTAMP(4);
     __syncthreads();  // barrier 3: actions visible to the env phase; every reader of the x images is done
     RSTAMP(5);
@@ -783,7 +804,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, u8* lds) {
     for (int i = 0; i < 8; ++i) g_rollout_stamps[(ACT_ROLE ? 0 : 8) + i] = rs_acc[i];
 #endif
   // ------------------------------------------------------------------ bootstrap value (ff_mappo.py:109-110)
-  write_out((long)T_steps, ACT_ROLE);  // the last observation
+  write_out((long)T_steps, ACT_ROLE, true);  // the last observation
   forward(!ACT_ROLE, false, 0u);
   {
   const auto& a = args_here();  // (the tail's pointers are fetched here, not carried through the loop)
@@ -912,17 +933,19 @@ extern "C" int mava_debug_get_rollout_stamps(unsigned long long* out16) {
 extern "C" int mava_debug_rollout_last_instance(void) { return g_rollout_last_instance; }
 
 // The fused rollout (include/mava_hip.h).  Each optional group of outputs may be null on its own: last_reward / last_done
-// (and step_counter, only with them), state16 / state16_valid, view16 / view16_valid.
-extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
-                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
-                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
-                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
-                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
-                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
-                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
-                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
-                                   float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
-                                   uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, hipStream_t s) {
+// (and step_counter, only with them), state16 / state16_valid, view16 / view16_valid.  flags: MAVA_ROLLOUT_SKIP_*, each
+// refused here without its record.
+extern "C" int mava_rollout_ff_flags_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                                         int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                                         uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                                         int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                         int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                         int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                                         uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                                         uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                         float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                         uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, uint32_t flags,
+                                         hipStream_t s) {
   MAVA_ARG_CHECK(E >= 1 && A >= 1 && O >= 2 && T >= 1 && n_actions >= 1 && time_limit >= 1, 0,
                  "mava_rollout_ff_f32: bad shape E=%d A=%d O=%d T=%d nA=%d", E, A, O, T, n_actions);
   MAVA_ARG_CHECK(actor_params && critic_params && step_count && run_return && run_length && ep_return && ep_length &&
@@ -956,6 +979,16 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
   MAVA_ARG_CHECK(view16 == nullptr || (uintptr_t)view16 % 16 == 0, 2, "mava_rollout_ff_f32: view16 needs 16-byte alignment");
   a.view16 = reinterpret_cast<_Float16*>(view16); a.view16_valid = view16_valid;
   a.v16_nc = (A + O + 8) / 8; a.v16_nc_m = 65536u / (uint32_t)a.v16_nc + 1u;
+  MAVA_ARG_CHECK((flags & ~(SKIP_VIEW | SKIP_STATE)) == 0, 3, "mava_rollout_ff_flags_f32: unknown flags 0x%x", flags);
+  MAVA_ARG_CHECK((flags & SKIP_VIEW) == 0 || (view16 != nullptr && view16_valid != nullptr), 3,
+                 "mava_rollout_ff_flags_f32: MAVA_ROLLOUT_SKIP_AGENTS_VIEW needs view16 and view16_valid");
+  MAVA_ARG_CHECK((flags & SKIP_STATE) == 0 || (state16 != nullptr && state16_valid != nullptr), 3,
+                 "mava_rollout_ff_flags_f32: MAVA_ROLLOUT_SKIP_GLOBAL_STATE needs state16 and state16_valid");
+  a.flags = flags;
+  a.s16_nc = state16 != nullptr ? A * O / 8 : 1; a.s16_nc_m = 65536u / (uint32_t)a.s16_nc + 1u;
+  // (div_small in the state16 loop: (64 / A) s16_nc chunks of a block, divided by s16_nc)
+  MAVA_ARG_CHECK((flags & SKIP_STATE) == 0 || (64 / A) * a.s16_nc * a.s16_nc < 65536, 3,
+                 "mava_rollout_ff_flags_f32: A*O=%d too wide for MAVA_ROLLOUT_SKIP_GLOBAL_STATE", A * O);
   if (critic_shared) {
     if (s1a == 5 && s1c == 17 && A >= 4) return launch_rollout<8, 5, 17, true>(a, s);  // RWARE tiny / small-4ag (O 66, A 4)
 #ifndef MAVA_FAST_BUILD
@@ -970,6 +1003,114 @@ extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, con
   if (s1a <= 2) return launch_rollout<8, 2, 2, false>(a, s);
 #endif
   return 1;
+}
+
+extern "C" int mava_rollout_ff_f32(const float* actor_params, int n_actions, const float* critic_params, int critic_shared,
+                                   int E, int A, int O, int T, int time_limit, uint64_t policy_seed, uint64_t env_seed,
+                                   uint32_t t0, uint32_t row_offset, uint32_t env_offset, int reward_mode,
+                                   int32_t* step_count, float* run_return, int32_t* run_length, float* ep_return,
+                                   int32_t* ep_length, float* agents_view, float* global_state, uint8_t* action_mask,
+                                   int32_t* obs_step_count, int32_t* action, float* value, float* reward, float* log_prob,
+                                   uint8_t* done, float* last_val, float* info_return, int32_t* info_length,
+                                   uint8_t* info_terminal, float* adv, float* tgt, float gamma, float gae_lambda,
+                                   float* last_reward, uint8_t* last_done, int32_t* step_counter, uint16_t* state16,
+                                   uint32_t* state16_valid, uint16_t* view16, uint32_t* view16_valid, hipStream_t s) {
+  return mava_rollout_ff_flags_f32(actor_params, n_actions, critic_params, critic_shared, E, A, O, T, time_limit, policy_seed, env_seed, t0, row_offset, env_offset, reward_mode, step_count, run_return, run_length, ep_return, ep_length, agents_view, global_state, action_mask, obs_step_count, action, value, reward, log_prob, done, last_val, info_return, info_length, info_terminal, adv, tgt, gamma, gae_lambda, last_reward, last_done, step_counter, state16, state16_valid, view16, view16_valid, 0u, s);
+}
+
+// The f32 records of slots 1 .. T - 1 rebuilt from the f16 records (include/mava_hip.h, mava_rollout_expand_f32): by the
+// records' contract the f32 trajectory is the image converted, so float(half) of the first `w` halves of every record row IS
+// the f32 row.  blockIdx.y = array (0: agents_view from view16, 1: global_state from state16).  A block takes tiles of 64
+// record rows: the tile's halves go to LDS in 16-byte pieces, consecutive lanes on consecutive pieces, and leave as the tile's
+// contiguous run of floats, in 16-byte stores where the destination allows (a tile starts a multiple of four floats into the
+// array), one float at a time otherwise.  force == 0: an array is rebuilt only when its validity word is not 1 - the gradient
+// kernels then read the f32 trajectory - and with the word at 1 a block leaves after that one scalar load.
+namespace {
+struct ExpandArgs {
+  const _Float16* src[2];   // record of slot 1, rows ld halves apart
+  float* dst[2];            // f32 array, slot 1
+  const uint32_t* word[2];
+  long rows[2];             // record rows of slots 1 .. T - 1
+  int ld[2], w[2];          // halves per record row, floats per f32 row (w <= ld, ld % 8 == 0)
+  int force;
+};
+constexpr int EXPAND_ROWS = 64;      // record rows per tile
+constexpr int EXPAND_LD_MAX = 288;   // LDS tile: 64 rows x 288 halves = 36 KiB
+__global__ __launch_bounds__(256) void rollout_expand_kernel(ExpandArgs x) {
+  __shared__ __attribute__((aligned(16))) _Float16 tile[EXPAND_ROWS * EXPAND_LD_MAX];
+  const int k = blockIdx.y;
+  if (x.src[k] == nullptr) return;
+  if (x.force == 0 && __builtin_amdgcn_readfirstlane((int)*x.word[k]) == 1) return;
+  const int ld = x.ld[k], w = x.w[k], nc = ld >> 3;
+  const long rows = x.rows[k], tiles = (rows + EXPAND_ROWS - 1) / EXPAND_ROWS;
+  const bool wide = (reinterpret_cast<uintptr_t>(x.dst[k]) & 15) == 0;
+  for (long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+    const long row0 = tl * EXPAND_ROWS;
+    const int nr = (int)(rows - row0 < EXPAND_ROWS ? rows - row0 : EXPAND_ROWS);  // (the last tile may be partial)
+    const uint4* const src = reinterpret_cast<const uint4*>(x.src[k] + row0 * ld);
+    for (int j = threadIdx.x; j < nr * nc; j += 256) reinterpret_cast<uint4*>(tile)[j] = src[j];
+    __syncthreads();
+    float* const dst = x.dst[k] + row0 * w;
+    const int n = nr * w;  // floats of the tile
+    if (wide) {
+      for (int q = threadIdx.x; 4 * q < n; q += 256) {
+        int r = (4 * q) / w, c = 4 * q - r * w;
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          v[i] = (4 * q + i < n) ? (float)tile[r * ld + c] : 0.0f;
+          if (++c == w) { c = 0; ++r; }
+        }
+        if (4 * q + 4 <= n) {
+          reinterpret_cast<float4*>(dst)[q] = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+          for (int i = 0; 4 * q + i < n; ++i) dst[4 * q + i] = v[i];
+        }
+      }
+    } else {
+      for (int e = threadIdx.x; e < n; e += 256) {
+        const int r = e / w, c = e - r * w;
+        dst[e] = (float)tile[r * ld + c];
+      }
+    }
+    __syncthreads();  // the tile is read before the next one is loaded
+  }
+}
+}  // namespace
+
+extern "C" int mava_rollout_expand_f32(int T, int E, int A, int O, float* agents_view, const uint16_t* view16,
+                                       const uint32_t* view16_valid, float* global_state, const uint16_t* state16,
+                                       const uint32_t* state16_valid, int force, hipStream_t s) {
+  MAVA_ARG_CHECK(T >= 1 && E >= 1 && A >= 1 && O >= 1, 0, "mava_rollout_expand_f32: bad shape T=%d E=%d A=%d O=%d", T, E, A, O);
+  MAVA_ARG_CHECK((agents_view == nullptr) == (view16 == nullptr) && (view16 == nullptr) == (view16_valid == nullptr), 1,
+                 "mava_rollout_expand_f32: agents_view, view16 and view16_valid go together");
+  MAVA_ARG_CHECK((global_state == nullptr) == (state16 == nullptr) && (state16 == nullptr) == (state16_valid == nullptr), 1,
+                 "mava_rollout_expand_f32: global_state, state16 and state16_valid go together");
+  MAVA_ARG_CHECK(view16 != nullptr || state16 != nullptr, 1, "mava_rollout_expand_f32: no record given");
+  MAVA_ARG_CHECK(((uintptr_t)view16 | (uintptr_t)state16) % 16 == 0, 2, "mava_rollout_expand_f32: the records need 16-byte alignment");
+  const int W = A + O, RP = 8 * ((W + 8) / 8), AO = A * O;
+  MAVA_ARG_CHECK(state16 == nullptr || AO % 8 == 0, 2, "mava_rollout_expand_f32: state16 needs A*O %% 8 == 0 (A*O=%d)", AO);
+  MAVA_ARG_CHECK((view16 == nullptr || RP <= EXPAND_LD_MAX) && (state16 == nullptr || AO <= EXPAND_LD_MAX), 2,
+                 "mava_rollout_expand_f32: record rows of more than %d halves are not supported", EXPAND_LD_MAX);
+  if (T < 2) return MAVA_OK;  // (no slot between 0 and T)
+  ExpandArgs x = {};
+  x.force = force ? 1 : 0;
+  long most = 0;
+  if (view16 != nullptr) {
+    const long EA = (long)E * A;
+    x.src[0] = reinterpret_cast<const _Float16*>(view16) + EA * RP; x.dst[0] = agents_view + EA * W; x.word[0] = view16_valid;
+    x.rows[0] = (long)(T - 1) * EA; x.ld[0] = RP; x.w[0] = W;
+    most = x.rows[0];
+  }
+  if (state16 != nullptr) {
+    x.src[1] = reinterpret_cast<const _Float16*>(state16) + (long)E * AO; x.dst[1] = global_state + (long)E * AO; x.word[1] = state16_valid;
+    x.rows[1] = (long)(T - 1) * E; x.ld[1] = AO; x.w[1] = AO;
+    most = x.rows[1] > most ? x.rows[1] : most;
+  }
+  const long tiles = mava_cdiv(most, (long)EXPAND_ROWS);
+  hipLaunchKernelGGL(rollout_expand_kernel, dim3((unsigned)(tiles > 2048 ? 2048 : tiles), 2), dim3(256), 0, s, x);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
 }
 
 // The bootstrap observation becomes the first observation of the next rollout: slot T -> slot 0 of the four observation

@@ -37,14 +37,14 @@ import torch
 
 from . import ops, parallel, ppo_learner
 from .networks import FeedForwardActor, FeedForwardValueNet, MLPTorso
-from .ppo_learner import PPOLearner
+from .ppo_learner import LeanReplica, PPOLearner
 from .types import LearnerState, TimeStep
 
 
 class FFLearner(PPOLearner):
     def __init__(self, env, config, centralised_critic: bool, device: Optional[torch.device] = None):
         # (critic aggregation is a setting of the learner's context handle, like the arithmetic mode: mava_ctx_*)
-        super().__init__(env, config, centralised_critic, device,
+        super().__init__(env, config, centralised_critic, device, replica=LeanReplica,
                          ctx_kwargs={"critic_aggregation": os.environ.get("MAVA_CRITIC_AGGREGATION", "1") != "0"})
         s, env0, action_head = config.system, self.reps[0].env, self.action_head
 
@@ -125,6 +125,12 @@ class FFLearner(PPOLearner):
         for rep in self.reps:
             rep.view16 = torch.zeros((self.T + 1, self.E, self.A, rp), dtype=torch.float16, device=d) if self.view16 else None
             rep.view16_valid = torch.zeros((1,), dtype=torch.int32, device=d) if self.view16 else None
+        # With a record active, every gradient launch of an update reads it instead of the f32 array whenever its word is 1, which
+        # on the environment's own observations it always is: the rollout is then told to leave slots 1 .. T - 1 of that f32 array
+        # unwritten (_reads_records asks the library whether the launches will read the record; the rule is the library's), and a
+        # conditional expand behind it rebuilds them on the device should a word ever end 0.  A host read of the skipped slots goes
+        # through LeanReplica's properties.  MAVA_ROLLOUT_LEAN=0 writes everything as before (A/B runs, tests).
+        self.lean = os.environ.get("MAVA_ROLLOUT_LEAN", "1") != "0"
         # One rank: nothing sits between the gradient kernels and Adam, so both slab sums, clip + Adam, the count increment and
         # the wide critic's W1 re-split run as TWO launches (ops.ppo_finish) instead of six.  With several replicas every
         # replica's gradient kernels write their own rows of the slab matrices and the one sum runs over all U * n_slab rows
@@ -240,19 +246,28 @@ class FFLearner(PPOLearner):
                 st.wait_stream(main)
         for u, rep in enumerate(self.reps):
             env = rep.env
+            skip_av, skip_gs = self._reads_records(rep) if self.lean else (False, False)
             with (torch.cuda.stream(self._roll_streams[u - 1]) if (side and u > 0) else contextlib.nullcontext()):
               ok = self._timed(
                 "rollout_fused", ops.rollout_ff, pa, pc, n_actions=self.nA, critic_shared=self.centralised, E=self.E,
                 A=self.A, O=env.raw_obs_dim, T=self.T, time_limit=env.time_limit, policy_seed=self.seed,
                 env_seed=env.seed, t0=self.t_global, row_offset=(self.rank * self.U + u) * EA, env_offset=env.env_offset,
-                reward_mode=1 if env.reward_mode == "match" else 0, env_state=rep.state, agents_view=rep.agents_view,
-                global_state=rep.global_state, action_mask=rep.action_mask, obs_step_count=rep.step_count,
+                reward_mode=1 if env.reward_mode == "match" else 0, env_state=rep.state, agents_view=rep.av_raw,
+                global_state=rep.gs_raw, action_mask=rep.action_mask, obs_step_count=rep.step_count,
                 action=rep.action, value=rep.value, reward=rep.reward, log_prob=rep.log_prob, done=rep.done,
                 last_val=rep.last_val, info_return=rep.info_return[n], info_length=rep.info_length[n],
                 info_terminal=rep.info_terminal[n], adv=rep.adv, tgt=rep.tgt, gamma=float(s.gamma),
                 gae_lambda=float(s.gae_lambda), last_reward=rep.last_reward, last_done=rep.last_done,
                 step_counter=self.step_dev if u == 0 else None,  # (the launch leaves all three: nothing follows it)
-                state16=rep.state16, state16_valid=rep.state16_valid, view16=rep.view16, view16_valid=rep.view16_valid)
+                state16=rep.state16, state16_valid=rep.state16_valid, view16=rep.view16, view16_valid=rep.view16_valid,
+                skip_agents_view=skip_av, skip_global_state=skip_gs)
+              if ok and (skip_av or skip_gs):
+                # a word that ended 0 (a slot-0 value with a low f16 term) sends the gradient launches back to the f32 arrays:
+                # the launch looks at the words itself and does nothing when they are 1
+                self._timed("rollout_expand", ops.rollout_expand, rep.av_raw if skip_av else None, rep.view16 if skip_av else None,
+                            rep.view16_valid if skip_av else None, rep.gs_raw if skip_gs else None, rep.state16 if skip_gs else None,
+                            rep.state16_valid if skip_gs else None, force=False)
+                rep.stale_av, rep.stale_gs = rep.stale_av or skip_av, rep.stale_gs or skip_gs
               if not ok:
                 assert u == 0
                 self.fused_rollout = self.x16 = self.view16 = False
@@ -263,6 +278,28 @@ class FFLearner(PPOLearner):
             for st in self._roll_streams:
                 main.wait_stream(st)
         return True
+
+    def _reads_records(self, rep) -> Tuple[bool, bool]:
+        """(agents_view, global_state): does EVERY gradient launch of an update that takes the f32 array also take its f16 record
+        and, by the library's own launch rule, read the record whenever its word is 1?  Same arguments as _minibatch's launches."""
+        T, TEA = self.T, self.T * self.E * self.A
+        av = rep.av_raw[:T].view(TEA, self.Oa)
+        v16 = rep.view16[:T].view(TEA, -1) if self.view16 else None
+        reads_av = v16 is not None and ops.ppo_actor_grad_reads_input16(self.ctx, av, self.nA, self.A, v16)
+        reads_gs = False
+        if self.centralised:
+            reads_gs = self.x16 and ops.ppo_critic_grad_reads_input16(
+                self.ctx, rep.gs_raw[:T].view(-1, self.Oc), self.critic_share, self.A, rep.state16[:T].view(-1, self.Oc))
+        elif reads_av:  # (the critic's input is agents_view too)
+            reads_av = self.critic_share == 1 and ops.ppo_critic_grad_reads_input16(self.ctx, av, 1, self.A, v16)
+        return bool(reads_av), bool(reads_gs)
+
+    def _lean_guard(self, rep) -> None:
+        """Before a gradient launch: the answer the rollout skipped by ("yes", for a stale array) must still hold - the handle's
+        settings can change in between; an array whose record would no longer be read is rebuilt first."""
+        if rep.stale_av or rep.stale_gs:
+            now = self._reads_records(rep)
+            rep.materialise(av=not now[0], gs=not now[1])
 
     def _rollout_body(self) -> None:
         """ff_mappo.py:76-106: T acting steps, recording the time-major trajectory in place."""
@@ -334,7 +371,8 @@ class FFLearner(PPOLearner):
         per_rep = self.fused_tail and self.U > 1  # (each replica's kernels own n_slab rows of the slab matrices)
         for u, rep in enumerate(self.reps):
             slab_a = self.slab_a[u * ns : (u + 1) * ns] if per_rep else self.slab_a
-            av = rep.agents_view[:T].view(TEA, self.Oa)
+            self._lean_guard(rep)
+            av = rep.av_raw[:T].view(TEA, self.Oa)
             if getattr(self, "_stats_batched", False) and perm is self._perm_bufs[k]:
                 stats = self._stats_all[u, k * self.M + mb]
             else:
@@ -356,8 +394,8 @@ class FFLearner(PPOLearner):
         # the critic's backward kernels run on this one
         w_actor = parallel.allreduce_sum_async(self.g[: self.Pa])
         for u, rep in enumerate(self.reps):
-            av = rep.agents_view[:T].view(TEA, self.Oa)
-            cx = rep.global_state[:T].view(-1, self.Oc) if self.centralised else av
+            av = rep.av_raw[:T].view(TEA, self.Oa)
+            cx = rep.gs_raw[:T].view(-1, self.Oc) if self.centralised else av
             in16 = in16_valid = None
             if self.x16:
                 in16, in16_valid = rep.state16[:T].view(-1, self.Oc), rep.state16_valid
@@ -507,7 +545,7 @@ class FFLearner(PPOLearner):
 
     def _carry_observation(self) -> None:
         for rep in self.reps:  # (one launch per replica)
-            ops.rollout_carry(rep.agents_view, rep.global_state, rep.action_mask, rep.step_count)
+            ops.rollout_carry(rep.av_raw, rep.gs_raw, rep.action_mask, rep.step_count)  # (slot T -> slot 0: always written)
 
 
 def learner_setup(env, keys, config, centralised_critic: bool, device=None):

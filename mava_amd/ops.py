@@ -516,15 +516,18 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
                reward_mode: int, env_state, agents_view, global_state, action_mask, obs_step_count, action, value,
                reward, log_prob, done, last_val, info_return, info_length, info_terminal, adv=None, tgt=None,
                gamma: float = 0.99, gae_lambda: float = 0.95, last_reward=None, last_done=None, step_counter=None,
-               state16=None, state16_valid=None, view16=None, view16_valid=None) -> bool:
-    """The whole rollout of one replica in one launch (mava_rollout_ff_f32).  Returns False when the library does not
+               state16=None, state16_valid=None, view16=None, view16_valid=None, skip_agents_view: bool = False,
+               skip_global_state: bool = False) -> bool:
+    """The whole rollout of one replica in one launch (mava_rollout_ff_flags_f32).  Returns False when the library does not
     instantiate the shape - the caller then steps policy_step / env.step_into per time step.
     last_reward / last_done (E, A): also written by the launch (= reward[T-1], done[T-1]); step_counter (1,) int32:
     advanced by T at the launch's end.
     state16 (T + 1, E, 1, A * O) float16 / state16_valid (1,) int32 holding 0 or 1: the launch also writes the f16 copy of
     global_state and whether it equals it; shared critic with A * O % 8 == 0 only.
     view16 (T + 1, E, A, RP) float16 with RP = 8 * ceil((A + O + 1) / 8) / view16_valid (1,) int32 holding 0 or 1: the f16 record of
-    agents_view - observation, 1.0, zeros - and its word; every instance."""
+    agents_view - observation, 1.0, zeros - and its word; every instance.
+    skip_agents_view / skip_global_state: slots 1 .. T - 1 of that f32 array are left unwritten (its f16 record holds the same
+    values: rollout_expand rebuilds them); the library refuses a skip without its record."""
     W = A + O
     _req(actor_params, torch.float32, "actor_params")
     _req(critic_params, torch.float32, "critic_params")
@@ -577,9 +580,63 @@ def rollout_ff(actor_params, critic_params, *, n_actions: int, critic_shared: bo
         _req(last_done, torch.uint8, "last_done", (E, A))
         if step_counter is not None:
             _req(step_counter, torch.int32, "step_counter", (1,))
-    rc = lib().mava_rollout_ff_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16), ptr(state16_valid),
-                                   ptr(view16), ptr(view16_valid), stream_ptr())
+    flags = (ROLLOUT_SKIP_AGENTS_VIEW if skip_agents_view else 0) | (ROLLOUT_SKIP_GLOBAL_STATE if skip_global_state else 0)
+    rc = lib().mava_rollout_ff_flags_f32(*args, ptr(last_reward), ptr(last_done), ptr(step_counter), ptr(state16),
+                                         ptr(state16_valid), ptr(view16), ptr(view16_valid), flags, stream_ptr())
     if rc == 1:
         return False
-    check(rc, "mava_rollout_ff_f32")
+    check(rc, "mava_rollout_ff_flags_f32")
     return True
+
+
+ROLLOUT_SKIP_AGENTS_VIEW, ROLLOUT_SKIP_GLOBAL_STATE = 1, 2  # include/mava_hip.h MAVA_ROLLOUT_SKIP_*
+
+
+def rollout_expand(agents_view, view16, view16_valid, global_state, state16, state16_valid, *, force: bool) -> None:
+    """Slots 1 .. T - 1 of the f32 trajectory arrays rebuilt from the f16 records of rollout_ff, one launch
+    (mava_rollout_expand_f32).  Either group - (agents_view (T + 1, E, A, A + O), view16, view16_valid) or (global_state
+    (T + 1, E, 1, A * O), state16, state16_valid) - may be None as a whole.  force=False: an array is rebuilt only when its
+    device word is not 1; no host read of the word."""
+    if (agents_view is None) != (view16 is None) or (view16 is None) != (view16_valid is None):
+        raise ValueError("agents_view, view16 and view16_valid go together")
+    if (global_state is None) != (state16 is None) or (state16 is None) != (state16_valid is None):
+        raise ValueError("global_state, state16 and state16_valid go together")
+    if view16 is None and state16 is None:
+        raise ValueError("rollout_expand: no record given")
+    if view16 is not None:
+        _req(agents_view, torch.float32, "agents_view")
+        T1, E, A, W = agents_view.shape
+        O = W - A
+        _req(view16, torch.float16, "view16", (T1, E, A, 8 * ((W + 8) // 8)))
+        _req(view16_valid, torch.int32, "view16_valid", (1,))
+    if state16 is not None:
+        _req(global_state, torch.float32, "global_state")
+        if view16 is None:
+            T1, E, AO = global_state.shape[0], global_state.shape[1], global_state.shape[-1]
+            A, O = 1, AO  # (the launch takes the row length of the state as A * O)
+        _req(global_state, torch.float32, "global_state", (T1, E, 1, A * O))
+        _req(state16, torch.float16, "state16", (T1, E, 1, A * O))
+        _req(state16_valid, torch.int32, "state16_valid", (1,))
+    check(lib().mava_rollout_expand_f32(T1 - 1, E, A, O, ptr(agents_view), ptr(view16), ptr(view16_valid), ptr(global_state),
+                                        ptr(state16), ptr(state16_valid), int(bool(force)), stream_ptr()), "mava_rollout_expand_f32")
+
+
+def ppo_actor_grad_reads_input16(ctx: Optional[Ctx], agents_view: torch.Tensor, n_actions: int, A: int,
+                                 input16: Optional[torch.Tensor]) -> bool:
+    """Would ppo_actor_grad with these arguments stage its input from input16 whenever the record's word reads 1?  The library's
+    own launch rule, asked on the host (mava_ppo_actor_grad_reads_input16); no launch."""
+    rc = lib().mava_ppo_actor_grad_reads_input16(ctx_ptr(ctx), agents_view.shape[1], n_actions, ptr(agents_view), A, ptr(input16),
+                                                 0 if input16 is None else input16.shape[1])
+    if rc < 0:
+        check(rc, "mava_ppo_actor_grad_reads_input16")
+    return rc == 1
+
+
+def ppo_critic_grad_reads_input16(ctx: Optional[Ctx], critic_input: torch.Tensor, x_share: int, A: int,
+                                  input16: Optional[torch.Tensor]) -> bool:
+    """The same question for ppo_critic_grad (mava_ppo_critic_grad_reads_input16)."""
+    rc = lib().mava_ppo_critic_grad_reads_input16(ctx_ptr(ctx), critic_input.shape[1], ptr(critic_input), x_share, A, ptr(input16),
+                                                  0 if input16 is None else input16.shape[1])
+    if rc < 0:
+        check(rc, "mava_ppo_critic_grad_reads_input16")
+    return rc == 1

@@ -69,6 +69,56 @@ class _Replica:
         return {"agents_view": self.agents_view[t], "global_state": self.global_state[t],
                 "action_mask": self.action_mask[t], "step_count": self.step_count[t]}
 
+    # the buffers themselves, for code that touches slots 0 and T only or hands the kernels a pointer (see LeanReplica)
+    @property
+    def av_raw(self) -> torch.Tensor:
+        return self.agents_view
+
+    @property
+    def gs_raw(self) -> torch.Tensor:
+        return self.global_state
+
+
+class LeanReplica(_Replica):
+    """The replica of a learner whose fused rollout may leave slots 1 .. T - 1 of the f32 agents_view / global_state
+    unwritten, their f16 records holding the same values (FFLearner._rollout_fused).  `agents_view` and `global_state`
+    are properties: a read while the array's inner slots are stale first rebuilds them from the record (one forced
+    ops.rollout_expand launch on the current stream) and then returns the same tensor object as ever.  The update's own
+    code takes av_raw / gs_raw: it reads slots 0 and T, which are always written, and passes pointers."""
+
+    def __init__(self, *args, **kwargs):
+        self.stale_av = self.stale_gs = False  # slots 1 .. T - 1 of the f32 array were skipped by the last rollout
+        self.state16 = self.state16_valid = self.view16 = self.view16_valid = None
+        super().__init__(*args, **kwargs)
+
+    def materialise(self, av: bool = True, gs: bool = True) -> None:
+        av, gs = av and self.stale_av, gs and self.stale_gs
+        if av or gs:
+            ops.rollout_expand(self.av_raw if av else None, self.view16 if av else None, self.view16_valid if av else None,
+                               self.gs_raw if gs else None, self.state16 if gs else None, self.state16_valid if gs else None,
+                               force=True)
+            self.stale_av, self.stale_gs = self.stale_av and not av, self.stale_gs and not gs
+
+    av_raw = gs_raw = None  # (plain attributes here: the buffers live under these names)
+
+    @property
+    def agents_view(self) -> torch.Tensor:
+        self.materialise(gs=False)
+        return self.av_raw
+
+    @agents_view.setter
+    def agents_view(self, t: torch.Tensor) -> None:
+        self.av_raw = t
+
+    @property
+    def global_state(self) -> torch.Tensor:
+        self.materialise(av=False)
+        return self.gs_raw
+
+    @global_state.setter
+    def global_state(self, t: torch.Tensor) -> None:
+        self.gs_raw = t
+
 
 class PPOLearner:
     def __init__(self, env, config, centralised_critic: bool, device: Optional[torch.device] = None, *, replica=_Replica,
@@ -205,12 +255,12 @@ class PPOLearner:
         return torch.stack([f(r) for r in self.reps], 0).unsqueeze(0)
 
     def _observation(self, slot: int = 0):
-        av = self._stack(lambda r: r.agents_view[slot])
+        av = self._stack(lambda r: r.av_raw[slot])  # (slot 0 or T: see LeanReplica)
         mask = self._stack(lambda r: r.action_mask[slot]).bool()
         sc = self._stack(lambda r: r.step_count[slot])
         if not self.centralised:
             return Observation(av, mask, sc)
-        gs = self._stack(lambda r: r.global_state[slot].expand(-1, self.A, -1) if r.env.gs_tiles == 1 else r.global_state[slot])
+        gs = self._stack(lambda r: r.gs_raw[slot].expand(-1, self.A, -1) if r.env.gs_tiles == 1 else r.gs_raw[slot])
         return ObservationGlobalState(av, mask, gs, sc)
 
     def _key(self) -> torch.Tensor:
@@ -260,7 +310,7 @@ class PPOLearner:
 
     def _guard_tensors(self) -> Tuple[torch.Tensor, List[Optional[torch.Tensor]]]:
         """(parameters, observation leaves) for the f16 range guard."""
-        return self.p, [t for r in self.reps for t in (r.agents_view[0], r.global_state[0] if self.centralised else None)]
+        return self.p, [t for r in self.reps for t in (r.av_raw[0], r.gs_raw[0] if self.centralised else None)]
 
     def learn(self, learner_state) -> ExperimentOutput:
         """LearnerFn (mava/types.py:154): num_updates_per_eval updates, asynchronous on the current
