@@ -685,6 +685,17 @@ int mava_rec_out_f32(int T, int Rm, int E, int A, int n_out, int agents_per_row,
                      const float* params_post_head, const uint8_t* mask, const int32_t* action, const float* f0,
                      const float* f1, const double* adv_stats, int n_stats, float clip_eps, float coef, float grad_scale,
                      int is_actor, float* dh, float* slab, long slab_stride, int n_slab, mava_stream_t s);
+/* mava_rec_out_f32 for the actor with ContinuousActionHead and a log_std vector (networks.py:127-169 with
+ * independent_std; the loss of mava_seq_actor_loss_continuous_f32, the same Philox counters for the entropy noise):
+ * `action` is the external (T, E, A, action_dim) buffer, log_std the action_dim raw scales, f0 / f1 = old_log_prob /
+ * advantages.  The slab row is [dWpost | dbpost | dWhead | dbhead | loss sums (2) | dlog_std (action_dim)], all in true
+ * units (dlog_std already times sigmoid(log_std)); slab_stride must cover it.  Returns 1 (nothing launched) for
+ * action_dim > 16 or n_slab > tiles. */
+int mava_rec_out_continuous_f32(int T, int Rm, int E, int A, int action_dim, float min_scale, const int32_t* idx,
+                                const float* hs, const float* params_post_head, const float* log_std, const float* action,
+                                const float* f0, const float* f1, const double* adv_stats, int n_stats, float clip_eps,
+                                float coef, uint64_t seed, uint32_t ent_step, uint32_t row_offset, float grad_scale,
+                                float* dh, float* slab, long slab_stride, int n_slab, mava_stream_t s);
 
 /* rollout epilogue: masked Categorical sample + log_prob from T32 logits of one step (rows = E*A). */
 int mava_seq_sample_f32(int rows, int n_actions, const float* logits, const uint8_t* mask, uint64_t seed,

@@ -104,6 +104,8 @@ _SIGNATURES = {
                           i32, i32, vp, vp],
     "mava_seq_critic_loss_f32": [i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, f32, f32, vp, vp, i32, vp],
     "mava_rec_out_f32": [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, vp, vp, lng, i32, vp],
+    "mava_rec_out_continuous_f32": [i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, u64, u32, u32, f32,
+                                    vp, vp, lng, i32, vp],
     "mava_rec_step_pack_bytes": [i32],
     "mava_t32_norm_act_f32": [vp, i32, lng, i32, vp, i32, vp, vp, vp, vp],
     "mava_t32_norm_act_bwd_f32": [vp, vp, i32, lng, i32, vp, vp, i32, vp, vp, vp],

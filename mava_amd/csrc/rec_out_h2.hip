@@ -17,12 +17,23 @@
 //  * gradients accumulate in registers over the block's tiles and leave as per-block slabs
 //    [dWpost | dbpost | dWhead | dbhead | loss sums] = the tail of the flat parameter layout.
 // Gradient units: d loss / d outputs is formed times grad_scale (rec_dense_h2.hip), dh is written in those units, the
-// slabs are multiplied by 1 / grad_scale.  Discrete actor heads up to 16 actions and the critic (one value, optionally the
-// sum of `agg` agents' loss gradients per row); the continuous head stays on the layer-wise kernels.
+// slabs are multiplied by 1 / grad_scale.  Discrete actor heads up to 16 actions, the critic (one value, optionally the
+// sum of `agg` agents' loss gradients per row) and the continuous actor with a log_std vector, up to 16 action dimensions
+// (rec_out_cont_h2_kernel, mava_rec_out_continuous_f32).  The continuous actor shares everything but P3:
+//  * eight lanes per row as in the discrete loss, lane l8 owns dimensions l8 and l8 + 8: the tanh-normal log-density terms
+//    (tanh_normal.h) and the entropy sample of its dimensions; log-prob and entropy of the row are sums over its 8 lanes;
+//  * softplus / sigmoid of log_std are taken once per launch (LDS, next to the head's bias) and kept in registers;
+//  * the stored action's components ride the two-deep row pipeline; the entropy noise (Philox + Box-Muller per dimension)
+//    of the NEXT tile is drawn in P5's even steps, under the dh / dWpost products, where the wave's VALU is otherwise idle;
+//  * d loss / d scale accumulates per lane next to the head's bias sums and leaves, times sigmoid(log_std) and in true
+//    units, behind the loss sums: [dWpost | dbpost | dWhead | dbhead | loss sums (2) | dlog_std (action_dim)]; fixed-order
+//    sums, no atomics.
+// ContinuousActionHead(independent_std=False) (a second head) stays on the general layer path.
 #include <float.h>
 
 #include "h2_core.h"
 #include "rec_task.h"
+#include "tanh_normal.h"
 
 namespace {
 
@@ -59,6 +70,11 @@ struct OutTask {
   float* slab;              // (gridDim.x, slab_stride)
   long slab_stride;
   unsigned long long* stamps;  // diagnostic builds (-DMAVA_STAMPS): per-phase cycle sums of block 0, wave 0
+  // continuous actor (behind the fields the other modes read, whose kernel arguments stay where they were)
+  const float* action_f;    // external (T, E, A, no)
+  const float* log_std;     // the `no` raw scales behind the network's parameters
+  float min_scale;
+  uint32_t seed_lo, seed_hi, ent_step, row_offset;  // entropy draw (tanh_normal.h)
 };
 
 constexpr int XPL = 128 * 64;       // bytes per staged plane
@@ -89,9 +105,13 @@ __device__ __forceinline__ Frag rows_frag(const u8* plane_hi, int f, int c) {
   return r;
 }
 
-template <int NO, bool ACTOR>
-__global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
-  extern __shared__ __attribute__((aligned(16))) u8 lds[];
+// MODE 0: critic, 1: discrete actor, 2: continuous actor (tanh-normal head with a log_std vector).  One body, inlined into the
+// kernels below: the modes differ in P3, in the row inputs its pipeline carries and in the tail of the slab.
+constexpr int CRITIC = 0, DISCRETE = 1, CONTINUOUS = 2;
+
+template <int NO, int MODE>
+__device__ __forceinline__ void rec_out_body(const OutTask& tk, u8* const lds) {
+  constexpr bool ACTOR = MODE == DISCRETE, CONT = MODE == CONTINUOUS, POLICY = MODE != CRITIC;
   u8* const STG = lds;                              // 2 x XBUF
   u8* const POSTI = STG + 2 * XBUF;                 // IMG_BYTES
   u8* const DPOSTI = POSTI + IMG_BYTES;             // IMG_BYTES
@@ -99,6 +119,7 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
   float* const YP = reinterpret_cast<float*>(DYI + 2 * DY_PLANE);  // [4][32][NO + 1]
   float* const misc = YP + 4 * 32 * (NO + 1);       // [0] adv mean, [1] adv rstd, [2 ..] reductions, then bhead
   float* const B3s = misc + 64;
+  float* const SCs = B3s + 32;                      // continuous: [0, 16) scale, [16, 32) sigmoid(log_std)
   const int tid = threadIdx.x;
   const int lane = tid & 63, h = lane >> 5, r = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -154,7 +175,12 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
 #pragma unroll
   for (int q = 0; q < 16; ++q) bp[q] = bpost[32 * w + 4 * h + (q & 3) + 8 * (q >> 2)];
   if (tid < NO) B3s[tid] = tid < no ? bhead[tid] : 0.0f;
-  if (ACTOR && tid == 0) {
+  if (CONT && tid < NO) {  // softplus / sigmoid of the log_std vector: once per launch, not per row
+    const float ls = tid < no ? tk.log_std[tid] : 0.0f;
+    SCs[tid] = tn::scale_of(ls, tk.min_scale);
+    SCs[16 + tid] = tn::sigmoid(ls);
+  }
+  if (POLICY && tid == 0) {
     double s1 = 0.0, s2 = 0.0;
     for (int i = 0; i < tk.n_stats; ++i) { s1 += tk.stats[2 * i]; s2 += tk.stats[2 * i + 1]; }
     const double mean = s1 / (double)R;
@@ -176,9 +202,9 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
   float ab2[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) ab2[q] = 0.0f;
-  float ab3[NO / 8], loss_a = 0.0f, loss_b = 0.0f;
+  float ab3[NO / 8], ads[NO / 8], loss_a = 0.0f, loss_b = 0.0f;  // ads: d loss / d scale column sums (continuous)
 #pragma unroll
-  for (int k = 0; k < NO / 8; ++k) ab3[k] = 0.0f;
+  for (int k = 0; k < NO / 8; ++k) ab3[k] = ads[k] = 0.0f;
 
   // ---------------------------------------------------------------- lane mappings
   // loss: eight lanes per row (all 32 rows of the tile in one pass), lane l8 of a row owns outputs l8, l8 + 8, ...
@@ -217,6 +243,7 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
   int n_act[NP];
   float n_f0[NP], n_f1[NP];
   uint32_t n_m[OPL];
+  float n_af[OPL], n_eps[OPL];  // continuous: the stored action's components and the entropy noise of this lane's dimensions
   // two-deep pipeline: the env ids (idx) of a tile are loaded two tiles ahead, the values behind them one tile ahead -
   // neither address waits for memory
   uint32_t p_t[NP], p_a[NP], p_env[NP];
@@ -239,6 +266,12 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
       n_f0[q] = n_f1[q] = 0.0f;
 #pragma unroll
       for (int k = 0; k < OPL; ++k) n_m[k] = 1u;
+      if (CONT) {
+        n_f0[q] = tk.f0[n_er[q]];
+        n_f1[q] = tk.f1[n_er[q]];
+#pragma unroll
+        for (int k = 0; k < OPL; ++k) n_af[k] = (l8 + 8 * k < no) ? tk.action_f[n_er[q] * no + l8 + 8 * k] : 0.0f;
+      }
       if (ACTOR) {
         n_act[q] = tk.action[n_er[q]];
         n_f0[q] = tk.f0[n_er[q]];
@@ -249,11 +282,23 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
       }
     }
   };
+  // continuous: the entropy noise depends on the row's external index alone, so the next tile's draws (Philox and a
+  // Box-Muller transform per dimension) are made in P5's even steps, under its matrix products, not in P3 where every wave waits
+  auto draw = [&](int k) {
+    n_eps[k] = tn::noise(tk.row_offset + (uint32_t)n_er[0], tk.ent_step, l8 + 8 * k, tn::STREAM_ENTROPY, tk.seed_lo, tk.seed_hi);
+  };
   load_env(it < ntiles ? it : 0);
   load_rows();
+  if (CONT) {
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) draw(k);
+  }
   load_env(it + G < ntiles ? it + G : (ntiles - 1));
   __syncthreads();
-  const float adv_mean = ACTOR ? misc[0] : 0.0f, adv_rstd = ACTOR ? misc[1] : 0.0f;
+  const float adv_mean = POLICY ? misc[0] : 0.0f, adv_rstd = POLICY ? misc[1] : 0.0f;
+  float sc[OPL];
+#pragma unroll
+  for (int k = 0; k < OPL; ++k) sc[k] = CONT ? SCs[l8 + 8 * k] : 1.0f;
   if (it < ntiles) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) issue(it, k);
@@ -284,6 +329,9 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
     for (int q = 0; q < NP; ++q) { er[q] = n_er[q]; r_act[q] = n_act[q]; r_f0[q] = n_f0[q]; r_f1[q] = n_f1[q]; }
 #pragma unroll
     for (int k = 0; k < OPL; ++k) r_m[k] = n_m[k];
+    float r_af[OPL], r_eps[OPL];
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) { r_af[k] = n_af[k]; r_eps[k] = n_eps[k]; }
     load_rows();                                                   // tile it + G (its env ids arrived a tile ago)
     load_env(it + 2 * G < ntiles ? it + 2 * G : (ntiles - 1));     // tile it + 2G
 
@@ -344,7 +392,45 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
         y[k] = (((yp[0] + yp[32 * (NO + 1)]) + yp[2 * 32 * (NO + 1)]) + yp[3 * 32 * (NO + 1)]) + B3s[o];
         dyo[k] = 0.0f;
       }
-      if (ACTOR) {
+      if (CONT) {
+        // Independent tanh-normal over the row's dimensions (networks.py:127-169, distributions.py:24-91; seq_loss_cont_kernel):
+        // lane l8 holds the log-density terms and the entropy sample of dimensions l8 and l8 + 8, the row's sums cross its 8 lanes
+        auto add_op = [](float a, float b) { return a + b; };
+        float dm[OPL], dsl[OPL], th[OPL];
+        float lp = 0.0f, ent = 0.0f;
+#pragma unroll
+        for (int k = 0; k < OPL; ++k) {
+          const bool live = l8 + 8 * k < no;  // (a padding dimension computes on mean 0, action 0, scale softplus(0) + min_scale)
+          const tn::LogProb l = tn::log_prob(r_af[k], y[k], sc[k]);
+          const float x = fmaf(sc[k], r_eps[k], y[k]);
+          th[k] = tanhf(x);
+          dm[k] = l.dmean;
+          dsl[k] = l.dscale;
+          lp += live ? l.lp : 0.0f;
+          ent += live ? 0.5f + tn::HALF_LOG_2PI + logf(sc[k]) + tn::tanh_fldj(x) : 0.0f;
+        }
+        lp = group_allreduce<8>(lp, add_op);
+        ent = group_allreduce<8>(ent, add_op);
+        const float gae = (r_f1[0] - adv_mean) * adv_rstd;
+        const float ratio = expf(lp - r_f0[0]);
+        const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
+        const float l1 = ratio * gae, l2 = rc * gae;
+        const bool inside = (ratio >= lo_c) && (ratio <= hi_c);
+        const float g1w = (l1 < l2) ? 1.0f : ((l1 == l2) ? 0.5f : 0.0f);
+        const float g2w = inside ? (1.0f - g1w) : 0.0f;
+        const float dlp = -(g1w + g2w) * gae * ratio * gsc;
+        const float ec = tk.coef * gsc;
+#pragma unroll
+        for (int k = 0; k < OPL; ++k) {
+          const bool live = l8 + 8 * k < no;
+          dyo[k] = live ? dlp * dm[k] + ec * 2.0f * th[k] : 0.0f;
+          ads[k] += live ? dlp * dsl[k] - ec * (1.0f / sc[k] - 2.0f * th[k] * r_eps[k]) : 0.0f;
+        }
+        if (l8 == 0) {
+          loss_a += -fminf(l1, l2) * invR;
+          loss_b += ent * invR;
+        }
+      } else if (ACTOR) {
         auto fmax_op = [](float a, float b) { return fmaxf(a, b); };
         auto add_op = [](float a, float b) { return a + b; };
         // masked Categorical over the row's outputs (networks.py:116-124, distributions.py:146-165)
@@ -470,6 +556,8 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
           const int k = s >> 1;
           stage4(wbuf, soff[k], raw[k]);
           issue(it_issue, k);
+        } else if (CONT && (s >> 1) < OPL) {
+          draw(s >> 1);  // n_er holds the next tile's rows since load_rows() at the top
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -490,7 +578,7 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
   // ---------------------------------------------------------------- epilogue: slabs (true units)
   float* slab = tk.slab + (long)blockIdx.x * tk.slab_stride;
   const float inv = 1.0f / tk.grad_scale;
-  const int oWp = 0, oBp = MLP_H * MLP_H, oW3 = oBp + MLP_H, oB3 = oW3 + MLP_H * no, oL = oB3 + no;
+  const int oWp = 0, oBp = MLP_H * MLP_H, oW3 = oBp + MLP_H, oB3 = oW3 + MLP_H * no, oL = oB3 + no, oS = oL + 2;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -524,7 +612,19 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
     }
     float* redl = reinterpret_cast<float*>(POSTI);
     if (lane == 0) { redl[2 * w] = loss_a; redl[2 * w + 1] = loss_b; }
+    float* reds = reinterpret_cast<float*>(DPOSTI);  // [4 waves][NO]: d loss / d scale, summed like the head's bias
+    if (CONT) {
+#pragma unroll
+      for (int k = 0; k < NO / 8; ++k) {
+        float v = ads[k];
+#pragma unroll
+        for (int m = 8; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+        if (lane < 8) reds[w * NO + lane + 8 * k] = v;
+      }
+    }
     __syncthreads();
+    // d scale / d log_std = sigmoid(log_std); the loss terms carry grad_scale, log_std's gradient leaves in true units
+    if (CONT && tid < no) slab[oS + tid] = (((reds[tid] + reds[NO + tid]) + reds[2 * NO + tid]) + reds[3 * NO + tid]) * inv * SCs[16 + tid];
     if (tid < no) slab[oB3 + tid] = (((red[tid] + red[NO + tid]) + red[2 * NO + tid]) + red[3 * NO + tid]) * inv;
     if (tid == 0) {
       slab[oL] = ((redl[0] + redl[2]) + redl[4]) + redl[6];
@@ -534,14 +634,50 @@ __global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
 }
 
 template <int NO, bool ACTOR>
+__global__ __launch_bounds__(256, 1) void rec_out_h2_kernel(OutTask tk) {
+  extern __shared__ __attribute__((aligned(16))) u8 lds[];
+  rec_out_body<NO, ACTOR ? DISCRETE : CRITIC>(tk, lds);
+}
+
+// The continuous actor: same phases, P3 on the tanh-normal head.  Its device code is generated without packed f32 arithmetic
+// (the host pass does not know the feature and would warn).
+#ifdef __HIP_DEVICE_COMPILE__
+#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NO_PACKED_F32
+#endif
+template <int NO>
+__global__ __launch_bounds__(256, 1) NO_PACKED_F32 void rec_out_cont_h2_kernel(OutTask tk) {
+  extern __shared__ __attribute__((aligned(16))) u8 lds[];
+  rec_out_body<NO, CONTINUOUS>(tk, lds);
+}
+
+constexpr size_t OUT_LDS(int NO, bool cont) {
+  return (size_t)2 * XBUF + 2 * IMG_BYTES + 2 * DY_PLANE + (size_t)(4 * 32 * (NO + 1) + 64 + 32 + (cont ? 32 : 0)) * 4;
+}
+
+template <int NO, bool ACTOR>
 int launch_out(const OutTask& tk, int n_slab, hipStream_t s) {
-  const size_t lb = (size_t)2 * XBUF + 2 * IMG_BYTES + 2 * DY_PLANE + (size_t)(4 * 32 * (NO + 1) + 64 + 32) * 4;
+  const size_t lb = OUT_LDS(NO, false);
   static bool attr_set = false;
   if (!attr_set) {
     MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)rec_out_h2_kernel<NO, ACTOR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     attr_set = true;
   }
   hipLaunchKernelGGL((rec_out_h2_kernel<NO, ACTOR>), dim3(n_slab), dim3(256), lb, s, tk);
+  MAVA_LAUNCH_CHECK();
+  return MAVA_OK;
+}
+
+template <int NO>
+int launch_out_cont(const OutTask& tk, int n_slab, hipStream_t s) {
+  const size_t lb = OUT_LDS(NO, true);
+  static bool attr_set = false;
+  if (!attr_set) {
+    MAVA_HIP_CHECK(hipFuncSetAttribute((const void*)rec_out_cont_h2_kernel<NO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((rec_out_cont_h2_kernel<NO>), dim3(n_slab), dim3(256), lb, s, tk);
   MAVA_LAUNCH_CHECK();
   return MAVA_OK;
 }
@@ -575,4 +711,28 @@ extern "C" int mava_rec_out_f32(int T, int Rm, int E, int A, int n_out, int agen
   if (!is_actor) return launch_out<8, false>(tk, n_slab, s);
   if (n_out <= 8) return launch_out<8, true>(tk, n_slab, s);
   return launch_out<16, true>(tk, n_slab, s);
+}
+
+// The continuous actor's output path (ContinuousActionHead with a log_std vector).  Returns 1 like mava_rec_out_f32.
+extern "C" int mava_rec_out_continuous_f32(int T, int Rm, int E, int A, int action_dim, float min_scale, const int32_t* idx,
+                                           const float* hs, const float* params_post_head, const float* log_std, const float* action,
+                                           const float* f0, const float* f1, const double* adv_stats, int n_stats, float clip_eps,
+                                           float coef, uint64_t seed, uint32_t ent_step, uint32_t row_offset, float grad_scale, float* dh,
+                                           float* slab, long slab_stride, int n_slab, hipStream_t s) {
+  MAVA_ARG_CHECK(T >= 1 && Rm >= 32 && Rm % 32 == 0 && E >= 1 && A >= 1 && action_dim >= 1 && n_slab >= 1, 0,
+                 "mava_rec_out_continuous_f32: bad shape");
+  MAVA_ARG_CHECK(hs && params_post_head && log_std && action && f0 && f1 && adv_stats && dh && slab, 1,
+                 "mava_rec_out_continuous_f32: null pointer argument");
+  MAVA_ARG_CHECK(slab_stride >= (long)MLP_H * MLP_H + MLP_H + (long)MLP_H * action_dim + action_dim + 2 + action_dim, 2,
+                 "mava_rec_out_continuous_f32: slab_stride too small");
+  if (action_dim > 16 || (long)n_slab > (long)T * Rm / 32) return 1;
+  OutTask tk = {};
+  tk.T = T; tk.Rm = Rm; tk.E = E; tk.A = A; tk.no = action_dim; tk.agg = 1; tk.idx = idx; tk.hs = hs; tk.params = params_post_head;
+  tk.action_f = action; tk.log_std = log_std; tk.min_scale = min_scale; tk.f0 = f0; tk.f1 = f1; tk.stats = adv_stats;
+  tk.n_stats = n_stats; tk.clip_eps = clip_eps; tk.coef = coef; tk.seed_lo = (uint32_t)seed; tk.seed_hi = (uint32_t)(seed >> 32);
+  tk.ent_step = ent_step; tk.row_offset = row_offset; tk.grad_scale = grad_scale; tk.dh = dh; tk.slab = slab;
+  tk.slab_stride = slab_stride;
+  tk.stamps = g_out_stamps;
+  if (action_dim <= 8) return launch_out_cont<8>(tk, n_slab, s);
+  return launch_out_cont<16>(tk, n_slab, s);
 }

@@ -68,6 +68,17 @@ class _RecReplica(_Replica):
         self.value_env = torch.zeros(E, device=dev)
 
 
+def fused_out_modes(matmul_mode: str, continuous: bool, independent_std: bool, n_out: int, generic_nets: bool, env=None):
+    """(fused_out, fused_out_continuous): which networks run their output path as one launch (csrc/rec_out_h2.hip).
+    fused_out: both networks of a discrete run (mava_rec_out_f32), on unless MAVA_REC_FUSED_OUT=0.
+    fused_out_continuous: the actor of a continuous run with a log_std vector (mava_rec_out_continuous_f32), on only with
+    MAVA_REC_FUSED_OUT_CONTINUOUS=1; the critic of such a run keeps the path it has."""
+    env = os.environ if env is None else env
+    shape_ok = matmul_mode == "f16x2" and n_out <= 16 and not generic_nets
+    return (shape_ok and not continuous and env.get("MAVA_REC_FUSED_OUT", "1") != "0",
+            shape_ok and continuous and bool(independent_std) and env.get("MAVA_REC_FUSED_OUT_CONTINUOUS", "0") == "1")
+
+
 class RecLearner(PPOLearner):
     def __init__(self, env, config, centralised_critic: bool, device: Optional[torch.device] = None):
         # (arithmetic of the dense / X^T Y products on T32 operands: "f16x2" is rec_dense_h2.hip)
@@ -129,8 +140,8 @@ class RecLearner(PPOLearner):
         # the backward chain runs in units of a power of two near the row count (mava_seq_actor_loss_f32: f16 range)
         self.grad_scale = float(2 ** math.ceil(math.log2(self.T * self.Rm)))
         # f16x2: both networks' weights pre-split in MFMA-fragment order for the fused acting step (re-packed per rollout)
-        self.fused_out = (self.matmul_mode == "f16x2" and not self.continuous and self.nA <= 16 and not self.generic_nets
-                          and os.environ.get("MAVA_REC_FUSED_OUT", "1") != "0")
+        self.fused_out, self.fused_out_continuous = fused_out_modes(self.matmul_mode, self.continuous, not self.dep_std, self.nA,
+                                                                    self.generic_nets)
         self.pack_a = torch.empty(lib().mava_rec_step_pack_bytes(self.Oa), dtype=torch.uint8, device=d)
         self.pack_c = torch.empty(lib().mava_rec_step_pack_bytes(self.Oc), dtype=torch.uint8, device=d)
         # (with several ranks a few CUs stay free of the persistent X^T Y blocks for RCCL's kernels: PPOLearner._slab_count)
@@ -318,8 +329,10 @@ class RecLearner(PPOLearner):
         flat_rows = (self._t_range32 + idx[None, :]).reshape(-1)  # (t*E + env) rows of the minibatch, int32 (T * E < 2^31): one launch
         L = lib()
         # f16x2: the output path (post_torso -> head -> loss -> backward) of both networks runs as ONE launch each
-        # (mava_rec_out_f32); the continuous head and more than 16 actions stay on the layer-wise kernels
+        # (mava_rec_out_f32); more than 16 actions stay on the layer-wise kernels, and so does the continuous head unless
+        # fused_out_continuous puts its actor on mava_rec_out_continuous_f32
         fused_out = self.fused_out
+        fused_actor = fused_out or self.fused_out_continuous
 
         def actor_part(ws, slabs):
             """rec_mappo.py:210-242 for every replica, on the current stream."""
@@ -328,9 +341,16 @@ class RecLearner(PPOLearner):
             for u, rep in enumerate(self.reps):
                 acc = u > 0
                 self.actor_network.forward_sequence(pa, ws, rep.agents_view[:T], 1, rep.done_in, rep.h0_actor, False, idx, T, Rm, E, A,
-                                                    training=True, stop_after_scan=fused_out)
+                                                    training=True, stop_after_scan=fused_actor)
                 ops.adv_stats(rep.adv.view(-1), flat_rows, 0, T * Em, A, out=self.stats)
-                if fused_out:
+                if self.fused_out_continuous:
+                    ok = self.actor_network.fused_output_continuous(
+                        pa, ws, idx, T, Rm, E, A, self.min_scale, rep.action, rep.log_prob, rep.adv, self.stats, float(s.clip_eps),
+                        float(s.ent_coef), self.seed & (2**64 - 1), self.ent_step & 0xFFFFFFFF,
+                        ((self.rank * self.U + u) * T * E * A) & 0xFFFFFFFF, slabs, self.g[: self.Pa], self.g[self.P : self.P + 2], acc,
+                        self.grad_scale)
+                    assert ok, "mava_rec_out_continuous_f32 refused a shape RecLearner.fused_out_continuous admitted"
+                elif fused_out:
                     ok = self.actor_network.fused_output(pa, ws, idx, T, Rm, E, A, 1, True, rep.action_mask[:T], rep.action, rep.log_prob,
                                                          rep.adv, self.stats, float(s.clip_eps), float(s.ent_coef), slabs,
                                                          self.g[: self.Pa], self.g[self.P : self.P + 2], acc, self.grad_scale)
@@ -352,10 +372,10 @@ class RecLearner(PPOLearner):
                                                     float(s.clip_eps), float(s.ent_coef), self.grad_scale, ptr(ws.dy), ptr(ws.loss_partials),
                                                     nblk, st),
                           "mava_seq_actor_loss_f32")
-                if not fused_out:
+                if not fused_actor:
                     ops.slab_reduce(ws.loss_partials, 2, self.g[self.P : self.P + 2], accumulate=acc)
                 self.actor_network.backward_sequence(pa, ws, rep.agents_view[:T], 1, rep.done_in, idx, T, Rm, E, A, slabs,
-                                                     self.g[: self.Pa], accumulate=acc, grad_scale=self.grad_scale, from_scan=fused_out)
+                                                     self.g[: self.Pa], accumulate=acc, grad_scale=self.grad_scale, from_scan=fused_actor)
 
         def critic_part(ws, slabs):
             """rec_mappo.py:244-266 for every replica, on the current stream."""

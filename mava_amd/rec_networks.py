@@ -539,6 +539,26 @@ class RecurrentActor(_RecurrentNet):
     def log_std(self, flat: torch.Tensor) -> torch.Tensor:
         return flat[self.num_net_params : self.num_net_params + self.n_out]
 
+    def fused_output_continuous(self, flat, ws: RecWorkspace, idx, T, Rm, E, A, min_scale: float, action, old_log_prob, adv, stats,
+                                clip_eps: float, ent_coef: float, seed: int, ent_step: int, row_offset: int, slabs, grad_out, loss_out,
+                                accumulate: bool, grad_scale: float) -> bool:
+        """fused_output for the continuous head with a log_std vector (mava_rec_out_continuous_f32): one launch, one reduction
+        of the slabs' main part and loss sums, and the dlog_std window behind them summed into log_std(grad_out).
+        False when the library does not instantiate the shape."""
+        n_out = self.n_out
+        o = self.off["Wpost"][0]
+        n_main = H * H + H + H * n_out + n_out
+        slabs = slabs[: max(1, min(slabs.shape[0], (T * Rm) // 32))]
+        rc = launch("rec_out_continuous", lib().mava_rec_out_continuous_f32, T, Rm, E, A, n_out, min_scale, ptr(idx), ptr(ws.hs),
+                    flat.data_ptr() + 4 * o, ptr(self.log_std(flat)), ptr(action), ptr(old_log_prob), ptr(adv), ptr(stats), stats.shape[0],
+                    clip_eps, ent_coef, seed, ent_step, row_offset, grad_scale, ptr(ws.dh_out), ptr(slabs), slabs.shape[1], slabs.shape[0],
+                    stream_ptr(), ok=(0, 1))
+        if rc == 1:
+            return False
+        ops.slab_reduce2(slabs, n_main, grad_out[o : o + n_main], loss_out.numel(), loss_out, accumulate=accumulate)
+        ops.slab_reduce_cols(slabs, n_main + 2, n_out, self.log_std(grad_out), accumulate=accumulate)
+        return True
+
     def tree(self, flat: torch.Tensor, lead: Tuple[int, ...] = ()) -> Dict[str, Any]:
         out = super().tree(flat, lead)
         if self.continuous and self.independent_std:
