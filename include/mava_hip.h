@@ -919,6 +919,21 @@ int mava_t32_im2col_f32(const float* src, int src_flat, long samples, int Hin, i
                         float* dst, mava_stream_t s);
 int mava_t32_col2im_f32(const float* dcol, int src_flat, long samples, int Hin, int Win, int C, int k, int stride,
                         float* dsrc, mava_stream_t s);
+/* The same convolution WITHOUT the patch matrix (csrc/conv_direct.hip): the patches of a 32-row tile are formed in LDS.
+ * Geometry, layouts and src_flat as mava_t32_im2col_f32; w: the flattened (k*k*C, Cout) kernel; arithmetic per
+ * MAVA_CTX_MATMUL_MODE like mava_rec_dense_f32.  Envelope: k <= 4, stride <= 3, C <= 64, Cout 32 or 64, Hin, Win <= 32,
+ * samples a multiple of 32; outside it the call returns 1 with nothing launched and nothing written.
+ *   fwd:        z (rows x Cout) = patches w + bias (bias may be NULL); y (or NULL) = act(z), act as mava_t32_norm_act_f32
+ *   bwd_data:   dsrc, T32 (samples*Hin*Win x C) = the adjoint applied to dz (rows x Cout); linear in dz
+ *   bwd_weight: per-block slabs (n_slab, slab_stride >= k*k*C*Cout + Cout) of [patches^T dz | colsum(dz)] / grad_scale for
+ *               mava_slab_reduce_f32; fixed order, a block without tiles writes exact zeros */
+int mava_conv_fwd_f32(const mava_ctx* ctx, const float* src, int src_flat, long samples, int Hin, int Win, int C, int k,
+                      int stride, int Cout, const float* w, const float* bias, int act, float* z, float* y, mava_stream_t s);
+int mava_conv_bwd_data_f32(const mava_ctx* ctx, const float* dz, long samples, int Hin, int Win, int C, int k, int stride,
+                           int Cout, const float* w, float* dsrc, mava_stream_t s);
+int mava_conv_bwd_weight_f32(const mava_ctx* ctx, const float* src, int src_flat, long samples, int Hin, int Win, int C, int k,
+                             int stride, int Cout, const float* dz, float grad_scale, float* slab, long slab_stride,
+                             int n_slab, mava_stream_t s);
 /* jax.lax.collapse(x, -3): T32 (samples*P x C) -> T32 (samples x P*C) (to_flat = 1) and back (0) */
 int mava_t32_flatten_f32(const float* src, long samples, int P, int C, int to_flat, float* dst, mava_stream_t s);
 

@@ -112,6 +112,9 @@ _SIGNATURES = {
     "mava_t32_colsum_f32": [vp, i32, lng, f32, vp, lng, i32, vp],
     "mava_t32_im2col_f32": [vp, i32, lng, i32, i32, i32, i32, i32, vp, vp],
     "mava_t32_col2im_f32": [vp, i32, lng, i32, i32, i32, i32, i32, vp, vp],
+    "mava_conv_fwd_f32": [vp, vp, i32, lng, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
+    "mava_conv_bwd_data_f32": [vp, vp, lng, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "mava_conv_bwd_weight_f32": [vp, vp, i32, lng, i32, i32, i32, i32, i32, i32, vp, f32, vp, lng, i32, vp],
     "mava_t32_flatten_f32": [vp, lng, i32, i32, i32, vp, vp],
     "mava_comm_unique_id": [vp],
     "mava_comm_create": [vp, i32, i32, vp],

@@ -44,6 +44,7 @@ HIP_SOURCES = [
     "rec_step_h2.hip",
     "rec_out_h2.hip",
     "generic_layers.hip",
+    "conv_direct.hip",
     "mat.hip",
     "mat_act.hip",
 ]

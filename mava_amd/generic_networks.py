@@ -17,6 +17,7 @@ observation-independent continuous head.  tree() exposes Flax-shaped views of it
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -69,18 +70,29 @@ def _same_out(n: int, stride: int) -> int:
 
 
 class _Layer:
-    __slots__ = ("kind", "K", "N", "ln", "act", "w", "b", "lnb", "name", "geo", "rows_mul", "src_flat")
+    __slots__ = ("kind", "K", "N", "ln", "act", "w", "b", "lnb", "name", "geo", "rows_mul", "src_flat", "direct")
+
+
+def _conv_direct_serves(H: int, W: int, C: int, k: int, stride: int, cout: int) -> bool:
+    """The envelope of csrc/conv_direct.hip (include/mava_hip.h: mava_conv_fwd_f32)."""
+    return k <= 4 and stride <= 3 and C <= 64 and cout in (32, 64) and H <= 32 and W <= 32
 
 
 class GenericNet:
     """torso (MLP or CNN) + Dense heads, forward / backward on T32 matrices."""
 
     ctx = None  # the owning learner's context handle (_lib.Ctx: arithmetic of the products); None = exact f32
+    # conv layers: "im2col" (patch matrix in memory + the dense products) or "direct" (csrc/conv_direct.hip, opt-in with
+    # MAVA_CONV_DIRECT=1 when the net is built; a layer outside its envelope keeps im2col).  Workspaces follow the setting
+    # they were built under.
+    conv = "im2col"
 
     def __init__(self, torso, din: int, heads: List[Tuple[str, int, float]], obs_shape: Optional[Tuple[int, int, int]] = None,
                  raw_tail: int = 0):
         self.torso, self.din, self.heads_spec, self.raw_tail = torso, int(din), heads, int(raw_tail)
         self.layers: List[_Layer] = []
+        if os.environ.get("MAVA_CONV_DIRECT", "0") == "1":
+            self.conv = "direct"
         off = 0
         act, ln = ACT[torso.activation], torso.use_layer_norm
         self.is_cnn = isinstance(torso, CNNTorso)
@@ -93,6 +105,7 @@ class GenericNet:
                 L = _Layer()
                 L.kind, L.K, L.N, L.ln, L.act, L.name = "conv", k * k * C, int(co), ln, act, f"Conv_{i}"
                 L.geo, L.src_flat = (H, W, C, int(k), int(st)), int(i == 0)
+                L.direct = _conv_direct_serves(H, W, C, int(k), int(st), int(co))
                 H, W = _same_out(H, st), _same_out(W, st)
                 mul = H * W
                 L.rows_mul = mul
@@ -109,6 +122,7 @@ class GenericNet:
             for i, n in enumerate(torso.layer_sizes):
                 L = _Layer()
                 L.kind, L.K, L.N, L.ln, L.act, L.name, L.rows_mul, L.geo, L.src_flat = "dense", K, int(n), ln, act, f"Dense_{i}", 1, None, 0
+                L.direct = False
                 L.w, off = off, off + L.K * L.N
                 L.b, off = off, off + L.N
                 L.lnb = off if ln else -1
@@ -120,6 +134,7 @@ class GenericNet:
         for name, n_out, _scale in heads:
             L = _Layer()
             L.kind, L.K, L.N, L.ln, L.act, L.name, L.rows_mul, L.geo, L.src_flat = "head", self.feat, int(n_out), False, 0, name, 1, None, 0
+            L.direct = False
             L.w, off = off, off + L.K * L.N
             L.b, off = off, off + L.N
             L.lnb = -1
@@ -225,6 +240,9 @@ class GenericNet:
                     tail = slabs[:, kb * nb : kb * nb + nb].contiguous()
                     ops.slab_reduce(tail, nb, gb[n0 : n0 + nb], accumulate=accumulate if gb_accumulate is None else gb_accumulate)
 
+    def serves_direct(self, ly: _Layer) -> bool:
+        return self.conv == "direct" and ly.direct
+
     # ----------------------------------------------------------------------------------- forward / backward
     def workspace(self, rows: int, device, training: bool) -> "GenericWorkspace":
         return GenericWorkspace(self, rows, device, training)
@@ -249,6 +267,16 @@ class GenericNet:
         for i, ly in enumerate(self.layers):
             w = flat[ly.w : ly.w + ly.K * ly.N]
             b = flat[ly.b : ly.b + ly.N]
+            if self.serves_direct(ly):  # z (and y = act(z) without layer norm) in one launch, no patch matrix
+                H, W, C, k, st = ly.geo
+                lrows = rows * ly.rows_mul
+                launch("conv_fwd", L.mava_conv_fwd_f32, ctx_ptr(self.ctx), ptr(cur), ly.src_flat, rows, H, W, C, k, st, ly.N, ptr(w), ptr(b),
+                       ly.act, ptr(ws.z[i]), None if ly.ln else ptr(ws.y[i]), s)
+                if ly.ln:
+                    check(L.mava_t32_norm_act_f32(ptr(ws.z[i]), ly.N, lrows, 1, ptr(flat[ly.lnb : ly.lnb + ly.N]), ly.act, ptr(ws.y[i]),
+                                                  ptr(ws.xhat[i]), ptr(ws.rstd[i]), s), "norm_act")
+                cur, cur_ld, cur_rows = ws.y[i], ly.N, lrows
+                continue
             if ly.kind == "conv":
                 H, W, C, k, st = ly.geo
                 check(L.mava_t32_im2col_f32(ptr(cur), ly.src_flat, rows, H, W, C, k, st, ptr(ws.col[i]), s), "im2col")
@@ -303,6 +331,22 @@ class GenericNet:
 
                 check(L.mava_t32_colsum_f32(ptr(ws.dz[i]), ly.N, lrows, inv, ptr(ws.slabs), ws.slabs.shape[1], ws.slabs.shape[0], s), "colsum")
                 ops.slab_reduce(ws.slabs, ly.N, grad_out[ly.lnb : ly.lnb + ly.N], accumulate=accumulate)
+            if self.serves_direct(ly):
+                from . import ops
+
+                assert i > 0 or dx_out is None, "dx_out is implemented for dense first layers"
+                H, W, C, k, st = ly.geo
+                src = ws.x_src if i == 0 else ws.y[i - 1]
+                launch("conv_bwd_weight", L.mava_conv_bwd_weight_f32, ctx_ptr(self.ctx), ptr(src), ly.src_flat, rows, H, W, C, k, st, ly.N,
+                       ptr(ws.dzin[i]), grad_scale, ptr(ws.slabs), ws.slabs.shape[1], ws.slabs.shape[0], s)
+                ops.slab_reduce(ws.slabs, ly.K * ly.N, grad_out[ly.w : ly.w + ly.K * ly.N], accumulate=accumulate)
+                ops.slab_reduce_cols(ws.slabs, ly.K * ly.N, ly.N, grad_out[ly.b : ly.b + ly.N], accumulate=accumulate)
+                if i == 0:
+                    break
+                launch("conv_bwd_data", L.mava_conv_bwd_data_f32, ctx_ptr(self.ctx), ptr(ws.dzin[i]), rows, H, W, C, k, st, ly.N,
+                       ptr(flat[ly.w : ly.w + ly.K * ly.N]), ptr(ws.dy[i - 1]), s)
+                d_cur = ws.dy[i - 1]
+                continue
             if ly.kind == "conv":
                 x_ptr, x_ld = ws.col[i].data_ptr(), ly.K
             elif i == 0:
@@ -343,12 +387,13 @@ class GenericWorkspace:
             self.y.append(f(lr * ly.N))
             self.xhat.append(f(lr * ly.N) if ly.ln else None)
             self.rstd.append(f(lr) if ly.ln else None)
-            self.col.append(f(lr * ly.K) if ly.kind == "conv" else None)
+            patches = ly.kind == "conv" and not net.serves_direct(ly)  # (the direct kernels form them in LDS)
+            self.col.append(f(lr * ly.K) if patches else None)
             if training:
                 self.dz.append(f(lr * ly.N))
                 self.dzin.append(f(lr * ly.N) if ly.ln else self.dz[-1])
                 self.dy.append(f(lr * ly.N))
-                self.dcol.append(f(lr * ly.K) if ly.kind == "conv" else None)
+                self.dcol.append(f(lr * ly.K) if patches else None)
         self.feat = f(rows * net.feat) if net.is_cnn else None
         self.feat_in = None
         self.out = [f(rows * hd.N) for hd in net.heads]
@@ -358,7 +403,8 @@ class GenericWorkspace:
             max_rows = rows * max([ly.rows_mul for ly in net.layers] + [1])
             n_slab = max(1, min(256, max_rows // 32))
             min_tiles = rows // 32  # every X^T Y block must own a tile of the smallest product
-            self.slabs = torch.zeros((max(1, min(n_slab, min_tiles)), 128 * 128 + 128 + 8), device=device)
+            width = max([128 * 128 + 128 + 8] + [ly.K * ly.N + ly.N for ly in net.layers if net.serves_direct(ly)])
+            self.slabs = torch.zeros((max(1, min(n_slab, min_tiles)), width), device=device)
             self.loss_partials = torch.zeros((1024, 2), device=device)
 
 

@@ -2,6 +2,7 @@
 """Connector measurements (DESIGN.md "Connector"; bench.py's headline is not involved).
 
     python tools/connector_bench.py [--out profiles/connector_bench.json] [--skip-learners]
+    python tools/connector_bench.py --conv direct|im2col|both [--out profiles/conv_direct_bench.json]
     python tools/connector_bench.py --curve [--calls N --lr X --envs E --rollout T] [--out profiles/connector_learning_curve.json]
 
 Default mode: the device time of one env step launch, graph-replayed (20 launches per graph, warm-up, median of 5), for
@@ -106,6 +107,37 @@ def throughput(system: str, network: str, scenario: str, E: int, steps: int, war
     return res
 
 
+def conv_compare(which: str, dev) -> dict:
+    """ff_mappo network=cnn on con-5x5x3a x 1024 envs with the conv layers on im2col and / or the direct kernels
+    (csrc/conv_direct.hip; MAVA_CONV_DIRECT), two alternating rounds in this process: ms per update (median of three learn()
+    calls), peak device memory, and the device time of every launch of the three direct kernels during one learn() call."""
+    from mava_amd import _lib
+
+    out = {"rounds": []}
+    settings = ["im2col", "direct"] if which == "both" else [which]
+    for rnd in range(2):
+        for conv in settings:
+            os.environ["MAVA_CONV_DIRECT"] = "1" if conv == "direct" else "0"
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            res = throughput("ff_mappo", "cnn", "con-5x5x3a", 1024, 3, 1, dev)
+            res.update(conv=conv, round=rnd, peak_device_bytes=torch.cuda.max_memory_allocated())
+            out["rounds"].append(res)
+    if "direct" in settings:
+        os.environ["MAVA_CONV_DIRECT"] = "1"
+        _lib.TIMERS = {}
+        try:
+            throughput("ff_mappo", "cnn", "con-5x5x3a", 1024, 1, 0, dev)
+            torch.cuda.synchronize()
+            out["direct_kernel_us_per_launch"] = {
+                name: {"launches": len(ev), "median_us": sorted(1e3 * a.elapsed_time(b) for a, b in ev)[len(ev) // 2]}
+                for name, ev in _lib.TIMERS.items() if name.startswith("conv_")}
+        finally:
+            _lib.TIMERS = None
+    os.environ.pop("MAVA_CONV_DIRECT", None)
+    return out
+
+
 def _transition(E, A, dev):
     return (torch.empty((E, A), device=dev), torch.empty((E, A), dtype=torch.uint8, device=dev), torch.empty(E, device=dev),
             torch.empty(E, dtype=torch.int32, device=dev), torch.empty(E, dtype=torch.uint8, device=dev))
@@ -172,6 +204,8 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=None)
     ap.add_argument("--rollout", type=int, default=None)
     ap.add_argument("--network", default=None)
+    ap.add_argument("--conv", choices=["direct", "im2col", "both"], default=None,
+                    help="only the network=cnn row, with its conv layers on these kernels (profiles/conv_direct_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -183,6 +217,8 @@ def main() -> None:
                                 ("network", args.network)) if v is not None}
         curve = learning_curve(dev, log=lambda m: print(m, file=sys.stderr, flush=True), **ov)
         out = {"config": dict(CURVE, **ov), "curve [updates, seconds, mean eval return]": curve, "measured_gain": gain(curve)}
+    elif args.conv:
+        out = {"device": torch.cuda.get_device_name(0), "conv": conv_compare(args.conv, dev)}
     else:
         out = {"device": torch.cuda.get_device_name(0), "env_step_graph_timed": step_device_times(dev)}
         if not args.skip_learners:
