@@ -878,6 +878,33 @@ int mava_sac_actor_grad_f32(int rows, int n_real, int A, int action_dim, float m
  * d loss / d log_alpha; loss_parts (A): each agent's share (their sum is the loss). */
 int mava_sac_alpha_loss_f32(int n_real, int A, const float* log_prob, const float* log_alpha, float target_entropy,
                             float* grad, float* loss_parts, mava_stream_t s);
+/* Fused train step (mava_amd/csrc/sac_fused.hip): update_q and the actor update as one launch each, for MLPTorso [128, 128]
+ * relu torsos without layer norm in f16x2 arithmetic.  Both read the sampled batch row-major at real row b * A + agent (obs /
+ * next_obs (B A, O), action (B A, action_dim), reward / done (B A), gs / next_gs (B, S) when joint) and the networks in
+ * GenericNet's flat layout (actor: [W1 (O,128) | b1 | W2 | b2 | mean W, b | log_std W, b]; q / q_target: [q1 | q2], each
+ * [W1 (Kq,128) | b1 | W2 | b2 | W3 | b3], Kq = O + action_dim, or S + A action_dim when joint).  A tile of 32 rows holds
+ * floor(32 / A) whole items; n_tiles = ceil(B / floor(32 / A)).  Noise: the standard normal of (real row, step, component) in
+ * the stream "SACN" of key `seed`, as mava_sac_sample_f32 with row_offset 0.  Both return 1 (nothing launched) outside
+ * action_dim <= 16, A <= 16, O + 1 <= 128, Kq + 1 <= 128.
+ *
+ * mava_sac_q_update_f32: the target (actor on next_obs, sample, both target networks), both online networks forward, the
+ * loss and the backward chains.  slab (n_tiles, slab_stride >= 2 Pq): per tile the gradient of [q1 | q2] (their sum over
+ * tiles is the gradient); partials (n_tiles, 4): per-tile sums of [q1_loss, q2_loss, mean q1, mean q2]; target (B A) and
+ * eps (B A, action_dim) may be NULL. */
+int mava_sac_q_update_f32(int joint, int B, int A, int O, int action_dim, int S, const float* obs, const float* next_obs,
+                          const float* action, const float* reward, const uint8_t* done, const float* gs, const float* next_gs,
+                          const float* actor, const float* q, const float* q_target, const float* log_alpha, float gamma,
+                          float min_scale, uint64_t seed, uint32_t step, float* slab, long slab_stride, float* partials,
+                          float* target, float* eps, mava_stream_t s);
+/* mode 0: actor_loss_fn's gradient: the actor on obs with its sample, both online Q networks on [obs | new action] (joint:
+ * [gs | stored joint action with the row's own slot new]) forward and backward to the input, mava_sac_actor_grad_f32's
+ * d mean / d raw log_std, and the actor's backward chain.  slab (n_tiles, slab_stride >= the actor's parameter count),
+ * partials (n_tiles, 2): per-tile sums of [actor loss, mean log_prob].  mode 1: forward and sample alone; writes
+ * log_prob (B A).  eps (B A, action_dim) may be NULL in both modes; mode 1 reads neither action, gs, q nor log_alpha. */
+int mava_sac_actor_update_f32(int mode, int joint, int B, int A, int O, int action_dim, int S, const float* obs,
+                              const float* action, const float* gs, const float* actor, const float* q, const float* log_alpha,
+                              float min_scale, uint64_t seed, uint32_t step, float* slab, long slab_stride, float* partials,
+                              float* log_prob, float* eps, mava_stream_t s);
 
 /* T32 <-> row-major conversion of a (rows x N) matrix. */
 int mava_t32_convert_f32(const float* src, int N, int rows, int to_t32, float* dst, mava_stream_t s);

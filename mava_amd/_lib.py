@@ -82,6 +82,8 @@ _SIGNATURES = {
     "mava_sac_q_loss_f32": [i32] * 3 + [vp] * 8 + [f32, f32] + [vp] * 4 + [i32, vp],
     "mava_sac_actor_grad_f32": [i32] * 4 + [f32] + [vp] * 9 + [i32, i32, i32, f32, f32] + [vp] * 3 + [i32, vp],
     "mava_sac_alpha_loss_f32": [i32, i32, vp, vp, f32, vp, vp, vp],
+    "mava_sac_q_update_f32": [i32] * 6 + [vp] * 11 + [f32, f32, u64, u32, vp, lng, vp, vp, vp, vp],
+    "mava_sac_actor_update_f32": [i32] * 7 + [vp] * 6 + [f32, u64, u32, vp, lng, vp, vp, vp, vp],
     "mava_rollout_ff_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18
                            + [vp, vp, f32, f32] + [vp] * 7 + [vp],
     "mava_rollout_ff_flags_f32": [vp, i32, vp, i32, i32, i32, i32, i32, i32, u64, u64, u32, u32, u32, i32] + [vp] * 18

@@ -36,6 +36,7 @@ HIP_SOURCES = [
     "q_learning.hip",
     "qmix.hip",
     "sac.hip",
+    "sac_fused.hip",
     "rec_dense.hip",
     "rec_dense_h2.hip",
     "rec_gru.hip",

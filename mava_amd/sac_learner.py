@@ -18,19 +18,26 @@ backward chain, mava_clip_adam, then (autotune) the actor pass again, mava_sac_s
 mava_clip_adam on log_alpha.  The policy-delay test, the buffer head and the noise counters are host arithmetic on step
 counts: nothing synchronises the host per step or per epoch.
 
+With MAVA_SAC_FUSED=1 at construction and a configuration `sac_fused_mode` accepts, the layer chains of a train step run as
+mava_sac_q_update_f32 and mava_sac_actor_update_f32 (csrc/sac_fused.hip): replay sample, the Q kernel, its slab sums,
+mava_clip_adam and the target update, then per actor update the actor kernel (mode 0), its slab sums, mava_clip_adam and
+(autotune) the actor kernel again (mode 1: the log-prob), mava_sac_alpha_loss_f32 and mava_clip_adam.  Acting, the noise
+counters, the delay rule and the metrics are the same in both modes.
+
 `done` of a stored transition is the env's `terminated` flag (a time-limit end is a truncation and keeps the bootstrap),
 which is what the reference's `~discount` is under Jumanji's truncation.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Dict, Optional
 
 import torch
 
 from . import ops
 from ._lib import launch, lib, ptr, stream_ptr
-from .generic_networks import CNNTorso, GenericActor, GenericNet, torso_from_config
+from .generic_networks import CNNTorso, GenericActor, GenericNet, is_default_mlp, torso_from_config
 from .learner_common import bind_learn, pad32
 from .networks import make_action_head
 from .replay_learner import ReplayLearner
@@ -41,6 +48,24 @@ from .utils.tree import tree_to
 ADAM_EPS = 1e-8  # optax.adam's default (ff_isac.py:146-152), not PPO's 1e-5
 TRAIN_KEY_TAG = 0x545241494E  # "TRAIN": xor-ed into the key of the train steps' noise, apart from the acting noise
 LOSS_BLOCKS = 8
+
+
+def sac_fused_mode(matmul_mode: str, actor_torso: Any, q_torso: Any, action_dim: int, obs_dim: int, q_dim: int, num_agents: int,
+                   env=None) -> bool:
+    """Whether a train step runs on the two fused kernels (csrc/sac_fused.hip: mava_sac_q_update_f32 and
+    mava_sac_actor_update_f32) instead of the layer-wise chain: only with MAVA_SAC_FUSED=1, f16x2 arithmetic, both pre-torsos
+    MLPTorso [128, 128] relu without layer norm, and widths the kernels instantiate (the input of a network plus one column
+    within one 128-feature image).  `actor_torso` / `q_torso`: the pre_torso configurations; `q_dim`: the Q input width."""
+    env = os.environ if env is None else env
+    return (env.get("MAVA_SAC_FUSED", "0") == "1" and matmul_mode == "f16x2" and is_default_mlp(actor_torso) and is_default_mlp(q_torso)
+            and action_dim <= 16 and num_agents <= 16 and obs_dim + 1 <= 128 and q_dim + 1 <= 128)
+
+
+def sac_tiles(batch_size: int, num_agents: int):
+    """(items per 32-row tile, tiles, real rows of the last tile): a tile holds whole items, so the last one may be partial."""
+    it = 32 // num_agents
+    n_tiles = -(-batch_size // it)
+    return it, n_tiles, (batch_size - (n_tiles - 1) * it) * num_agents
 
 
 class QNetwork:
@@ -165,6 +190,13 @@ class SACLearner(ReplayLearner):
         # counts the items stored and t_train is the train noise's counter too
         self.t = 0
         self._explore_gen = torch.Generator(device=d)
+        # ---- the fused train step (opt-in): one gradient slab per 32-row tile, summed by ops.slab_reduce
+        self.fused = sac_fused_mode(self.ctx.matmul_mode, config.network.actor_network.pre_torso, config.network.critic_network.pre_torso,
+                                    D, O, self.Kq, A)
+        if self.fused:
+            n_tiles = sac_tiles(self.B, A)[1]
+            self.slab_q, self.slab_a = z(n_tiles, 2 * Pq), z(n_tiles, Pa)
+            self.fq_partials, self.fpi_partials = z(n_tiles, 4), z(n_tiles, 2)
 
     # ------------------------------------------------------------------------------------ setup
     def init_params(self, actor_seed: int, q_seeds) -> None:
@@ -248,6 +280,21 @@ class SACLearner(ReplayLearner):
         L_, s, sm = lib(), stream_ptr(), self.smp
         Rp, BA, Pq = self.Rp, self.BA, self.Pq
         key = self.seed ^ TRAIN_KEY_TAG
+        if self.fused:
+            launch("sac_q_update", L_.mava_sac_q_update_f32, int(self.centralised), self.B, self.A, self.O, self.D, self.S, ptr(sm.obs[0]),
+                   ptr(sm.next_obs[0]), ptr(sm.action), ptr(sm.reward), ptr(sm.done), ptr(sm.obs[1]), ptr(sm.next_obs[1]), ptr(self.pa),
+                   ptr(self.pq), ptr(self.pqt), ptr(self.log_alpha), self.gamma, self.min_scale, key & (2**64 - 1),
+                   (3 * self.t_train) & 0xFFFFFFFF, ptr(self.slab_q), 2 * Pq, ptr(self.fq_partials), ptr(self.target), ptr(self.eps), s)
+            if self.debug is not None:
+                self.debug["eps_q"].append(self.eps.clone())
+            ops.slab_reduce(self.slab_q, 2 * Pq, self.gq)
+            ops.slab_reduce(self.fq_partials, 4, self.train_metrics[n, k, :4])
+            if self.debug is not None:
+                self.debug["g_q"].append(self.gq.clone())
+                self.debug["target"].append(self.target.clone())
+            self._adam(self.pq, self.gq, self.mq, self.vq, 1, self.q_lr)
+            launch("target_update", L_.mava_target_update_f32, 2 * Pq, ptr(self.pq), ptr(self.pqt), self.tau, 0, s)
+            return
         self._pi(self.ws_pi_inf, sm.next_obs[0], Rp, BA, key, 3 * self.t_train, self.new_action, self.logp, self.eps)
         if self.debug is not None:
             self.debug["eps_q"].append(self.eps.clone())
@@ -276,6 +323,18 @@ class SACLearner(ReplayLearner):
         key = self.seed ^ TRAIN_KEY_TAG
         an, ws = self.actor_network.net, self.ws_pi
         for _ in range(self.delay):
+            if self.fused:  # the actor gradient in one launch, the log-prob of the alpha step in another
+                self._fused_actor(0, 3 * self.t_train + 1)
+                ops.slab_reduce(self.slab_a, self.Pa, self.ga)
+                ops.slab_reduce(self.fpi_partials, 1, self.train_metrics[n, k, 4:5])
+                if self.debug is not None:
+                    self.debug["g_actor"].append(self.ga.clone())
+                    self.debug["eps_actor"].append(self.eps.clone())
+                self._adam(self.pa, self.ga, self.ma, self.va, 0, self.policy_lr)
+                if self.autotune:
+                    self._fused_actor(1, 3 * self.t_train + 2)
+                    self._alpha_step(n, k)
+                continue
             self._pi(ws, sm.obs[0], Rp, BA, key, 3 * self.t_train + 1, self.new_action, None, self.eps)
             self._concat(self.x_q, False, sm.action if self.centralised else self.new_action,
                          self.new_action if self.centralised else None)
@@ -297,13 +356,26 @@ class SACLearner(ReplayLearner):
             self._adam(self.pa, self.ga, self.ma, self.va, 0, self.policy_lr)
             if self.autotune:  # :367-381: the log-prob under the UPDATED actor, with `key` itself as the noise key
                 self._pi(self.ws_pi_inf, sm.obs[0], Rp, BA, key, 3 * self.t_train + 2, self.new_action, self.logp, self.eps)
-                launch("sac_alpha_loss", L_.mava_sac_alpha_loss_f32, BA, A, ptr(self.logp), ptr(self.log_alpha), self.target_entropy,
-                       ptr(self.gl), ptr(self.alpha_parts), s)
-                ops.slab_reduce(self.alpha_parts.view(A, 1), 1, self.train_metrics[n, k, 5:6])
-                if self.debug is not None:
-                    self.debug["g_alpha"].append(self.gl.clone())
-                    self.debug["eps_alpha"].append(self.eps.clone())
-                self._adam(self.log_alpha, self.gl, self.ml, self.vl, 2, self.alpha_lr)
+                self._alpha_step(n, k)
+
+    def _alpha_step(self, n: int, k: int) -> None:
+        """:367-381 from self.logp on: alpha_loss_fn's gradient and the Adam step on log_alpha."""
+        A = self.A
+        launch("sac_alpha_loss", lib().mava_sac_alpha_loss_f32, self.BA, A, ptr(self.logp), ptr(self.log_alpha), self.target_entropy,
+               ptr(self.gl), ptr(self.alpha_parts), stream_ptr())
+        ops.slab_reduce(self.alpha_parts.view(A, 1), 1, self.train_metrics[n, k, 5:6])
+        if self.debug is not None:
+            self.debug["g_alpha"].append(self.gl.clone())
+            self.debug["eps_alpha"].append(self.eps.clone())
+        self._adam(self.log_alpha, self.gl, self.ml, self.vl, 2, self.alpha_lr)
+
+    def _fused_actor(self, mode: int, step: int) -> None:
+        """mava_sac_actor_update_f32: mode 0 the actor gradient slabs and loss partials, mode 1 self.logp under the actor as it is."""
+        sm = self.smp
+        launch("sac_actor_update", lib().mava_sac_actor_update_f32, mode, int(self.centralised), self.B, self.A, self.O, self.D, self.S,
+               ptr(sm.obs[0]), ptr(sm.action), ptr(sm.obs[1]), ptr(self.pa), ptr(self.pq), ptr(self.log_alpha), self.min_scale,
+               (self.seed ^ TRAIN_KEY_TAG) & (2**64 - 1), step & 0xFFFFFFFF, ptr(self.slab_a), self.Pa, ptr(self.fpi_partials),
+               ptr(self.logp), ptr(self.eps), stream_ptr())
 
     def _train_step(self, n: int, k: int, t: int) -> None:
         """:387-416 with `t` the env-step counter entering the update step."""

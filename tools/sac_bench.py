@@ -2,11 +2,17 @@
 """Soft actor-critic timings (DESIGN.md "Soft actor-critic"; bench.py's headline is not involved).
 
     python tools/sac_bench.py [--out profiles/sac_bench.json]
+    python tools/sac_bench.py --fused [--out profiles/sac_fused_bench.json]
 
 For ff_isac and ff_masac on spread-3a with the reference's system defaults (batch 32, epochs 32, rollout_length 2, policy
 delay 4 - at num_envs 16 every epoch trains the actor four times): wall ms per update step and per train step (epoch),
 env-steps/s through learn(), and the kernel launches of one update step counted through the library's launch hook.
 Warm-up first, median of 3 timed repeats of `--updates` update steps each, the device synchronised around every repeat.
+
+--fused: the fused train step (MAVA_SAC_FUSED=1, csrc/sac_fused.hip) against the layer-wise one in the same process: one
+learner per mode from the same seeds, both warmed up, then the timed repeats alternate between the modes; "faster" is
+claimed by DESIGN.md section 3.10's rule alone (every fused repeat below every layer-wise one, the gap at least three
+times the larger within-mode spread).
 """
 from __future__ import annotations
 
@@ -59,19 +65,82 @@ def measure(system: str, dev, updates: int, overrides=()) -> dict:
             "launch_calls_per_update_step": counted, "launch_calls_per_update_step_total": sum(counted.values())}
 
 
+def _learner(system: str, dev, updates: int, overrides, fused: bool):
+    from mava_amd import envs
+    from mava_amd.config import compose
+
+    mod = importlib.import_module(f"mava_amd.systems.sac.{system}")
+    cfg = compose(f"default_{system}_spread", ["system.buffer_size=100000", "system.explore_steps=1024", *overrides])
+    cfg.system.num_updates_per_eval = updates
+    env, _ = envs.make(cfg, add_global_state=system == "ff_masac", device=dev)
+    os.environ["MAVA_SAC_FUSED"] = "1" if fused else "0"  # read once, when the learner is built
+    try:
+        learn, _net, state = mod.learner_setup(env, [1, 2, 3, 4, 5, 6], cfg, device=dev)
+    finally:
+        del os.environ["MAVA_SAC_FUSED"]
+    assert learn.learner.fused == fused, "the fused mode does not serve this configuration"
+    learn.explore()
+    state = learn(state).learner_state  # warm-up
+    torch.cuda.synchronize()
+    return learn, state
+
+
+def measure_pair(system: str, dev, updates: int, overrides=(), repeats: int = 5) -> dict:
+    from mava_amd import _lib
+
+    modes = {"layer_wise": _learner(system, dev, updates, overrides, False), "fused": _learner(system, dev, updates, overrides, True)}
+    times = {m: [] for m in modes}
+    for _ in range(repeats):
+        for m, (learn, state) in list(modes.items()):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            state = learn(state).learner_state
+            torch.cuda.synchronize()
+            times[m].append(time.perf_counter() - t0)
+            modes[m] = (learn, state)
+    L = modes["fused"][0].learner
+    out = {"workload": f"{system} env=spread spread-3a network=continuous_mlp", "overrides": list(overrides), "envs": L.E,
+           "rollout_length": L.T, "epochs": L.K, "batch_size": L.B, "policy_update_delay": L.delay, "matmul_mode": L.matmul_mode,
+           "updates": updates, "repeats": repeats, "modes": {}}
+    for m, (learn, _state) in modes.items():
+        Lm = learn.learner
+        Lm.n_upd = 1
+        _lib.TIMERS = {}
+        Lm.update(0)
+        torch.cuda.synchronize()
+        counted = {k: len(v) for k, v in _lib.TIMERS.items()}
+        _lib.TIMERS = None
+        ms = [1e3 * t / updates for t in times[m]]
+        out["modes"][m] = {"ms_per_update": statistics.median(ms), "ms_per_train_step": statistics.median(ms) / L.K,
+                           "ms_per_update_all": [round(v, 3) for v in ms], "launch_calls_per_update_step": counted,
+                           "launch_calls_per_update_step_total": sum(counted.values())}
+    a, b = out["modes"]["layer_wise"]["ms_per_update_all"], out["modes"]["fused"]["ms_per_update_all"]
+    spread = max(max(a) - min(a), max(b) - min(b))
+    out["fused_faster"] = bool(max(b) < min(a) and min(a) - max(b) >= 3.0 * spread)
+    out["speedup_of_medians"] = out["modes"]["layer_wise"]["ms_per_update"] / out["modes"]["fused"]["ms_per_update"]
+    return out
+
+
+LARGE = ["arch.num_envs=64", "system.batch_size=256", "system.epochs=2", "system.policy_update_delay=2"]
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--updates", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fused", action="store_true", help="fused against layer-wise train step, alternating in one process")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sac_bench.py measures on the GPU; no GPU found")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    out = {"device": torch.cuda.get_device_name(0),
-           "results": [measure("ff_isac", dev, args.updates), measure("ff_masac", dev, args.updates),
-                       measure("ff_isac", dev, args.updates, ["arch.num_envs=64", "system.batch_size=256", "system.epochs=2",
-                                                              "system.policy_update_delay=2"])]}
+    if args.fused:
+        out = {"device": torch.cuda.get_device_name(0),
+               "results": [measure_pair(sys_, dev, args.updates, ov) for ov in ([], LARGE) for sys_ in ("ff_isac", "ff_masac")]}
+    else:
+        out = {"device": torch.cuda.get_device_name(0),
+               "results": [measure("ff_isac", dev, args.updates), measure("ff_masac", dev, args.updates),
+                           measure("ff_isac", dev, args.updates, LARGE)]}
     print(json.dumps(out))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
