@@ -1066,6 +1066,32 @@ int mava_transformer_act_continuous_f32(const float* params, const float* agents
                                         uint32_t row_offset, int greedy, float* action, float* log_prob, float* value,
                                         void* workspace, size_t workspace_bytes, int n_blocks, mava_stream_t s);
 
+/* ---- ff_mat, fused training pass (csrc/mat_train.hip): the teacher-forced pass of MATPass.encode + decode in ONE launch and
+ *      its backward pass in a second one.  A workgroup carries groups of max(1, 32 / A) consecutive minibatch samples through
+ *      the whole network; dense products on the exact-f32 MFMA whatever the context's matmul mode, everything between them in
+ *      mat.hip's arithmetic.  Row b * A + j of the minibatch reads agent j of sample idx[b] of agents_view (n_samples, A, O) and
+ *      of action (n_samples, A).  Contract: idx in [0, n_samples) and action in [0, n_actions); the kernel clamps a value outside
+ *      its range so that a corrupt trajectory cannot read out of bounds, it does not report it.  1 <= A <= 32, n_head divides D,
+ *      1 <= n_actions <= 64, 1 <= O <= 1024.  Both launches return 1 ("not instantiated", nothing launched) when D is not one of
+ *      32, 64, 96, 128 or n_block > 4. */
+/* bytes of the backward launch's device workspace: (12 + 26 n_block) saved activations of 32 x D + 32 floats per block of the
+ * grid; 0 for a shape without an instance */
+size_t mava_transformer_train_workspace_bytes(int Bm, int A, int O, int D, int n_block, int n_blocks);
+/* logits: T32 (ceil32(Bm * A) rows x n_actions); value: ceil32(Bm * A) floats - the layouts mava_mat_loss_f32 reads; padding
+ * rows are written as exact zeros.  Bit-identical for any n_blocks.  The forward launch needs no workspace. */
+int mava_transformer_train_fwd_f32(const float* params, const float* agents_view, long n_samples, const int32_t* idx,
+                                   const int32_t* action, int Bm, int A, int O, int n_actions, int D, int n_head, int n_block,
+                                   float* logits, float* value, int n_blocks, mava_stream_t s);
+/* dlogits, dvalues: what mava_mat_loss_f32 wrote (times grad_scale).  slab (n_blocks, slab_stride >= parameter count): row i
+ * receives block i's sum of the parameter gradient, already times 1 / grad_scale, in the flat layout of
+ * mava_transformer_param_count; the launch zeroes every row itself and mava_slab_reduce_f32 sums them.  workspace: at least
+ * mava_transformer_train_workspace_bytes(...) bytes, 16-byte aligned, never read before it is written in the same launch.
+ * Bit-identical run to run for a given n_blocks; the summed gradient depends on n_blocks like every slab. */
+int mava_transformer_train_bwd_f32(const float* params, const float* agents_view, long n_samples, const int32_t* idx,
+                                   const int32_t* action, int Bm, int A, int O, int n_actions, int D, int n_head, int n_block,
+                                   const float* dlogits, const float* dvalues, float grad_scale, float* slab, long slab_stride,
+                                   void* workspace, size_t workspace_bytes, int n_blocks, mava_stream_t s);
+
 /* ---- exchange step: replaces the jax.lax.pmean calls of mava/systems/ppo/ff_mappo.py:224-238
  *      (actor and critic (grads, loss_info) over the "batch" and "device" axes) for a host without torch.distributed.
  *      One process per GPU: rank 0 obtains a 128-byte id (mava_comm_unique_id) and hands it to the other ranks by any

@@ -146,10 +146,14 @@ _SIGNATURES = {
     "mava_transformer_param_count_continuous": [i32, i32, i32, i32],
     "mava_transformer_act_continuous_f32": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, u64, u32, u32, i32, vp, vp, vp, vp, C.c_size_t,
                                             i32, vp],
+    "mava_transformer_train_workspace_bytes": [i32, i32, i32, i32, i32, i32],
+    "mava_transformer_train_fwd_f32": [vp, vp, lng, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
+    "mava_transformer_train_bwd_f32": [vp, vp, lng, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, lng, vp, C.c_size_t, i32,
+                                       vp],
 }
 _RESTYPES = {"mava_last_error": C.c_char_p, "mava_rec_step_pack_bytes": C.c_long, "mava_ppo_finish_workspace_bytes": C.c_size_t,
              "mava_transformer_param_count": C.c_long, "mava_transformer_act_workspace_bytes": C.c_size_t,
-             "mava_transformer_param_count_continuous": C.c_long}
+             "mava_transformer_param_count_continuous": C.c_long, "mava_transformer_train_workspace_bytes": C.c_size_t}
 
 
 def declared_symbols():

@@ -48,6 +48,7 @@ HIP_SOURCES = [
     "conv_direct.hip",
     "mat.hip",
     "mat_act.hip",
+    "mat_train.hip",
 ]
 CPP_SOURCES = ["api.cpp", "comm.cpp"]
 
@@ -56,6 +57,9 @@ HIP_FLAGS = [f"--offload-arch={ARCH}", "-ffp-contract=fast", "-Wno-unused-result
 # developer knobs: MAVA_HIPCC_EXTRA="-DMAVA_FAST_BUILD -DMAVA_STAMPS" builds a diagnostic library
 EXTRA_FLAGS = os.environ.get("MAVA_HIPCC_EXTRA", "").split()
 FLAG_STAMP = os.path.join(CSRC, ".build_flags")
+# per-file flags: mat_train.hip is compiled without packed f32 arithmetic as a whole file (a target attribute on the kernel
+# alone keeps every helper that is not force-inlined, __syncthreads included, out of line)
+FILE_FLAGS = {"mat_train.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _headers():
@@ -85,7 +89,7 @@ def _compile(src: str, verbose: bool) -> str:
         return obj
     cmd = [HIPCC, "-c", path, "-o", obj] + COMMON_FLAGS
     if src.endswith(".hip"):
-        cmd += HIP_FLAGS + EXTRA_FLAGS
+        cmd += HIP_FLAGS + FILE_FLAGS.get(src, []) + EXTRA_FLAGS
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)

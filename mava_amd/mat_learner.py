@@ -11,7 +11,9 @@ Network (discrete actions).  One sample is one (t, env) pair with its A agents i
 Acting is autoregressive: A decoder passes per env step, pass i samples agent i (mava_mat_sample_f32) and the next pass
 sees its action in the shifted one-hot.  Training is one teacher-forced pass.  With network.acting=fused an env step is one
 launch instead (mava_transformer_act_f32, csrc/mat_act.hip: the same network with a key/value cache, f32 dense products
-whatever system.matmul_mode); the bootstrap value and training stay on the layer-wise tapes.
+whatever system.matmul_mode); the bootstrap value stays on the layer-wise tapes.  With network.training=fused (discrete head)
+a minibatch's forward and backward passes are two launches (mava_transformer_train_fwd_f32 / _bwd_f32, csrc/mat_train.hip:
+exact-f32 MFMA products whatever system.matmul_mode) around the unchanged loss launch, instead of the training tape.
 With a ContinuousActionHead (network=continuous_transformer; float64 model tests/mat_continuous_model.py) the decoder's input is
 the shifted ACTION VECTOR (row 0 zero, no start token; act_dense has a bias and runs in exact f32), head_out gives the d means of
 Independent(TanhTransformed(Normal(mean, softplus(log_std) + min_scale))) and decoder/log_std is the flat vector's last leaf;
@@ -47,6 +49,7 @@ from .types import LearnerState, TimeStep
 
 MAX_AGENTS, MAX_EMBED, MAX_ACTIONS = 32, 128, 64  # csrc/mat.hip's limits
 MAX_ACTION_DIM = 16  # ... and of its continuous head (csrc/tanh_normal.h's users)
+TRAINING = ("layerwise", "fused")  # network.training: the tape of MATPass(training=True), or csrc/mat_train.hip's two launches
 ACTING = ("layerwise", "fused")  # network.acting: MATPass.act launches layer by layer, or csrc/mat_act.hip once per env step
 
 
@@ -499,6 +502,7 @@ class MATLearner(PPOLearner):
         net = config.network
         self.D, self.H, self.n_block = int(net.get("n_embd", 64)), int(net.get("n_head", 1)), int(net.get("n_block", 1))
         self.acting = str(net.get("acting", "layerwise"))
+        self.training = str(net.get("training", "layerwise"))
         super().__init__(env, config, False, device)
         s, self.rep = config.system, self.reps[0]
         self.O = self.Oa  # (image observations: their flat row)
@@ -512,8 +516,12 @@ class MATLearner(PPOLearner):
         self.Bm = self.T * self.E // self.M  # (t, env) samples per minibatch
         self.actor_network = MATActor(self.net, self.ctx, d, self.acting)
         self.roll = self.actor_network.pass_for(self.E)
-        self.train = MATPass(self.net, self.Bm, d, True, self.ctx)
-        rows = self.train.rows
+        self._train: Optional[MATPass] = None  # the training tape: built when a minibatch first runs on it
+        rows = pad32(self.Bm * self.A)
+        if self.training == "fused":
+            self._alloc_fused(rows)
+        else:
+            self._build_tape()
         self.grad_scale = float(2 ** math.ceil(math.log2(rows)))
         self.dlogits = torch.zeros(rows * self.nA, device=d)
         self.dvalues = torch.zeros(rows, device=d)
@@ -522,9 +530,36 @@ class MATLearner(PPOLearner):
         self.dls_partials = torch.zeros((self.loss_blocks, self.nA), device=d) if self.continuous else None  # d loss / d log_std per block
         self.debug: Optional[Dict[str, list]] = None  # tests: {"grads": [], "perms": [], "state": []} records every minibatch (and "slot0")
 
+    def _build_tape(self) -> MATPass:
+        if self._train is None:
+            self._train = MATPass(self.net, self.Bm, self.device, True, self.ctx)
+        return self._train
+
+    @property
+    def train(self) -> MATPass:
+        return self._build_tape()
+
+    def _alloc_fused(self, rows: int) -> None:
+        """Outputs, slab and workspace of the fused training launches, once."""
+        d, net = self.device, self.net
+        self.f_blocks = max(1, min(256, -(-self.Bm // max(1, 32 // self.A))))  # one block per group of samples
+        need = int(lib().mava_transformer_train_workspace_bytes(self.Bm, self.A, self.O, self.D, self.n_block, self.f_blocks))
+        self.f_ok = need > 0  # False: the kernel has no instance for this width or depth, every minibatch runs on the tape
+        if not self.f_ok:
+            return
+        self.f_idx = torch.zeros(self.Bm, dtype=torch.int32, device=d)
+        self.f_logits = torch.zeros(rows * self.nA, device=d)
+        self.f_value = torch.zeros(rows, device=d)
+        self.f_slab = torch.zeros((self.f_blocks, self.P), device=d)
+        self.f_ws = torch.zeros(need, dtype=torch.uint8, device=d)
+
     def _refuse(self, env, config) -> None:
         head = dict(config.network.get("action_head", None) or {})
+        if self.training not in TRAINING:
+            raise MavaHipError(f"ff_mat: network.training must be one of {TRAINING}, got {self.training!r}")
         if "ContinuousActionHead" in str(head.get("_target_", "")):
+            if self.training == "fused":
+                raise MavaHipError("ff_mat: network.training=fused is not implemented for a continuous action head")
             if not getattr(env, "continuous_actions", False):  # its step kernel would read the f32 action vectors as int32 indices
                 raise MavaHipError("ff_mat: a continuous action head is not implemented for an environment with discrete actions "
                                    "(the environment does not set continuous_actions; env=spread does)")
@@ -578,12 +613,41 @@ class MATLearner(PPOLearner):
         ops.gae(rep.reward.view(T, EA), rep.value.view(T, EA), rep.done.view(T, EA), rep.last_val.view(EA), float(s.gamma),
                 float(s.gae_lambda), out=(rep.adv.view(T, EA), rep.tgt.view(T, EA)), ctx=self.ctx)
 
+    def _minibatch_fused(self, perm_mb: torch.Tensor) -> bool:
+        """Forward launch, the loss launch, backward launch and the slab sum into g; False (nothing launched) when the kernel
+        has no instance for this network."""
+        if not self.f_ok:
+            return False
+        s, rep, T, Bm, net, L = self.config.system, self.rep, self.T, self.Bm, self.net, lib()
+        rows, TE = self.dvalues.numel(), T * self.E
+        self.f_idx.copy_(perm_mb)
+        shape = (Bm, self.A, net.O, net.nA, net.D, net.H, net.n_block)
+        launch("mat_train_fwd", L.mava_transformer_train_fwd_f32, ptr(self.p), ptr(rep.agents_view[:T]), TE, ptr(self.f_idx),
+               ptr(rep.action), *shape, ptr(self.f_logits), ptr(self.f_value), self.f_blocks, stream_ptr())
+        ops.adv_stats(rep.adv.view(-1), self.f_idx, 0, Bm, self.A, out=self.stats)
+        launch("mat_loss", L.mava_mat_loss_f32, Bm, self.A, self.nA, rows, ptr(self.f_idx), ptr(self.f_logits), ptr(self.f_value),
+               ptr(rep.action_mask[:T]), ptr(rep.action), ptr(rep.log_prob), ptr(rep.adv), ptr(rep.value), ptr(rep.tgt), ptr(self.stats),
+               self.stats.shape[0], float(s.clip_eps), float(s.ent_coef), float(s.vf_coef), self.grad_scale, ptr(self.dlogits),
+               ptr(self.dvalues), ptr(self.partials), self.loss_blocks, stream_ptr())
+        ops.slab_reduce(self.partials, 3, self.g[self.P : self.P + 3])
+        launch("mat_train_bwd", L.mava_transformer_train_bwd_f32, ptr(self.p), ptr(rep.agents_view[:T]), TE, ptr(self.f_idx),
+               ptr(rep.action), *shape, ptr(self.dlogits), ptr(self.dvalues), self.grad_scale, ptr(self.f_slab), self.f_slab.shape[1],
+               ptr(self.f_ws), self.f_ws.numel(), self.f_blocks, stream_ptr())
+        ops.slab_reduce(self.f_slab, self.P, self.g[: self.P])
+        return True
+
     def _minibatch(self, n: int, k: int, mb: int, perm: torch.Tensor) -> None:
-        s, rep, tr, T, Bm = self.config.system, self.rep, self.train, self.T, self.Bm
+        s, rep, T, Bm = self.config.system, self.rep, self.T, self.Bm
         if self.debug is not None:
             if mb == 0:
                 self.debug["perms"].append(perm.clone())
             self.debug["state"].append((self.p.clone(), self.m.clone(), self.v.clone()))
+        if self.training == "fused" and self._minibatch_fused(perm[mb * Bm : (mb + 1) * Bm]):
+            if self.debug is not None:
+                self.debug["grads"].append(self.g.clone())
+            self._clip_adam(n, k, mb)
+            return
+        tr = self.train
         tr.idx[:Bm].copy_(perm[mb * Bm : (mb + 1) * Bm])
         tr.gather_obs(rep.agents_view[:T], T * self.E)
         tr.shift_onehot(rep.action, self.A - 1, True)

@@ -5,6 +5,8 @@
     python tools/mat_bench.py --curve [--acting fused] [--out profiles/mat_learning_curve_fused.json]
     python tools/mat_bench.py --continuous [--envs 1024] [--out profiles/mat_continuous_bench.json]
     python tools/mat_bench.py --continuous --curve [--out profiles/mat_continuous_learning_curve.json]
+    python tools/mat_bench.py --acting fused --training both [--out profiles/mat_train_bench.json]
+    python tools/mat_bench.py --curve --acting fused --training fused [--out profiles/mat_learning_curve_train_fused.json]
 
 Default mode: ms per update and library calls per update of ff_mat at its defaults on env=rware tiny-4ag, ff_mappo
 (update_batch_size 1) in the same run for scale, and the per-launch HIP-event times of the attention and LayerNorm kernels at
@@ -16,6 +18,8 @@ tests/test_gpu_mat_fused_act.py; with --acting only that setting runs.
 env-steps and the same seed - with the bar the test holds ff_mat to.
 --continuous: the same two measurements for the continuous action head on env=spread (CONT_CURVE): ff_mat
 network=continuous_transformer against ff_mappo network=continuous_mlp, update cost layer-wise against fused.
+--training layerwise|fused|both: network.training of ff_mat (csrc/mat_train.hip); `both` runs the two settings in one process
+and adds the HIP-event time per forward / backward launch and the library calls per minibatch.
 """
 from __future__ import annotations
 
@@ -55,7 +59,8 @@ def _setup(system: str, dev, c=CURVE):
                                         f"system.actor_lr={c['lr']}", f"system.critic_lr={c['lr']}",
                                         f"arch.num_eval_episodes={c['eval_envs']}"]
                   + list(c.get("overrides", {}).get(system, []))
-                  + ([f"network.acting={c['acting']}"] if system == "ff_mat" and c.get("acting") else []))
+                  + ([f"network.acting={c['acting']}"] if system == "ff_mat" and c.get("acting") else [])
+                  + ([f"network.training={c['training']}"] if system == "ff_mat" and c.get("training") else []))
     cfg.system.num_updates_per_eval = c["updates_per_call"]
     env, eval_env = envs.make(cfg, add_global_state=system == "ff_mappo", device=dev)
     learn, actor_network, state = mod.learner_setup(env, (c["seed"], c["seed"] + 2, c["seed"] + 3), cfg, device=dev)
@@ -85,9 +90,11 @@ def learning_curve(system: str, dev, log=None, c=CURVE) -> dict:
     return {"curve": curve, "final_sem": sem}
 
 
-def learning_run(dev, log=None, acting=None, curve=CURVE) -> dict:
+def learning_run(dev, log=None, acting=None, curve=CURVE, training=None) -> dict:
     """Both systems on `curve`, and the bar: ff_mat's gain must reach BAR_FACTOR of ff_mappo's."""
     c = curve if acting is None else dict(curve, acting=acting)
+    if training is not None:
+        c = dict(c, training=training)
     out = {"config": c, "bar_factor": BAR_FACTOR, "env_steps": c["calls"] * c["updates_per_call"] * c["rollout"] * c["envs"]}
     for system in ("ff_mappo", "ff_mat"):
         t0 = time.perf_counter()
@@ -125,11 +132,13 @@ class _CallCounter:
 ACT_SYMBOLS = ("mava_transformer_act_f32", "mava_transformer_act_continuous_f32")
 
 
-def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None, continuous: bool = False) -> dict:
+def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None, continuous: bool = False, training=None) -> dict:
     base = dict(CONT_CURVE_3A) if continuous else dict(CURVE, env="rware", scenario="tiny-4ag")
     c = dict(base, envs=envs_, rollout=128, updates_per_call=1, lr=2.5e-4, eval_envs=32)
     if acting is not None:
         c["acting"] = acting
+    if training is not None:
+        c["training"] = training
     cfg, learn, state, _ = _setup(system, dev, c)
     state = learn(state).learner_state  # warm-up (and ff_mappo's graph capture needs two calls)
     state = learn(state).learner_state
@@ -156,6 +165,11 @@ def update_cost(system: str, envs_: int, dev, steps: int = 3, acting=None, conti
         extra["library_calls_outside_rollout"] = cc.n - rollout_calls
         if L.acting == "fused":
             extra["fused_act_us_per_launch"] = _fused_step_us(L)
+        if training is not None:
+            extra["training"] = L.training
+            extra["library_calls_per_minibatch"] = _minibatch_calls(L)
+            if L.training == "fused":
+                extra["train_launch_us"] = _train_launch_us(learn, state)
     return {"system": system, "envs": envs_, **extra, "agents": L.A, "rollout_length": L.T, "ms_per_update": round(1e3 * sorted(times)[len(times) // 2], 3),
             "ms_per_update_all": [round(1e3 * t, 3) for t in times], "env_steps_per_s": round(L.T * L.E / sorted(times)[len(times) // 2]),
             "library_calls_per_update": cc.n, "library_calls_by_symbol": dict(sorted(cc.by.items(), key=lambda kv: -kv[1]))}
@@ -175,6 +189,32 @@ def _fused_step_us(L, reps: int = 30) -> float:
         b.record()
     torch.cuda.synchronize()
     return round(sorted(1e3 * a.elapsed_time(b) for a, b in ev)[reps // 2], 2)
+
+
+def _minibatch_calls(L) -> int:
+    """Library calls of one minibatch of the learner (its parameters move by one Adam step)."""
+    perm = torch.randperm(L.T * L.E, device=L.device).to(torch.int32)
+    with _CallCounter() as cc:
+        L._minibatch(0, 0, 0, perm)
+        torch.cuda.synchronize()
+    return cc.n
+
+
+def _train_launch_us(learn, state) -> dict:
+    """Median HIP-event time (us, includes the Python launch cost) of the fused forward and backward launches over one update."""
+    from mava_amd import _lib
+
+    _lib.TIMERS = {}
+    try:
+        learn(state)
+        torch.cuda.synchronize()
+        out = {}
+        for k in ("mat_train_fwd", "mat_train_bwd"):
+            us = sorted(1e3 * a.elapsed_time(b) for a, b in _lib.TIMERS.get(k, []))
+            out[k] = {"launches": len(us), "median_us": round(us[len(us) // 2], 1) if us else None}
+        return out
+    finally:
+        _lib.TIMERS = None
 
 
 def fused_accuracy(dev) -> dict:
@@ -236,6 +276,8 @@ def main() -> None:
     ap.add_argument("--calls", type=int, default=None, help="--curve: learn() calls (the budget), default the curve's")
     ap.add_argument("--acting", choices=("layerwise", "fused"), default=None, help="network.acting of ff_mat (default: the "
                     "config's in --curve mode, both settings otherwise)")
+    ap.add_argument("--training", choices=("layerwise", "fused", "both"), default=None, help="network.training of ff_mat; both: the "
+                    "two settings in one process (update cost mode)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -248,7 +290,8 @@ def main() -> None:
         curve = CONT_CURVE if args.continuous else CURVE
         if args.calls:
             curve = dict(curve, calls=args.calls)
-        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True), acting=args.acting, curve=curve)
+        out = learning_run(dev, log=lambda m: print(m, file=sys.stderr, flush=True), acting=args.acting, curve=curve,
+                           training=None if args.training == "both" else args.training)
         out["device"] = torch.cuda.get_device_name(0)
         if args.continuous:
             log = lambda m: print(m, file=sys.stderr, flush=True)
@@ -265,6 +308,14 @@ def main() -> None:
         by = {r.get("acting"): r for r in results if r["system"] == "ff_mat"}
         if len(by) == 2:
             out["fused_speedup_per_update"] = round(by["layerwise"]["ms_per_update"] / by["fused"]["ms_per_update"], 2)
+    elif args.training:
+        trainings = ["layerwise", "fused"] if args.training == "both" else [args.training]
+        results = [update_cost("ff_mat", args.envs, dev, acting=args.acting, training=t) for t in trainings]
+        results.append(update_cost("ff_mappo", args.envs, dev))
+        out = {"device": torch.cuda.get_device_name(0), "workload": f"env=rware tiny-4ag x {args.envs} envs, defaults", "results": results}
+        by = {r.get("training"): r for r in results if r["system"] == "ff_mat"}
+        if len(by) == 2:
+            out["fused_training_speedup_per_update"] = round(by["layerwise"]["ms_per_update"] / by["fused"]["ms_per_update"], 2)
     else:
         settings = [args.acting] if args.acting else ["layerwise", "fused"]
         results = [update_cost("ff_mat", args.envs, dev, acting=a) for a in settings] + [update_cost("ff_mappo", args.envs, dev)]
