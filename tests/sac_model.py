@@ -14,13 +14,29 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from oracle.philox import philox4x32_10
+from oracle.philox import philox4x32_10, u01_open
 
 THRESH = float(np.float32(0.999))  # the kernels clip at the float32 constant
 ATANH_THRESH = math.atanh(0.999)
 LOG_EPS = math.log(1.0 - 0.999)
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 ITEM_STREAM = 0x53414342  # "SACB"
+NOISE_STREAM = 0x5341434E  # "SACN"
+
+
+# ---- the noise ----------------------------------------------------------------------------------------------------------
+def sac_noise(seed: int, step: int, rows: int, action_dim: int, row_offset: int = 0) -> np.ndarray:
+    """(rows, action_dim) float64: the standard normals of mava_sac_sample_f32 and of the fused kernels.  Component d of
+    row r comes from the Philox block (row_offset + r, step, d >> 1, "SACN") under the seed key: words (x, y) for an even
+    d, (z, w) for an odd one, through Box-Muller's cosine branch on the open 24-bit uniforms, evaluated in float64."""
+    gid = (np.arange(rows, dtype=np.uint64) + np.uint64(row_offset)).astype(np.uint32)
+    out = np.empty((rows, action_dim), np.float64)
+    for c in range((action_dim + 1) // 2):
+        w = philox4x32_10(gid, np.uint32(step & 0xFFFFFFFF), c, NOISE_STREAM, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+        for odd in range(min(2, action_dim - 2 * c)):
+            a, b = u01_open(w[2 * odd]).astype(np.float64), u01_open(w[2 * odd + 1]).astype(np.float64)
+            out[:, 2 * c + odd] = np.sqrt(-2.0 * np.log(a)) * np.cos(2.0 * np.pi * b)
+    return out
 
 
 # ---- the distribution ---------------------------------------------------------------------------------------------------

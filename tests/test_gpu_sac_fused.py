@@ -1,7 +1,8 @@
 """GPU: the fused soft actor-critic kernels (csrc/sac_fused.hip) through the C ABI against tests/sac_model.py (float64) at
 the project's f16x2 gradient tolerance (1e-4 of rms), then a whole train step with MAVA_SAC_FUSED=1
 and the fallback outside the envelope.  Shapes: (A 3, D 2, B 12) two tiles of 30 and 6 real rows; (A 2, D 1, B 16) a full
-tile; (A 5, D 16, B 7) the widest action, MASAC's Kq = 100.  Input widths 15 and 16 sit on and past a 16-deep k-step."""
+tile; (A 5, D 16, B 7) the widest action, MASAC's Kq = 100.  Input widths 15 and 16 sit on and past a 16-deep k-step.
+The edges of the envelope, the noise and the refusals are in tests/test_gpu_sac_fused_edges.py."""
 import math
 
 import numpy as np
@@ -32,9 +33,9 @@ def _flat(net: sm.Net, gen, head_scale=1.0):
     return torch.cat(parts).float().double()  # float32 values: the kernels and the model see the same numbers
 
 
-def _case(dev, case, joint, head_scale=1.0):
+def _case(dev, case, joint, head_scale=1.0, seed=None):
     A, D, B, O, S = case
-    gen = torch.Generator().manual_seed(7 + A + D)
+    gen = torch.Generator().manual_seed(7 + A + D if seed is None else seed)
     Kq = S + A * D if joint else O + D
     model = sm.Sac(sm.Net(O, [128, 128], [D, D]), sm.Net(Kq, [128, 128], [1]), A, D, joint, GAMMA, MIN_SCALE, -float(D))
     p = {"actor": _flat(model.actor, gen, head_scale), "log_alpha": torch.tensor([0.3, -0.2, 0.1, 0.25, -0.15][:A], dtype=torch.float64)}
@@ -152,6 +153,26 @@ def test_fused_train_step_gradients_match_the_model(dev, system, monkeypatch):
     for k in ("q1", "q2"):
         assert_close(_np(after[k + "_t"]), _np(sm.polyak(after[k], before[k + "_t"], L.tau)), 1e-6, f"{k} target")
     assert L.count.tolist() == [1, 1, 1]
+
+
+@pytest.mark.parametrize("system", ["ff_isac", "ff_masac"])
+def test_fused_policy_delay_two_repeats_the_update_with_the_same_noise(dev, system, monkeypatch):
+    """test_gpu_sac's test of the same name, on the fused path."""
+    monkeypatch.setenv("MAVA_SAC_FUSED", "1")
+    _cfg, learn, L, state = _setup(dev, system, ["system.policy_update_delay=2", "system.autotune=false"])
+    assert L.fused
+    learn.explore()
+    before = _params(L)
+    learn(state)  # t = 64 entering the update: 64 % 2 == 0, the actor trains - twice
+    torch.cuda.synchronize()
+    after, dbg = _params(L), L.debug
+    assert sm.policy_fires(64, 2) and len(dbg["g_actor"]) == 2 and L.count.tolist() == [2, 1, 0]
+    assert torch.equal(dbg["eps_actor"][0], dbg["eps_actor"][1]) and not torch.equal(dbg["g_actor"][0], dbg["g_actor"][1])
+    for k in ("q1", "q2"):
+        assert_close(_np(after[k + "_t"]), _np(sm.polyak(after[k], before[k + "_t"], L.tau)), 1e-6, f"{k} target")
+    # autotune off: log_alpha keeps log(init_alpha) and reports no alpha loss
+    assert torch.equal(after["log_alpha"], before["log_alpha"]) and abs(float(after["log_alpha"][0]) - math.log(0.1)) < 1e-6
+    assert float(L.train_metrics[0, 0, 5]) == 0.0 and dbg["g_alpha"] == []
 
 
 def test_outside_the_envelope_the_layer_wise_path_runs(dev, monkeypatch):

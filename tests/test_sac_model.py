@@ -86,6 +86,25 @@ def test_policy_delay_reads_the_env_step_counter():
     assert sm.policy_fires(7, 1)
 
 
+def test_sac_noise_is_box_muller_over_the_philox_words():
+    from oracle.philox import philox4x32_10, u01_open
+
+    seed, step = 0x1234567890ABCDEF, 6
+    e = sm.sac_noise(seed, step, 4096, 5)
+    # one entry by hand: row 37, component 3 is odd, so words (z, w) of block 3 >> 1 = 1
+    w = philox4x32_10(37, step, 1, 0x5341434E, 0x90ABCDEF, 0x12345678)
+    a, b = float(u01_open(w[2])), float(u01_open(w[3]))
+    assert e[37, 3] == np.sqrt(-2.0 * np.log(a)) * np.cos(2.0 * np.pi * b)
+    # standard normals, the components and the rows apart from each other, bounded as 24-bit uniforms bound them
+    assert abs(e.mean()) < 0.03 and abs(e.std() - 1.0) < 0.03 and np.abs(e).max() < 5.8
+    assert abs(np.corrcoef(e[:, 0], e[:, 1])[0, 1]) < 0.06 and abs(np.corrcoef(e[:-1, 2], e[1:, 2])[0, 1]) < 0.06
+    # the counters: a row offset shifts rows, another step or seed draws other numbers, the width only cuts columns off
+    assert np.array_equal(sm.sac_noise(seed, step, 64, 5, row_offset=32), e[32:96])
+    assert np.array_equal(sm.sac_noise(seed, step, 4096, 4), e[:, :4])
+    assert not np.array_equal(sm.sac_noise(seed, step + 1, 4096, 5), e) and not np.array_equal(sm.sac_noise(seed + 1, step, 4096, 5), e)
+    assert not np.array_equal(e[:32], e[32:64])
+
+
 def test_ring_and_sampled_items_across_a_wrap():
     cap, E = 64, 24
     head, stored = 0, {}
