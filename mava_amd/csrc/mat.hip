@@ -35,21 +35,16 @@
 #include <cfloat>
 
 #include "common.h"
+#include "mat_layout.h"
 #include "mat_rows.h"
 #include "tanh_normal.h"
 
 namespace {
 
-constexpr int TILE = 32;
-constexpr int MAX_A = 32;
-constexpr int MAX_D = 128;
-constexpr int LDQ = MAX_D + 1;   // LDS row stride of a staged (rows x hd) tile: rows fall on different banks
-constexpr int LDP = MAX_A + 1;   // LDS row stride of the (rows x A) score tile
-constexpr int MAX_ACT = 64;
-constexpr int MAX_DIM = 16;       // action dimensions of the continuous head (the limit of the other continuous kernels)
-constexpr double LN_EPS = 1e-6;  // flax.linen.LayerNorm default epsilon
+using namespace mat;
 
-__device__ __forceinline__ long t32(long row, long f, long N) { return ((row >> 5) * N + f) * 32 + (row & 31); }
+constexpr int TILE = 32;
+constexpr int LDQ = MAX_D + 1;   // LDS row stride of a staged (rows x hd) tile: rows fall on different banks
 
 struct AttnTask {
   const float *q, *k, *v, *dy;
@@ -292,22 +287,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   }
 }
 
-// flax nn.gelu(approximate=True): 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))
-constexpr double GELU_C = 0.7978845608028654, GELU_K = 0.044715;
-
 __global__ __launch_bounds__(256) void gelu_kernel(const float* __restrict__ x, long n, float* __restrict__ y) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const double v = (double)x[i];
-    y[i] = (float)(0.5 * v * (1.0 + tanh(GELU_C * (v + GELU_K * v * v * v))));
-  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = gelu_f(x[i]);
 }
 
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, long n,
                                                        float* __restrict__ dx) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const double v = (double)x[i];
-    const double t = tanh(GELU_C * (v + GELU_K * v * v * v));
-    const double d = 0.5 * (1.0 + t) + 0.5 * v * (1.0 - t * t) * GELU_C * (1.0 + 3.0 * GELU_K * v * v);
+    const double d = gelu_d(x[i]);
     dx[i] = (float)((double)dy[i] * d);
   }
 }

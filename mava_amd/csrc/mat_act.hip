@@ -37,21 +37,13 @@
 #include <cfloat>
 
 #include "common.h"
+#include "mat_layout.h"
 #include "mat_rows.h"
 #include "tanh_normal.h"
 
 namespace {
 
-constexpr int ROWS = 32;
-constexpr int MAX_A = 32;
-constexpr int MAX_D = 128;
-constexpr int MAX_ACT = 64;
-constexpr int MAX_DIM = 16;    // action dimensions of the continuous head
-constexpr int MAX_O = 1024;
-constexpr int MAX_NBLOCK = 4;  // decoder blocks the kernel takes; beyond that the caller runs layer by layer
-constexpr int LDP = MAX_A + 1;
-constexpr double LN_EPS = 1e-6;
-constexpr double GELU_C = 0.7978845608028654, GELU_K = 0.044715;
+using namespace mat;
 
 struct ActTask {
   const float* params;
@@ -66,28 +58,6 @@ struct ActTask {
   float* action_f;  // continuous head: (B, A, nA) f32 actions, nA = the action dimension
   float min_scale;
 };
-
-__host__ __device__ inline long enc_block_size(long D) { return 6 * D * D + 10 * D; }
-__host__ __device__ inline long dec_block_size(long D) { return 10 * D * D + 16 * D; }
-__host__ __device__ inline long enc_size(long O, long D, long nb) {
-  return 2 * O + O * D + D + 2 * D + nb * enc_block_size(D) + D * D + D + 2 * D + D + 1;
-}
-__host__ __device__ inline long dec_size(long nA, long D, long nb) {
-  return (nA + 1) * D + 2 * D + nb * dec_block_size(D) + D * D + D + 2 * D + D * nA + nA;
-}
-
-__device__ __forceinline__ float gelu_f(float x) {
-  const double v = (double)x;
-  return (float)(0.5 * v * (1.0 + tanh(GELU_C * (v + GELU_K * v * v * v))));
-}
-
-// sum over the 8 lanes of a row, the same bits on each of them
-__device__ __forceinline__ double sum8(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
 
 // out[o0 + r * os][n] = f(bias[n] + sum_k in[i0 + r * is][k] W[k][n]), r < nr <= NJ * NS.  `in` rows have stride D + 1 (LDS).
 template <int D, int NJ, bool GELU>
@@ -157,16 +127,6 @@ __device__ __forceinline__ void ln_rows(const float* x, int x0, int xs, const fl
       const double xh = ((double)(rp != nullptr ? xp[f] + rp[f] : xp[f]) - mean) * rstd;
       out[r * LD + f] = (float)fma(xh, (double)scale[f], (double)bias[f]);
     }
-}
-
-struct AttnW {
-  const float *qw, *qb, *kw, *kb, *vw, *vb, *pw, *pb;
-};
-
-template <int D>
-__device__ __forceinline__ AttnW attn_w(const float* a) {
-  constexpr long DD = (long)D * D;
-  return {a, a + DD, a + DD + D, a + 2 * DD + D, a + 2 * DD + 2 * D, a + 3 * DD + 2 * D, a + 3 * DD + 3 * D, a + 4 * DD + 3 * D};
 }
 
 // softmax in place over s[0 .. n), f64
@@ -263,7 +223,10 @@ template <int D, bool CONT>
 __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int LD = D + 1, NS = 256 / D, RPT = ROWS / NS;
-  constexpr long DD = (long)D * D;
+  using At = Attn<D>;
+  using EB = EncBlock<D>;
+  using DB = DecBlock<D>;
+  using HD = Head<D>;
   double* const s_sc = reinterpret_cast<double*>(lds);  // [32][33] scores / probabilities
   double* const s_mom = s_sc + ROWS * LDP;               // [32] mean, [32] rstd of the observation rows
   float* const X = reinterpret_cast<float*>(s_mom + 2 * ROWS);  // encoder: x, then rep
@@ -282,11 +245,11 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
   const float* const e_obs_b = e_obs_w + (long)O * D;
   const float* const e_ln = e_obs_b + D;
   const float* const e_blk = e_ln + 2 * D;
-  const float* const e_head = e_blk + nb * enc_block_size(D);
-  const float* const dec = enc + enc_size(O, D, nb);
+  const float* const e_head = e_blk + nb * EB::size;
+  const float* const dec = e_head + head_size(D, 1);
   const float* const d_ln = dec + (long)(nA + 1) * D;
   const float* const d_blk = d_ln + 2 * D;
-  const float* const d_head = d_blk + nb * dec_block_size(D);
+  const float* const d_head = d_blk + nb * DB::size;
   float* const cache = a.cache + (long)blockIdx.x * nb * 4 * ROWS * D;
 
   const long groups = ((long)a.B + S - 1) / S;
@@ -353,31 +316,31 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
     ln_rows<D>(T, 0, 1, nullptr, 0, 0, X, e_ln, e_ln + D, nr);
     __syncthreads();
     for (int l = 0; l < nb; ++l) {
-      const float* const bp = e_blk + l * enc_block_size(D);
-      const AttnW w = attn_w<D>(bp);
-      dense<D, false>(w.qw, w.qb, X, 0, 1, Q, LD, 0, 1, nr);
-      dense<D, false>(w.kw, w.kb, X, 0, 1, K, LD, 0, 1, nr);
-      dense<D, false>(w.vw, w.vb, X, 0, 1, V, LD, 0, 1, nr);
+      const float* const bp = e_blk + l * EB::size;
+      const float* const w = bp + EB::attn;
+      dense<D, false>(w + At::q_w, w + At::q_b, X, 0, 1, Q, LD, 0, 1, nr);
+      dense<D, false>(w + At::k_w, w + At::k_b, X, 0, 1, K, LD, 0, 1, nr);
+      dense<D, false>(w + At::v_w, w + At::v_b, X, 0, 1, V, LD, 0, 1, nr);
       __syncthreads();
       attn_full<D>(a, Q, K, V, s_sc, nr);
-      dense<D, false>(w.pw, w.pb, Q, 0, 1, T, LD, 0, 1, nr);
+      dense<D, false>(w + At::proj_w, w + At::proj_b, Q, 0, 1, T, LD, 0, 1, nr);
       __syncthreads();
-      ln_rows<D>(T, 0, 1, X, 0, 1, X, bp + 4 * DD + 4 * D, bp + 4 * DD + 5 * D, nr);
+      ln_rows<D>(T, 0, 1, X, 0, 1, X, bp + EB::ln1, bp + EB::ln1 + D, nr);
       __syncthreads();
-      dense<D, true>(bp + 4 * DD + 6 * D, bp + 5 * DD + 6 * D, X, 0, 1, Q, LD, 0, 1, nr);
+      dense<D, true>(bp + EB::mlp0_w, bp + EB::mlp0_b, X, 0, 1, Q, LD, 0, 1, nr);
       __syncthreads();
-      dense<D, false>(bp + 5 * DD + 7 * D, bp + 6 * DD + 7 * D, Q, 0, 1, T, LD, 0, 1, nr);
+      dense<D, false>(bp + EB::mlp1_w, bp + EB::mlp1_b, Q, 0, 1, T, LD, 0, 1, nr);
       __syncthreads();
-      ln_rows<D>(T, 0, 1, X, 0, 1, X, bp + 6 * DD + 8 * D, bp + 6 * DD + 9 * D, nr);
+      ln_rows<D>(T, 0, 1, X, 0, 1, X, bp + EB::ln2, bp + EB::ln2 + D, nr);
       __syncthreads();
     }
     // value = Dense(1)(LN(GELU(Dense(rep))))
-    dense<D, true>(e_head, e_head + DD, X, 0, 1, Q, LD, 0, 1, nr);
+    dense<D, true>(e_head + HD::dense_w, e_head + HD::dense_b, X, 0, 1, Q, LD, 0, 1, nr);
     __syncthreads();
-    ln_rows<D>(Q, 0, 1, nullptr, 0, 0, T, e_head + DD + D, e_head + DD + 2 * D, nr);
+    ln_rows<D>(Q, 0, 1, nullptr, 0, 0, T, e_head + HD::ln, e_head + HD::ln + D, nr);
     __syncthreads();
     if (a.value != nullptr && tid < nr) {
-      const float* hw = e_head + DD + 3 * D;
+      const float* hw = e_head + HD::out_w;
       float acc = 0.0f;
       for (int k = 0; k < D; ++k) acc = fmaf(T[tid * LD + k], hw[k], acc);
       a.value[row0 + tid] = acc + hw[D];
@@ -390,7 +353,7 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
     float* const TR = T;  // branch output
     for (int i = 0; i < A; ++i) {
       if constexpr (CONT) {
-        const float* const ab = dec + (long)nA * D;  // act_dense's bias follows its (nA x D) kernel
+        const float* const ab = dec + (long)nA * D;  // act_dense's bias follows its (nA x D) kernel: Layout::act_bias
         for (int e = tid; e < ns * D; e += 256) {
           const int s = e / D, d = e - s * D;
           float acc = 0.0f;
@@ -411,42 +374,42 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
       ln_rows<D>(QR, 0, 1, nullptr, 0, 0, XR, d_ln, d_ln + D, ns);
       __syncthreads();
       for (int l = 0; l < nb; ++l) {
-        const float* const bp = d_blk + l * dec_block_size(D);
+        const float* const bp = d_blk + l * DB::size;
         float* const ck = cache + (long)l * 4 * ROWS * D;
-        const AttnW w1 = attn_w<D>(bp);
-        dense<D, false>(w1.qw, w1.qb, XR, 0, 1, QR, LD, 0, 1, ns);
-        dense<D, false>(w1.kw, w1.kb, XR, 0, 1, ck, D, i, A, ns);
-        dense<D, false>(w1.vw, w1.vb, XR, 0, 1, ck + ROWS * D, D, i, A, ns);
+        const float* const w1 = bp + DB::attn1;
+        dense<D, false>(w1 + At::q_w, w1 + At::q_b, XR, 0, 1, QR, LD, 0, 1, ns);
+        dense<D, false>(w1 + At::k_w, w1 + At::k_b, XR, 0, 1, ck, D, i, A, ns);
+        dense<D, false>(w1 + At::v_w, w1 + At::v_b, XR, 0, 1, ck + ROWS * D, D, i, A, ns);
         __syncthreads();
         attn_cached<D>(a, QR, ck, ck + ROWS * D, s_sc, ns, i);
-        dense<D, false>(w1.pw, w1.pb, QR, 0, 1, TR, LD, 0, 1, ns);
+        dense<D, false>(w1 + At::proj_w, w1 + At::proj_b, QR, 0, 1, TR, LD, 0, 1, ns);
         __syncthreads();
-        ln_rows<D>(TR, 0, 1, XR, 0, 1, XR, bp + 4 * DD + 4 * D, bp + 4 * DD + 5 * D, ns);
+        ln_rows<D>(TR, 0, 1, XR, 0, 1, XR, bp + DB::ln1, bp + DB::ln1 + D, ns);
         __syncthreads();
-        const AttnW w2 = attn_w<D>(bp + 4 * DD + 6 * D);
-        dense<D, false>(w2.qw, w2.qb, X, i, A, QR, LD, 0, 1, ns);
-        dense<D, false>(w2.kw, w2.kb, XR, 0, 1, ck + 2 * ROWS * D, D, i, A, ns);
-        dense<D, false>(w2.vw, w2.vb, XR, 0, 1, ck + 3 * ROWS * D, D, i, A, ns);
+        const float* const w2 = bp + DB::attn2;
+        dense<D, false>(w2 + At::q_w, w2 + At::q_b, X, i, A, QR, LD, 0, 1, ns);
+        dense<D, false>(w2 + At::k_w, w2 + At::k_b, XR, 0, 1, ck + 2 * ROWS * D, D, i, A, ns);
+        dense<D, false>(w2 + At::v_w, w2 + At::v_b, XR, 0, 1, ck + 3 * ROWS * D, D, i, A, ns);
         __syncthreads();
         attn_cached<D>(a, QR, ck + 2 * ROWS * D, ck + 3 * ROWS * D, s_sc, ns, i);
-        dense<D, false>(w2.pw, w2.pb, QR, 0, 1, TR, LD, 0, 1, ns);
+        dense<D, false>(w2 + At::proj_w, w2 + At::proj_b, QR, 0, 1, TR, LD, 0, 1, ns);
         __syncthreads();
-        ln_rows<D>(TR, 0, 1, X, i, A, XR, bp + 8 * DD + 10 * D, bp + 8 * DD + 11 * D, ns);
+        ln_rows<D>(TR, 0, 1, X, i, A, XR, bp + DB::ln2, bp + DB::ln2 + D, ns);
         __syncthreads();
-        dense<D, true>(bp + 8 * DD + 12 * D, bp + 9 * DD + 12 * D, XR, 0, 1, QR, LD, 0, 1, ns);
+        dense<D, true>(bp + DB::mlp0_w, bp + DB::mlp0_b, XR, 0, 1, QR, LD, 0, 1, ns);
         __syncthreads();
-        dense<D, false>(bp + 9 * DD + 13 * D, bp + 10 * DD + 13 * D, QR, 0, 1, TR, LD, 0, 1, ns);
+        dense<D, false>(bp + DB::mlp1_w, bp + DB::mlp1_b, QR, 0, 1, TR, LD, 0, 1, ns);
         __syncthreads();
-        ln_rows<D>(TR, 0, 1, XR, 0, 1, XR, bp + 10 * DD + 14 * D, bp + 10 * DD + 15 * D, ns);
+        ln_rows<D>(TR, 0, 1, XR, 0, 1, XR, bp + DB::ln3, bp + DB::ln3 + D, ns);
         __syncthreads();
       }
-      dense<D, true>(d_head, d_head + DD, XR, 0, 1, QR, LD, 0, 1, ns);
+      dense<D, true>(d_head + HD::dense_w, d_head + HD::dense_b, XR, 0, 1, QR, LD, 0, 1, ns);
       __syncthreads();
-      ln_rows<D>(QR, 0, 1, nullptr, 0, 0, TR, d_head + DD + D, d_head + DD + 2 * D, ns);
+      ln_rows<D>(QR, 0, 1, nullptr, 0, 0, TR, d_head + HD::ln, d_head + HD::ln + D, ns);
       __syncthreads();
       {
-        const float* hw = d_head + DD + 3 * D;
-        const float* hb = hw + (long)D * nA;
+        const float* hw = d_head + HD::out_w;
+        const float* hb = hw + (long)D * nA;  // HD::out_b(nA)
         for (int e = tid; e < ns * nA; e += 256) {
           const int s = e / nA, o = e - s * nA;
           float acc = 0.0f;
@@ -458,7 +421,7 @@ __global__ __launch_bounds__(256) void mat_act_kernel(ActTask a) {
       if constexpr (CONT) {
         if (tid < ns) {
           const long row = (b0 + tid) * A + i;
-          const float* const ls = d_head + DD + 3 * D + (long)D * nA + nA;  // decoder/log_std: the last leaf
+          const float* const ls = d_head + HD::out_w + (long)D * nA + nA;  // decoder/log_std, the last leaf: Layout::log_std
           const uint32_t gid = a.row_offset + (uint32_t)row;
           float lp = 0.0f;
           for (int o = 0; o < nA; ++o) {
@@ -503,7 +466,7 @@ int launch_act(const ActTask& a, int n_blocks, hipStream_t s) {
 
 extern "C" long mava_transformer_param_count(int O, int n_actions, int D, int n_block) {
   if (O < 1 || n_actions < 1 || D < 1 || n_block < 0) return -1;
-  return enc_size(O, D, n_block) + dec_size(n_actions, D, n_block);
+  return Layout(O, n_actions, D, n_block, false).total;
 }
 
 extern "C" size_t mava_transformer_act_workspace_bytes(int B, int A, int D, int n_block, int n_blocks) {
@@ -548,7 +511,7 @@ extern "C" int mava_transformer_act_f32(const float* params, const float* agents
 
 extern "C" long mava_transformer_param_count_continuous(int O, int action_dim, int D, int n_block) {
   if (O < 1 || action_dim < 1 || D < 1 || n_block < 0) return -1;
-  return enc_size(O, D, n_block) + dec_size(action_dim, D, n_block) + action_dim;
+  return Layout(O, action_dim, D, n_block, true).total;
 }
 
 extern "C" int mava_transformer_act_continuous_f32(const float* params, const float* agents_view, int B, int A, int O, int action_dim,

@@ -5,11 +5,10 @@
 // HBM, written by one launch and read by the next - runs here per group of samples inside one workgroup.  A sample's A agent
 // rows only interact with each other (attention over the agents), so a group never needs another group's rows.
 //
-// Work split (mat_act.hip's).  A group is S = max(1, 32 / A) consecutive minibatch samples, R = S * A <= 32 agent rows; the
-// padding rows of a partial group are exact zeros in every tile.  Groups are dealt to the workgroups round robin in a
-// persistent loop; a group is computed the same way whichever workgroup takes it and every sum has a fixed order: logits and
-// values are bit-identical for any grid.  No grid barrier, no atomics; every barrier sits under block-uniform control flow
-// (the loops run over groups, layers, heads and column chunks; nr is a per-group number).
+// Work split (mat_act.hip's).  A group is S = max(1, 32 / A) consecutive minibatch samples, R = S * A <= 32 agent rows; the padding
+// rows of a partial group are exact zeros in every tile.  Groups are dealt to the workgroups round robin in a persistent loop; a
+// group is computed the same way whichever workgroup takes it and every sum has a fixed order: logits and values are bit-identical
+// for any grid.  No grid barrier, no atomics; every barrier sits under block-uniform control flow (nr is a per-group number).
 //
 // Inputs in place.  Row b * A + j of the minibatch reads agent j of trajectory sample idx[b]; the decoder's input row is row 0
 // (start token) or row 1 + action[idx[b]][j - 1] of decoder/act_dense/kernel, and its gradient is a row scatter-add into the
@@ -29,40 +28,30 @@
 //  GELU, saves the activation and zeroes the padding rows (Grp::take).
 //  Like mat_act.hip the kernel does not follow the context's matmul mode: its products are exact f32.
 //
-// Between the products: mat.hip's arithmetic.  f32 storage; LayerNorm's moments (8 lanes per row, a butterfly of shuffles),
-// its backward row sums, the softmax with its exp, the attention dot products over hd and GELU's tanh in f64; the
-// probabilities are computed again in the backward half; eps 1e-6; tanh-form GELU.  The two heads' last layers (D x 1 and
-// D x n_actions) are plain f32 FMA loops.
+// Between the products: mat.hip's arithmetic.  f32 storage; LayerNorm's moments (8 lanes per row, a butterfly of shuffles), its
+// backward row sums, the softmax with its exp, the attention dot products over hd and GELU's tanh in f64; the probabilities are
+// computed again in the backward half.  The two heads' last layers (D x 1 and D x n_actions) are plain f32 FMA loops.
 //
-// BWD instance.  It recomputes the group's forward pass and saves every activation the backward half needs in a
-// workgroup-private region of the caller's workspace ((12 + 26 n_block) slots of 32 x D + 32 floats, overwritten group
-// after group), then walks the network in reverse: decoder head, decoder blocks, embedding rows, encoder (the gradient of
-// `rep` is collected in a slot of its own: value head first, then every decoder block's cross attention and second
-// LayerNorm).  A slot is read for rows < nr only and after this launch wrote it.  dlogits / dvalues are scaled by
-// 1 / grad_scale as they are read (a power of two in the learner: exact), so the slab holds the gradient itself.
-// The slab row is zeroed in the prologue (a workgroup without groups leaves exact zeros) and every element of it is only
-// ever touched by the one lane that owns it.
+// BWD instance.  It recomputes the group's forward pass, saves every activation the backward half needs in a workgroup-private
+// region of the caller's workspace (mat_layout.h's slots, overwritten group after group; a slot is read for rows < nr only and
+// after this launch wrote it), then walks the network in reverse.  dlogits / dvalues are scaled by 1 / grad_scale as they are read
+// (a power of two in the learner: exact), so the slab holds the gradient itself.  The slab row is zeroed in the prologue (a
+// workgroup without groups leaves exact zeros) and every element of it is only ever touched by the one lane that owns it.
 //
 // LDS: six (32 x (D + 1)) tiles, the KS partial tiles, the two f64 score tiles (32 x 33; the staged W chunk aliases them),
 // the logits tile (32 x 64): 141 568 bytes at D = 128, 92 544 at D = 64 (dynamic, the attribute is raised).
 #include <cfloat>
 
+#include "mat_layout.h"
 #include "mlp_core.h"
 
 namespace {
 
-constexpr int ROWS = 32;
-constexpr int MAX_A = 32;
-constexpr int MAX_D = 128;
-constexpr int MAX_ACT = 64;
-constexpr int MAX_O = 1024;
-constexpr int MAX_NBLOCK = 4;
-constexpr int LDP = MAX_A + 1;  // row stride of the score tiles and of the staged W chunk
-constexpr double LN_EPS = 1e-6;
+using namespace mat;
+
 // phases of the stamps: recomputed forward, dW products on the slab row (with their staging), dX products (with W's staging and the
 // partial-tile pass), LayerNorm and GELU backward, attention backward (with the q / k / v loads), the rest
 enum { ST_FWD, ST_DW, ST_DX, ST_ELEM, ST_ATTN, ST_OTHER, ST_N };
-constexpr double GELU_C = 0.7978845608028654, GELU_K = 0.044715;
 
 struct TrainTask {
   const float* params;
@@ -81,37 +70,6 @@ struct TrainTask {
   float* slab;            // BWD: n_blocks x slab_stride
   long slab_stride, P;
 };
-
-__host__ __device__ inline long enc_block_size(long D) { return 6 * D * D + 10 * D; }
-__host__ __device__ inline long dec_block_size(long D) { return 10 * D * D + 16 * D; }
-__host__ __device__ inline long enc_size(long O, long D, long nb) {
-  return 2 * O + O * D + D + 2 * D + nb * enc_block_size(D) + D * D + D + 2 * D + D + 1;
-}
-__host__ __device__ inline long dec_size(long nA, long D, long nb) {
-  return (nA + 1) * D + 2 * D + nb * dec_block_size(D) + D * D + D + 2 * D + D * nA + nA;
-}
-__host__ __device__ inline int n_slots(int nb) { return 12 + 26 * nb; }
-
-__device__ __forceinline__ long t32(long row, long f, long N) { return ((row >> 5) * N + f) * 32 + (row & 31); }
-
-__device__ __forceinline__ float gelu_f(float x) {
-  const double v = (double)x;
-  return (float)(0.5 * v * (1.0 + tanh(GELU_C * (v + GELU_K * v * v * v))));
-}
-
-__device__ __forceinline__ double gelu_d(float x) {
-  const double v = (double)x;
-  const double t = tanh(GELU_C * (v + GELU_K * v * v * v));
-  return 0.5 * (1.0 + t) + 0.5 * v * (1.0 - t * t) * GELU_C * (1.0 + 3.0 * GELU_K * v * v);
-}
-
-// sum over the 8 lanes of a row, the same bits on each of them
-__device__ __forceinline__ double sum8(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
 
 // The thread index behind an empty asm: address arithmetic derived from it stays next to its use.  Without it the compiler hoists
 // every helper call's per-thread LDS addresses out of the group loop and keeps hundreds of them live across it (scratch).
@@ -478,12 +436,11 @@ struct Grp {
   // parameters and their slab; s0: its slots q, k, v, y.  On exit (a barrier) G = dq, V = dk, DV = dv, and proj's gradients are in.
   __device__ __forceinline__ void attn_core_bwd(float* G, float* B, float* Q, float* K, float* V, float* DV, const float* aw, float* as,
                                                 int s0, bool causal) const {
-    constexpr long DD = (long)D * D;
-    dense_dw(slot(s0 + 3), Q, G, as + 3 * DD + 3 * D, as + 4 * DD + 3 * D);
-    dx(G, aw + 3 * DD + 3 * D, B, false);
-    load(Q, slot(s0));
-    load(K, slot(s0 + 1));
-    load(V, slot(s0 + 2));
+    dense_dw(slot(s0 + AS::y), Q, G, as + Attn<D>::proj_w, as + Attn<D>::proj_b);
+    dx(G, aw + Attn<D>::proj_w, B, false);
+    load(Q, slot(s0 + AS::q));
+    load(K, slot(s0 + AS::k));
+    load(V, slot(s0 + AS::v));
     __syncthreads();
     attn_bwd(B, Q, K, V, DV, causal);
     stamp(ST_ATTN);
@@ -501,7 +458,10 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   using G_ = Grp<D>;
   constexpr int LD = G_::LD, TILE = G_::TILE;
-  constexpr long DD = (long)D * D;
+  using At = Attn<D>;
+  using EB = EncBlock<D>;
+  using DB = DecBlock<D>;
+  using HD = Head<D>;
   double* const s_sc = reinterpret_cast<double*>(lds);
   double* const s_sd = s_sc + ROWS * LDP;
   double* const s_mom = s_sd + ROWS * LDP;  // [32] mean, [32] rstd of the observation rows
@@ -520,12 +480,10 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
   const int A = a.A, O = a.O, nA = a.nA, nb = a.nb, S = a.S;
 
   const long oE_w0 = 2 * (long)O, oE_b0 = oE_w0 + (long)O * D, oE_ln = oE_b0 + D, oE_blk = oE_ln + 2 * D;
-  const long EB = enc_block_size(D), DB = dec_block_size(D);
-  const long oE_head = oE_blk + nb * EB, oDec = oE_head + DD + 4 * D + 1;
-  const long oD_ln = oDec + (long)(nA + 1) * D, oD_blk = oD_ln + 2 * D, oD_head = oD_blk + nb * DB;
-  // slots: encoder [h0, xhat0, x0 | per block q k v y xhat1 x1 h g xhat2 x2 | head h xhat y], decoder [xhat0, x0 | per block
-  // q1 k1 v1 y1 xhat1 x1 q2 k2 v2 y2 xhat2 x2 h g xhat3 x3 | head h xhat y], d rep
-  const int eh = 3 + 10 * nb, db0 = eh + 3, dh = db0 + 2 + 16 * nb, s_grep = dh + 3, s_rep = 3 + 10 * (nb - 1) + 9;
+  const long oE_head = oE_blk + nb * EB::size, oDec = oE_head + head_size(D, 1);
+  const long oD_ln = oDec + (long)(nA + 1) * D, oD_blk = oD_ln + 2 * D, oD_head = oD_blk + nb * DB::size;
+  const int eh = slot::enc_head(nb), db0 = slot::dec_in(eh), dh = slot::dec_head(db0, nb), s_grep = slot::d_rep(dh);
+  const int s_rep = slot::enc_blk(nb - 1) + ES::x2;  // the encoder's output
 
   G_ g;
   g.pb = s_pb;
@@ -619,34 +577,34 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
       }
       g.put(C);
       __syncthreads();
-      g.template take<true>(T, false, p + oE_b0, g.slot(0), nullptr);
+      g.template take<true>(T, false, p + oE_b0, g.slot(slot::enc_h0), nullptr);
       __syncthreads();
     }
-    g.ln(T, nullptr, X, p + oE_ln, g.slot(1), g.slot(2));
+    g.ln(T, nullptr, X, p + oE_ln, g.slot(slot::enc_xhat0), g.slot(slot::enc_x0));
     __syncthreads();
     for (int l = 0; l < nb; ++l) {
-      const float* const bp = p + oE_blk + l * EB;
-      const int s0 = 3 + 10 * l;
-      g.template dense<false>(X, bp, bp + DD, Q, nullptr, g.slot(s0));
-      g.template dense<false>(X, bp + DD + D, bp + 2 * DD + D, K, nullptr, g.slot(s0 + 1));
-      g.template dense<false>(X, bp + 2 * DD + 2 * D, bp + 3 * DD + 2 * D, V, nullptr, g.slot(s0 + 2));
-      g.attn(Q, K, V, false, g.slot(s0 + 3));
-      g.template dense<false>(Q, bp + 3 * DD + 3 * D, bp + 4 * DD + 3 * D, T, nullptr, nullptr);
-      g.ln(T, X, X, bp + 4 * DD + 4 * D, g.slot(s0 + 4), g.slot(s0 + 5));
+      const float* const bp = p + oE_blk + l * EB::size;
+      const int s0 = slot::enc_blk(l);
+      g.template dense<false>(X, bp, bp + At::q_b, Q, nullptr, g.slot(s0 + ES::q));
+      g.template dense<false>(X, bp + At::k_w, bp + At::k_b, K, nullptr, g.slot(s0 + ES::k));
+      g.template dense<false>(X, bp + At::v_w, bp + At::v_b, V, nullptr, g.slot(s0 + ES::v));
+      g.attn(Q, K, V, false, g.slot(s0 + ES::y));
+      g.template dense<false>(Q, bp + At::proj_w, bp + At::proj_b, T, nullptr, nullptr);
+      g.ln(T, X, X, bp + EB::ln1, g.slot(s0 + ES::xhat1), g.slot(s0 + ES::x1));
       __syncthreads();
-      g.template dense<true>(X, bp + 4 * DD + 6 * D, bp + 5 * DD + 6 * D, Q, g.slot(s0 + 6), g.slot(s0 + 7));
-      g.template dense<false>(Q, bp + 5 * DD + 7 * D, bp + 6 * DD + 7 * D, T, nullptr, nullptr);
-      g.ln(T, X, X, bp + 6 * DD + 8 * D, g.slot(s0 + 8), g.slot(s0 + 9));
+      g.template dense<true>(X, bp + EB::mlp0_w, bp + EB::mlp0_b, Q, g.slot(s0 + ES::h), g.slot(s0 + ES::g));
+      g.template dense<false>(Q, bp + EB::mlp1_w, bp + EB::mlp1_b, T, nullptr, nullptr);
+      g.ln(T, X, X, bp + EB::ln2, g.slot(s0 + ES::xhat2), g.slot(s0 + ES::x2));
       __syncthreads();
     }
     {  // value = Dense(1)(LN(GELU(Dense(rep))))
       const float* const hp = p + oE_head;
-      g.template dense<true>(X, hp, hp + DD, Q, g.slot(eh), nullptr);
-      g.ln(Q, nullptr, T, hp + DD + D, g.slot(eh + 1), g.slot(eh + 2));
+      g.template dense<true>(X, hp, hp + HD::dense_b, Q, g.slot(eh + HS::h), nullptr);
+      g.ln(Q, nullptr, T, hp + HD::ln, g.slot(eh + HS::xhat), g.slot(eh + HS::y));
       __syncthreads();
       if constexpr (!BWD) {
         if (tid < nr) {
-          const float* hw = hp + DD + 3 * D;
+          const float* hw = hp + HD::out_w;
           float acc = 0.0f;
           for (int k = 0; k < D; ++k) acc = fmaf(T[tid * LD + k], hw[k], acc);
           a.value[row0 + tid] = acc + hw[D];
@@ -660,39 +618,39 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
       T[r * LD + n] = r < nr ? gelu_f(p[oDec + (long)s_tok[r] * D + n]) : 0.0f;
     }
     __syncthreads();
-    g.ln(T, nullptr, Y, p + oD_ln, g.slot(db0), g.slot(db0 + 1));
+    g.ln(T, nullptr, Y, p + oD_ln, g.slot(db0), g.slot(slot::dec_x0(db0)));
     __syncthreads();
     for (int l = 0; l < nb; ++l) {
-      const float* const bp = p + oD_blk + l * DB;
-      const float* const a2 = bp + 4 * DD + 6 * D;
-      const int s0 = db0 + 2 + 16 * l;
-      g.template dense<false>(Y, bp, bp + DD, Q, nullptr, g.slot(s0));
-      g.template dense<false>(Y, bp + DD + D, bp + 2 * DD + D, K, nullptr, g.slot(s0 + 1));
-      g.template dense<false>(Y, bp + 2 * DD + 2 * D, bp + 3 * DD + 2 * D, V, nullptr, g.slot(s0 + 2));
-      g.attn(Q, K, V, true, g.slot(s0 + 3));
-      g.template dense<false>(Q, bp + 3 * DD + 3 * D, bp + 4 * DD + 3 * D, T, nullptr, nullptr);
-      g.ln(T, Y, Y, bp + 4 * DD + 4 * D, g.slot(s0 + 4), g.slot(s0 + 5));
+      const float* const bp = p + oD_blk + l * DB::size;
+      const float* const a2 = bp + DB::attn2;
+      const int s0 = slot::dec_blk(db0, l);
+      g.template dense<false>(Y, bp, bp + At::q_b, Q, nullptr, g.slot(s0 + DS::q1));
+      g.template dense<false>(Y, bp + At::k_w, bp + At::k_b, K, nullptr, g.slot(s0 + DS::k1));
+      g.template dense<false>(Y, bp + At::v_w, bp + At::v_b, V, nullptr, g.slot(s0 + DS::v1));
+      g.attn(Q, K, V, true, g.slot(s0 + DS::y1));
+      g.template dense<false>(Q, bp + At::proj_w, bp + At::proj_b, T, nullptr, nullptr);
+      g.ln(T, Y, Y, bp + DB::ln1, g.slot(s0 + DS::xhat1), g.slot(s0 + DS::x1));
       __syncthreads();
-      g.template dense<false>(X, a2, a2 + DD, Q, nullptr, g.slot(s0 + 6));
-      g.template dense<false>(Y, a2 + DD + D, a2 + 2 * DD + D, K, nullptr, g.slot(s0 + 7));
-      g.template dense<false>(Y, a2 + 2 * DD + 2 * D, a2 + 3 * DD + 2 * D, V, nullptr, g.slot(s0 + 8));
-      g.attn(Q, K, V, true, g.slot(s0 + 9));
-      g.template dense<false>(Q, a2 + 3 * DD + 3 * D, a2 + 4 * DD + 3 * D, T, nullptr, nullptr);
-      g.ln(T, X, Y, bp + 8 * DD + 10 * D, g.slot(s0 + 10), g.slot(s0 + 11));
+      g.template dense<false>(X, a2, a2 + At::q_b, Q, nullptr, g.slot(s0 + DS::q2));
+      g.template dense<false>(Y, a2 + At::k_w, a2 + At::k_b, K, nullptr, g.slot(s0 + DS::k2));
+      g.template dense<false>(Y, a2 + At::v_w, a2 + At::v_b, V, nullptr, g.slot(s0 + DS::v2));
+      g.attn(Q, K, V, true, g.slot(s0 + DS::y2));
+      g.template dense<false>(Q, a2 + At::proj_w, a2 + At::proj_b, T, nullptr, nullptr);
+      g.ln(T, X, Y, bp + DB::ln2, g.slot(s0 + DS::xhat2), g.slot(s0 + DS::x2));
       __syncthreads();
-      g.template dense<true>(Y, bp + 8 * DD + 12 * D, bp + 9 * DD + 12 * D, Q, g.slot(s0 + 12), g.slot(s0 + 13));
-      g.template dense<false>(Q, bp + 9 * DD + 13 * D, bp + 10 * DD + 13 * D, T, nullptr, nullptr);
-      g.ln(T, Y, Y, bp + 10 * DD + 14 * D, g.slot(s0 + 14), g.slot(s0 + 15));
+      g.template dense<true>(Y, bp + DB::mlp0_w, bp + DB::mlp0_b, Q, g.slot(s0 + DS::h), g.slot(s0 + DS::g));
+      g.template dense<false>(Q, bp + DB::mlp1_w, bp + DB::mlp1_b, T, nullptr, nullptr);
+      g.ln(T, Y, Y, bp + DB::ln3, g.slot(s0 + DS::xhat3), g.slot(s0 + DS::x3));
       __syncthreads();
     }
     {
       const float* const hp = p + oD_head;
-      g.template dense<true>(Y, hp, hp + DD, Q, g.slot(dh), nullptr);
-      g.ln(Q, nullptr, T, hp + DD + D, g.slot(dh + 1), g.slot(dh + 2));
+      g.template dense<true>(Y, hp, hp + HD::dense_b, Q, g.slot(dh + HS::h), nullptr);
+      g.ln(Q, nullptr, T, hp + HD::ln, g.slot(dh + HS::xhat), g.slot(dh + HS::y));
       __syncthreads();
       if constexpr (!BWD) {
-        const float* hw = hp + DD + 3 * D;
-        const float* hb = hw + (long)D * nA;
+        const float* hw = hp + HD::out_w;
+        const float* hb = hw + (long)D * nA;  // HD::out_b(nA)
         for (int e = tid; e < nr * nA; e += 256) {
           const int r = e / nA, o = e - r * nA;
           float acc = 0.0f;
@@ -712,10 +670,10 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
       float* const grep = g.slot(s_grep);
       // ---- value head: d rep starts here
       if (tid < ROWS) s_dv[tid] = tid < nr ? a.dvalues[row0 + tid] * a.inv_scale : 0.0f;
-      g.load(Q, g.slot(eh + 2));
+      g.load(Q, g.slot(eh + HS::y));
       __syncthreads();
       {
-        const long oo = oE_head + DD + 3 * D;
+        const long oo = oE_head + HD::out_w;
         if (tid < D) {
           float s = 0.0f;
           for (int r = 0; r < nr; ++r) s = fmaf(s_dv[r], Q[r * LD + tid], s);
@@ -731,10 +689,10 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
         }
       }
       __syncthreads();
-      g.ln_bwd(GX, g.slot(eh + 1), p + oE_head + DD + D, sl + oE_head + DD + D);
-      g.gelu_bwd(GX, g.slot(eh));
+      g.ln_bwd(GX, g.slot(eh + HS::xhat), p + oE_head + HD::ln, sl + oE_head + HD::ln);
+      g.gelu_bwd(GX, g.slot(eh + HS::h));
       __syncthreads();
-      g.dense_dw(g.slot(s_rep), Q, GX, sl + oE_head, sl + oE_head + DD);
+      g.dense_dw(g.slot(s_rep), Q, GX, sl + oE_head, sl + oE_head + HD::dense_b);
       g.dx(GX, p + oE_head, B, false);
       for (int e = tid; e < ROWS * D; e += 256) {
         const int r = e / D, n = e - r * D;
@@ -745,10 +703,10 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
         const int r = e / nA, o = e - r * nA;
         s_log[r * MAX_ACT + o] = r < nr ? a.dlogits[t32(row0 + r, o, nA)] * a.inv_scale : 0.0f;
       }
-      g.load(Q, g.slot(dh + 2));
+      g.load(Q, g.slot(dh + HS::y));
       __syncthreads();
       {
-        const long ow = oD_head + DD + 3 * D;
+        const long ow = oD_head + HD::out_w;
         for (int e = tid; e < D * nA; e += 256) {
           const int k = e / nA, o = e - k * nA;
           float s = 0.0f;
@@ -768,71 +726,71 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
         }
       }
       __syncthreads();
-      g.ln_bwd(GX, g.slot(dh + 1), p + oD_head + DD + D, sl + oD_head + DD + D);
-      g.gelu_bwd(GX, g.slot(dh));
+      g.ln_bwd(GX, g.slot(dh + HS::xhat), p + oD_head + HD::ln, sl + oD_head + HD::ln);
+      g.gelu_bwd(GX, g.slot(dh + HS::h));
       __syncthreads();
-      g.dense_dw(g.slot(db0 + 2 + 16 * (nb - 1) + 15), Q, GX, sl + oD_head, sl + oD_head + DD);
+      g.dense_dw(g.slot(slot::dec_blk(db0, nb - 1) + DS::x3), Q, GX, sl + oD_head, sl + oD_head + HD::dense_b);
       g.dx(GX, p + oD_head, GX, false);
       // ---- decoder blocks
       for (int l = nb - 1; l >= 0; --l) {
-        const long ob = oD_blk + l * DB, o2 = ob + 4 * DD + 6 * D;
+        const long ob = oD_blk + l * DB::size, o2 = ob + DB::attn2;
         const float* const bp = p + ob;
         float* const bs = sl + ob;
-        const int s0 = db0 + 2 + 16 * l, xin = l == 0 ? db0 + 1 : s0 - 1;
-        g.ln_bwd(GX, g.slot(s0 + 14), bp + 10 * DD + 14 * D, bs + 10 * DD + 14 * D);
-        g.dense_dw(g.slot(s0 + 13), Q, GX, bs + 9 * DD + 13 * D, bs + 10 * DD + 13 * D);
-        g.dx(GX, bp + 9 * DD + 13 * D, B, false);
-        g.gelu_bwd(B, g.slot(s0 + 12));
+        const int s0 = slot::dec_blk(db0, l), xin = l == 0 ? slot::dec_x0(db0) : s0 - 1;  // x0, or the block before's x3
+        g.ln_bwd(GX, g.slot(s0 + DS::xhat3), bp + DB::ln3, bs + DB::ln3);
+        g.dense_dw(g.slot(s0 + DS::g), Q, GX, bs + DB::mlp1_w, bs + DB::mlp1_b);
+        g.dx(GX, bp + DB::mlp1_w, B, false);
+        g.gelu_bwd(B, g.slot(s0 + DS::h));
         __syncthreads();
-        g.dense_dw(g.slot(s0 + 11), Q, B, bs + 8 * DD + 12 * D, bs + 9 * DD + 12 * D);
-        g.dx(B, bp + 8 * DD + 12 * D, GX, true);
-        g.ln_bwd(GX, g.slot(s0 + 10), bp + 8 * DD + 10 * D, bs + 8 * DD + 10 * D);  // GX = d(rep + attn2)
+        g.dense_dw(g.slot(s0 + DS::x2), Q, B, bs + DB::mlp0_w, bs + DB::mlp0_b);
+        g.dx(B, bp + DB::mlp0_w, GX, true);
+        g.ln_bwd(GX, g.slot(s0 + DS::xhat2), bp + DB::ln2, bs + DB::ln2);  // GX = d(rep + attn2)
         for (int e = tid; e < ROWS * D; e += 256) {
           const int r = e / D, n = e - r * D;
           if (r < nr) grep[e] += GX[r * LD + n];
         }
-        g.attn_core_bwd(GX, B, Q, K, V, DV, p + o2, sl + o2, s0 + 6, true);
-        g.dense_dw(g.slot(s_rep), Q, B, sl + o2, sl + o2 + DD);  // the query reads rep
+        g.attn_core_bwd(GX, B, Q, K, V, DV, p + o2, sl + o2, s0 + DS::q2, true);
+        g.dense_dw(g.slot(s_rep), Q, B, sl + o2, sl + o2 + At::q_b);  // the query reads rep
         g.dx(B, p + o2, K, false);
         for (int e = tid; e < ROWS * D; e += 256) {
           const int r = e / D, n = e - r * D;
           if (r < nr) grep[e] += K[r * LD + n];
         }
         g.stamp(ST_OTHER);
-        g.load(Q, g.slot(s0 + 5));  // keys and values read x1
+        g.load(Q, g.slot(s0 + DS::x1));  // keys and values read x1
         __syncthreads();
-        g.xtdy(Q, V, sl + o2 + DD + D, D);
-        g.colsum(V, sl + o2 + 2 * DD + D);
-        g.xtdy(Q, DV, sl + o2 + 2 * DD + 2 * D, D);
-        g.colsum(DV, sl + o2 + 3 * DD + 2 * D);
+        g.xtdy(Q, V, sl + o2 + At::k_w, D);
+        g.colsum(V, sl + o2 + At::k_b);
+        g.xtdy(Q, DV, sl + o2 + At::v_w, D);
+        g.colsum(DV, sl + o2 + At::v_b);
         g.stamp(ST_DW);
         {
           f32x16 C = zero16();
-          g.dywt(C, V, p + o2 + DD + D, D);
-          g.dywt(C, DV, p + o2 + 2 * DD + 2 * D, D);
+          g.dywt(C, V, p + o2 + At::k_w, D);
+          g.dywt(C, DV, p + o2 + At::v_w, D);
           g.put(C);
           __syncthreads();
           g.template take<false>(GX, false, nullptr, nullptr, nullptr);  // GX = d x1
           __syncthreads();
           g.stamp(ST_DX);
         }
-        g.ln_bwd(GX, g.slot(s0 + 4), bp + 4 * DD + 4 * D, bs + 4 * DD + 4 * D);
-        g.attn_core_bwd(GX, B, Q, K, V, DV, bp, bs, s0, true);
+        g.ln_bwd(GX, g.slot(s0 + DS::xhat1), bp + DB::ln1, bs + DB::ln1);
+        g.attn_core_bwd(GX, B, Q, K, V, DV, bp, bs, s0 + DS::q1, true);
         g.stamp(ST_OTHER);
         g.load(Q, g.slot(xin));
         __syncthreads();
         g.xtdy(Q, B, bs, D);
-        g.colsum(B, bs + DD);
-        g.xtdy(Q, V, bs + DD + D, D);
-        g.colsum(V, bs + 2 * DD + D);
-        g.xtdy(Q, DV, bs + 2 * DD + 2 * D, D);
-        g.colsum(DV, bs + 3 * DD + 2 * D);
+        g.colsum(B, bs + At::q_b);
+        g.xtdy(Q, V, bs + At::k_w, D);
+        g.colsum(V, bs + At::k_b);
+        g.xtdy(Q, DV, bs + At::v_w, D);
+        g.colsum(DV, bs + At::v_b);
         g.stamp(ST_DW);
         {
           f32x16 C = zero16();
           g.dywt(C, B, bp, D);
-          g.dywt(C, V, bp + DD + D, D);
-          g.dywt(C, DV, bp + 2 * DD + 2 * D, D);
+          g.dywt(C, V, bp + At::k_w, D);
+          g.dywt(C, DV, bp + At::v_w, D);
           g.put(C);
           __syncthreads();
           g.template take<false>(GX, true, nullptr, nullptr, nullptr);
@@ -854,34 +812,34 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
       g.load(GX, grep);
       __syncthreads();
       for (int l = nb - 1; l >= 0; --l) {
-        const long ob = oE_blk + l * EB;
+        const long ob = oE_blk + l * EB::size;
         const float* const bp = p + ob;
         float* const bs = sl + ob;
-        const int s0 = 3 + 10 * l, xin = l == 0 ? 2 : s0 - 1;
-        g.ln_bwd(GX, g.slot(s0 + 8), bp + 6 * DD + 8 * D, bs + 6 * DD + 8 * D);
-        g.dense_dw(g.slot(s0 + 7), Q, GX, bs + 5 * DD + 7 * D, bs + 6 * DD + 7 * D);
-        g.dx(GX, bp + 5 * DD + 7 * D, B, false);
-        g.gelu_bwd(B, g.slot(s0 + 6));
+        const int s0 = slot::enc_blk0 + ES::n * l, xin = l == 0 ? slot::enc_x0 : s0 - 1;  // slot::enc_blk(l); x0, or the block before's x2
+        g.ln_bwd(GX, g.slot(s0 + ES::xhat2), bp + EB::ln2, bs + EB::ln2);
+        g.dense_dw(g.slot(s0 + ES::g), Q, GX, bs + EB::mlp1_w, bs + EB::mlp1_b);
+        g.dx(GX, bp + EB::mlp1_w, B, false);
+        g.gelu_bwd(B, g.slot(s0 + ES::h));
         __syncthreads();
-        g.dense_dw(g.slot(s0 + 5), Q, B, bs + 4 * DD + 6 * D, bs + 5 * DD + 6 * D);
-        g.dx(B, bp + 4 * DD + 6 * D, GX, true);
-        g.ln_bwd(GX, g.slot(s0 + 4), bp + 4 * DD + 4 * D, bs + 4 * DD + 4 * D);
-        g.attn_core_bwd(GX, B, Q, K, V, DV, bp, bs, s0, false);
+        g.dense_dw(g.slot(s0 + ES::x1), Q, B, bs + EB::mlp0_w, bs + EB::mlp0_b);
+        g.dx(B, bp + EB::mlp0_w, GX, true);
+        g.ln_bwd(GX, g.slot(s0 + ES::xhat1), bp + EB::ln1, bs + EB::ln1);
+        g.attn_core_bwd(GX, B, Q, K, V, DV, bp, bs, s0 + ES::q, false);
         g.stamp(ST_OTHER);
         g.load(Q, g.slot(xin));
         __syncthreads();
         g.xtdy(Q, B, bs, D);
-        g.colsum(B, bs + DD);
-        g.xtdy(Q, V, bs + DD + D, D);
-        g.colsum(V, bs + 2 * DD + D);
-        g.xtdy(Q, DV, bs + 2 * DD + 2 * D, D);
-        g.colsum(DV, bs + 3 * DD + 2 * D);
+        g.colsum(B, bs + At::q_b);
+        g.xtdy(Q, V, bs + At::k_w, D);
+        g.colsum(V, bs + At::k_b);
+        g.xtdy(Q, DV, bs + At::v_w, D);
+        g.colsum(DV, bs + At::v_b);
         g.stamp(ST_DW);
         {
           f32x16 C = zero16();
           g.dywt(C, B, bp, D);
-          g.dywt(C, V, bp + DD + D, D);
-          g.dywt(C, DV, bp + 2 * DD + 2 * D, D);
+          g.dywt(C, V, bp + At::k_w, D);
+          g.dywt(C, DV, bp + At::v_w, D);
           g.put(C);
           __syncthreads();
           g.template take<false>(GX, true, nullptr, nullptr, nullptr);
@@ -890,8 +848,8 @@ __global__ __launch_bounds__(256) void mat_train_kernel(TrainTask a) {
         }
       }
       // ---- encoder input: LayerNorm, GELU, obs_dense and obs_ln D features at a time
-      g.ln_bwd(GX, g.slot(1), p + oE_ln, sl + oE_ln);
-      g.gelu_bwd(GX, g.slot(0));
+      g.ln_bwd(GX, g.slot(slot::enc_xhat0), p + oE_ln, sl + oE_ln);
+      g.gelu_bwd(GX, g.slot(slot::enc_h0));
       __syncthreads();
       g.colsum(GX, sl + oE_b0);
       for (int c0 = 0; c0 < O; c0 += D) {
@@ -980,7 +938,7 @@ int train_task(TrainTask& a, const char* who, const float* params, const float* 
   a.Bm = Bm; a.A = A; a.O = O; a.nA = n_actions; a.H = n_head; a.hd = D / n_head; a.nb = n_block;
   a.S = A >= ROWS ? 1 : ROWS / A;
   a.rows = ((long)Bm * A + 31) / 32 * 32;
-  a.P = enc_size(O, D, n_block) + dec_size(n_actions, D, n_block);
+  a.P = Layout(O, n_actions, D, n_block, false).total;
   return MAVA_OK;
 }
 

@@ -102,7 +102,8 @@ def _dense_leaves(name: str, K: int, N: int, scale: float, bias: bool = True):
 def param_spec(O: int, nA: int, D: int, n_block: int, continuous: bool = False):
     """[(tree path, shape, init)] of the flat vector [encoder | decoder]; init: an orthogonal scale, 0.0 or "ones".
     continuous (nA = the action dimension): act_dense reads the nA-wide action vector and has a bias, head_out gives the nA
-    means, and decoder/log_std (nA zeros) is the last leaf."""
+    means, and decoder/log_std (nA zeros) is the last leaf.
+    csrc/mat_layout.h mirrors this order for the fused kernels: change them together."""
     r2 = math.sqrt(2.0)
     enc = _ln_leaves("obs_ln", O) + _dense_leaves("obs_dense", O, D, r2) + _ln_leaves("ln", D)
     for i in range(n_block):

@@ -56,7 +56,8 @@ def resources(src: str, extra=()):
     b = _build_module()
     path = src if os.path.exists(src) else os.path.join(b.CSRC, src)
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = ([b.HIPCC, "-c", path, "-o", os.path.join(tmp, "x.o")] + b.COMMON_FLAGS + b.HIP_FLAGS + b.EXTRA_FLAGS + list(extra)
+        cmd = ([b.HIPCC, "-c", path, "-o", os.path.join(tmp, "x.o")] + b.COMMON_FLAGS + b.HIP_FLAGS
+               + b.FILE_FLAGS.get(os.path.basename(src), []) + b.EXTRA_FLAGS + list(extra)
                + ["-Rpass-analysis=kernel-resource-usage"])
         r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
