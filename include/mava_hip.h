@@ -813,6 +813,27 @@ int mava_qmix_td_f32(int mode, int L, int B, int A, int Rp, int n_actions, int E
                      const float* w1_target, const float* b1_target, const float* w2_target, const float* b2_target, float gamma,
                      float grad_scale, float* dq, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* partials, int nblk,
                      mava_stream_t s);
+/* The qmix train step's whole mixer part in one launch (mava_amd/csrc/qmix_fused.hip), opt-in (MAVA_QMIX_FUSED=1): what
+ * mava_qmix_state_t32_f32, the four hypernetworks' layer-wise forward passes on the online and the target parameters,
+ * mava_qmix_td_f32 (mode 1) and the hypernetworks' backward passes compute together.  obs / next_obs: the time-major sample
+ * (>= L, Rp, O), row-major; the mixer's state of row (t, b) is the A * O floats from obs[t, b * A] on (next_obs for the target
+ * mixer).  q / q_next_online / q_next_target, action, reward, terminal_next, next_mask and the per-row semantics (select,
+ * first argmax, y, loss over the N = L * B real mixer rows) as for mava_qmix_td_f32.  mixer / mixer_target: the flat
+ * parameters [w1 net | b1 dense | w2 net | b2 net], each net [kernel (K, N) | bias | kernel | bias], with
+ * w1 = Dense(A * Em)(relu(Dense(Hh)(s))), b1 = Dense(Em)(s), w2 = Dense(Em)(relu(Dense(Hh)(s))), b2 = Dense(1)(relu(Dense(Em)(s))).
+ * Outputs: dq (T32, every element, in units of grad_scale, 0 off the taken action and on padding rows); slab (n_slab,
+ * slab_stride >= Pm + 3): block i adds the tiles i, i + n_slab, .. of 32 mixer rows into row i in tile order - columns [0, Pm)
+ * the mixer's gradient (unscaled: d loss / d parameter), columns [Pm, Pm + 3) the sums of (q_loss, mean_q, mean_target)
+ * already divided by N; a row without tiles is zeros.  The column sums over the rows (mava_slab_reduce2_f32) are the gradient
+ * and the metrics; no atomics, bit-identical across launches.  Products are f16x2 (hi + lo f16 operands, f32 accumulation),
+ * per-row sums over agents and the embedding f64.  Refused with nothing launched: a context that is not in f16x2 mode,
+ * A outside [1, 16], n_actions outside [1, 32], Em outside [1, 64], Hh outside [1, 128], A * Em > 512, Rp not a multiple of 32
+ * holding B * A, n_slab outside [1, 1024], slab_stride < Pm + 3, a NULL pointer, dq aliasing a Q input.  Any A * O >= 1. */
+int mava_qmix_mixer_update_f32(const mava_ctx* ctx, int L, int B, int A, int O, int Rp, int n_actions, int Em, int Hh,
+                               const float* obs, const float* next_obs, const int32_t* action, const float* reward,
+                               const uint8_t* terminal_next, const uint8_t* next_mask, const float* q, const float* q_next_online,
+                               const float* q_next_target, const float* mixer, const float* mixer_target, float gamma,
+                               float grad_scale, float* dq, float* slab, long slab_stride, int n_slab, mava_stream_t s);
 
 /* ---- soft actor-critic (ff_isac / ff_masac): mava/systems/sac/ff_isac.py:245-384, ff_masac.py,
  *      mava/utils/centralised_training.py (mava_amd/csrc/sac.hip).  The actor (ContinuousActionHead with

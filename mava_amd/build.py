@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "spread.hip",
     "q_learning.hip",
     "qmix.hip",
+    "qmix_fused.hip",
     "sac.hip",
     "sac_fused.hip",
     "rec_dense.hip",

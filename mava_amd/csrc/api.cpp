@@ -122,3 +122,37 @@ extern "C" int mava_ctx_get(const mava_ctx* c, int key, long* value) {
     default: mava_set_error("mava_ctx_get: unknown key %d", key); return MAVA_EARG(2);
   }
 }
+
+// ---- rec_qmix: the fused mixer update (qmix_fused.hip).  The envelope is checked here: nothing is launched on refusal.
+#include "qmix_fused.h"
+
+extern "C" int mava_qmix_mixer_update_f32(const mava_ctx* ctx, int L, int B, int A, int O, int Rp, int n_actions, int Em, int Hh,
+                                          const float* obs, const float* next_obs, const int32_t* action, const float* reward,
+                                          const uint8_t* terminal_next, const uint8_t* next_mask, const float* q,
+                                          const float* q_next_online, const float* q_next_target, const float* mixer,
+                                          const float* mixer_target, float gamma, float grad_scale, float* dq, float* slab,
+                                          long slab_stride, int n_slab, hipStream_t s) {
+  MAVA_ARG_CHECK(ctx != nullptr && ctx->matmul_mode == 1, 0, "mava_qmix_mixer_update_f32: f16x2 products only (a context in f16x2 mode)");
+  MAVA_ARG_CHECK(L >= 1 && B >= 1 && O >= 1 && A >= 1 && A <= QMIX_FUSED_MAX_A && n_actions >= 1 && n_actions <= QMIX_FUSED_MAX_ACTIONS, 1,
+                 "mava_qmix_mixer_update_f32: bad shape L=%d B=%d A=%d O=%d n_actions=%d (1..16 agents, 1..32 actions)", L, B, A, O,
+                 n_actions);
+  MAVA_ARG_CHECK(Em >= 1 && Em <= QMIX_FUSED_MAX_EM, 2, "mava_qmix_mixer_update_f32: Em=%d outside [1, 64]", Em);
+  MAVA_ARG_CHECK(Hh >= 1 && Hh <= QMIX_FUSED_MAX_HH, 3, "mava_qmix_mixer_update_f32: Hh=%d outside [1, 128]", Hh);
+  MAVA_ARG_CHECK(A * Em <= QMIX_FUSED_MAX_AE, 4, "mava_qmix_mixer_update_f32: A*Em=%d above 512", A * Em);
+  MAVA_ARG_CHECK(Rp >= 32 && Rp % 32 == 0 && (long)B * A <= Rp, 5,
+                 "mava_qmix_mixer_update_f32: Rp=%d must be a multiple of 32 holding B*A=%ld rows", Rp, (long)B * A);
+  MAVA_ARG_CHECK((long)A * O <= (1L << 20) && (long)L * Rp * (O > n_actions ? O : n_actions) < (1L << 40), 6,
+                 "mava_qmix_mixer_update_f32: state or batch too large");
+  const long Pm = qmix_mixer_params((long)A * O, A, Em, Hh);
+  MAVA_ARG_CHECK(n_slab >= 1 && n_slab <= QMIX_FUSED_MAX_SLABS && slab_stride >= Pm + 3, 7,
+                 "mava_qmix_mixer_update_f32: n_slab=%d outside [1, 1024] or slab_stride=%ld below the mixer's %ld parameters + 3 metrics",
+                 n_slab, slab_stride, Pm);
+  MAVA_ARG_CHECK(obs && next_obs && action && reward && terminal_next && next_mask && q && q_next_online && q_next_target && mixer &&
+                     mixer_target && dq && slab, 8, "mava_qmix_mixer_update_f32: null pointer");
+  MAVA_ARG_CHECK(dq != q && dq != q_next_online && dq != q_next_target, 9, "mava_qmix_mixer_update_f32: dq must not alias a Q input");
+  MAVA_ARG_CHECK(gamma >= 0.0f && grad_scale > 0.0f, 10, "mava_qmix_mixer_update_f32: gamma=%g or grad_scale=%g out of range", (double)gamma,
+                 (double)grad_scale);
+  const QmixFusedArgs a = {L, B, A, O, Rp, n_actions, Em, Hh, obs, next_obs, action, reward, terminal_next, next_mask, q, q_next_online,
+                           q_next_target, mixer, mixer_target, gamma, grad_scale, dq, slab, slab_stride, n_slab};
+  return mava_qmix_fused_launch(a, s);
+}

@@ -20,16 +20,20 @@ target-update launch.  Launches per train step: mava_replay_sample_f32, the thre
 mava_qmix_state_t32_f32 and the hypernetworks' forward passes (general layer path, `ctx` = this learner's handle) on the
 online and the target parameters, mava_qmix_td_f32 (select + argmax, both mixers, TD error, backward through the online
 mixer: one launch), the hypernetworks' backward passes, backward_sequence, mava_clip_adam, mava_target_update_f32.
+
+Opt-in (MAVA_QMIX_FUSED=1, f16x2, qmix_fused_mode): everything between the forward_sequence chains and backward_sequence is
+mava_qmix_mixer_update_f32 (csrc/qmix_fused.hip) plus one slab sum; no state matrix or hypernet workspace is allocated.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
 from . import ops
-from ._lib import launch, lib, ptr, stream_ptr
+from ._lib import ctx_ptr, launch, lib, ptr, stream_ptr
 from .generic_networks import GenericMLPTorso, GenericNet
 from .iql_learner import IQLLearner
 from .learner_common import bind_learn, pad32
@@ -43,6 +47,18 @@ MAX_AGENTS, MAX_EMBED = 16, 64  # mava_qmix_td_f32's limits
 # at scale 1 the initial |Q_tot| is in the tens against rewards below 1, and the first TD errors, multiplied by grad_scale,
 # leave the f16 range of the f16x2 backward chain.  At 0.1 Q_tot starts O(1) with dQ_tot / dqa_j ~ 1, like vdn.
 OUT_SCALE = 0.1
+# envelope of the fused mixer kernel (csrc/qmix_fused.hip): widths one 32-row tile's forward and backward hold in LDS
+FUSED_MAX_HIDDEN, FUSED_MAX_W1, FUSED_MAX_ACTIONS, FUSED_MAX_SLABS = 128, 512, 32, 256
+
+
+def qmix_fused_mode(matmul_mode: str, mixer_kind: str, A: int, Em: int, Hh: int, n_actions: int, env=None) -> bool:
+    """Whether the train step's mixer part runs as one fused launch (csrc/qmix_fused.hip, mava_qmix_mixer_update_f32)
+    instead of the state gather, the layer-wise hypernetworks and mava_qmix_td_f32: only with MAVA_QMIX_FUSED=1, f16x2
+    arithmetic, the qmix mixer and widths inside the kernel's envelope (any state width)."""
+    env = os.environ if env is None else env
+    return (env.get("MAVA_QMIX_FUSED", "0") == "1" and matmul_mode == "f16x2" and mixer_kind == "qmix" and 1 <= A <= MAX_AGENTS
+            and 1 <= n_actions <= FUSED_MAX_ACTIONS and 1 <= Em <= MAX_EMBED and 1 <= Hh <= FUSED_MAX_HIDDEN
+            and A * Em <= FUSED_MAX_W1)
 
 
 class QMixer:
@@ -143,7 +159,14 @@ class QMIXLearner(IQLLearner):
         self.m, self.v, self.g = torch.zeros(P, device=d), torch.zeros(P, device=d), torch.zeros(P, device=d)
         self.td_blocks = max(1, min(256, -(-self.mrows // 64)))
         self.partials = torch.zeros((self.td_blocks, 3), device=d)
+        self.fused = qmix_fused_mode(self.matmul_mode, self.mixer_kind, A, self.Em, self.Hh, self.nA)  # read once
         if self.mixer is not None:
+            # the hypernetworks' backward runs in the Q network's units (grad_scale); both row counts enter one power of two
+            self.grad_scale = float(2 ** math.ceil(math.log2(max(self.L * self.Rp, self.mrows))))
+        if self.fused:
+            # one gradient slab per persistent block: [mixer gradient | 3 metric sums], summed by one slab_reduce2
+            self.slab = torch.zeros((min(self.mrows // 32, FUSED_MAX_SLABS), self.Pm + 3), device=d)
+        elif self.mixer is not None:
             self.mixer.set_ctx(self.ctx)
             self.mstate = torch.zeros(self.mrows * self.Dsp, device=d)
             self.mstate_next = torch.zeros(self.mrows * self.Dsp, device=d)
@@ -153,8 +176,6 @@ class QMIXLearner(IQLLearner):
             self.d_b1 = torch.zeros(self.mrows * self.Em, device=d)
             self.d_w2 = torch.zeros(self.mrows * self.Em, device=d)
             self.d_b2 = torch.zeros(self.mrows, device=d)
-            # the hypernetworks' backward runs in the Q network's units (grad_scale); both row counts enter one power of two
-            self.grad_scale = float(2 ** math.ceil(math.log2(max(self.L * self.Rp, self.mrows))))
 
     # ------------------------------------------------------------------------------------ setup
     def init_params(self, q_seed: int) -> None:
@@ -190,6 +211,13 @@ class QMIXLearner(IQLLearner):
         ws.dy, the hypernetwork outputs' gradients into d_* - and the hypernetworks' backward into g[Pq:]."""
         L_, s = lib(), stream_ptr()
         Lq, Rp, sm = self.L, self.Rp, self.smp
+        if self.fused:  # the whole mixer part in one launch; the slab sum writes g[Pq:] and the metrics
+            launch("qmix_mixer_update", L_.mava_qmix_mixer_update_f32, ctx_ptr(self.ctx), Lq, self.B, self.A, self.O, Rp, self.nA,
+                   self.Em, self.Hh, ptr(sm.obs[0]), ptr(sm.next_obs[0]), ptr(sm.action), ptr(sm.reward), ptr(sm.terminal[1:]),
+                   ptr(sm.next_obs[1]), ptr(q), ptr(qn), ptr(self.q_target), ptr(self.p[self.Pq :]), ptr(self.pt[self.Pq :]),
+                   self.gamma, self.grad_scale, ptr(self.ws.dy), ptr(self.slab), self.slab.shape[1], self.slab.shape[0], s)
+            ops.slab_reduce2(self.slab, self.Pm, self.g[self.Pq :], 3, self.train_metrics[n, k])
+            return
         hyper: List[Optional[int]] = [None] * 8  # vdn: no hypernetwork outputs
         grads: List[Optional[int]] = [None] * 4
         if self.mixer is not None:

@@ -4,11 +4,13 @@ headline is not involved).
 
     python tools/qmix_bench.py [--out profiles/qmix_bench.json]
     python tools/qmix_bench.py --curve [--out profiles/qmix_learning_curve.json]
+    python tools/qmix_bench.py --fused [--out profiles/qmix_fused_bench.json]
 
 Default mode: tools/iql_bench.py's two shapes - the reference defaults (16 envs, B = 32, L = 20) and the wide one (1024
 envs, B = 256) - for rec_qmix, rec_vdn and rec_iql, each past the train gate: the median time of one update, env-steps/s and
 the library calls per update; then the per-launch time of the two new kernels at each shape (HIP events around the learner's
-own launches).  --curve: the learning runs of tests/test_gpu_qmix_learning.py (rec_iql's overrides, unchanged).
+own launches).  --fused: rec_qmix alone, layer-wise and with MAVA_QMIX_FUSED=1 (csrc/qmix_fused.hip) in one process at both
+shapes.  --curve: the learning runs of tests/test_gpu_qmix_learning.py (rec_iql's overrides, unchanged).
 """
 from __future__ import annotations
 
@@ -48,10 +50,12 @@ def _setup(system, overrides, updates):
     return learn, L, state
 
 
-def bench_shape(system, name, overrides, updates, repeats):
+def bench_shape(system, name, overrides, updates, repeats, fused=False):
     from mava_amd import _lib
 
+    os.environ["MAVA_QMIX_FUSED"] = "1" if fused else "0"  # read once, when the learner is built
     learn, L, state = _setup(system, overrides, updates)
+    assert getattr(L, "fused", False) == fused
     times = []
     for _ in range(repeats):
         t0 = time.perf_counter()
@@ -68,13 +72,15 @@ def bench_shape(system, name, overrides, updates, repeats):
     torch.cuda.synchronize()
     timers, _lib.TIMERS = _lib.TIMERS, None
     per_launch = {k: round(1e3 * statistics.median(a.elapsed_time(b) for a, b in v), 2) for k, v in timers.items()
-                  if k in ("qmix_td", "qmix_state", "q_td_loss")}
+                  if k in ("qmix_td", "qmix_state", "q_td_loss", "qmix_mixer_update")}
     med = statistics.median(times)
     res = {"system": system, "shape": name, "num_envs": L.E, "num_agents": L.A, "rollout_length": L.T, "epochs": L.K,
            "sample_batch_size": L.B, "sample_sequence_length": L.L, "matmul_mode": L.matmul_mode, "params": int(L.p.numel()),
            "median_update_ms": round(med * 1e3, 3), "update_ms_all": [round(x * 1e3, 3) for x in times],
            "env_steps_per_s": round(L.E * L.T / med, 1), "launches_per_update": cnt.n / updates,
            "median_launch_us": per_launch}
+    if system == "rec_qmix":
+        res["fused"] = fused
     if system != "rec_iql":
         res["mixer_rows"], res["mixer_state_dim"], res["td_blocks"] = L.mrows, L.Ds, L.td_blocks
     return res
@@ -102,6 +108,7 @@ def curve(out_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     ap.add_argument("--updates", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -110,6 +117,15 @@ def main():
         curve(a.out or os.path.join(ROOT, "profiles", "qmix_learning_curve.json"))
         return
     res = {"device": torch.cuda.get_device_name(0), "scenario": SCENARIO, "results": []}
+    if a.fused:
+        for name, ov in SHAPES.items():
+            for fused in (False, True):
+                r = bench_shape("rec_qmix", name, ov + ["system.matmul_mode=f16x2"], a.updates, a.repeats, fused)
+                print(json.dumps(r), flush=True)
+                res["results"].append(r)
+        with open(a.out or os.path.join(ROOT, "profiles", "qmix_fused_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     for name, ov in SHAPES.items():
         for system in SYSTEMS:
             r = bench_shape(system, name, ov, a.updates, a.repeats)
